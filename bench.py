@@ -10,7 +10,13 @@ scale, a ~31 GB index built on the GPU in the reference's format and kept reside
 device has >= 64 GB free; 256 otherwise, and the line says so), 30 % of bases in planted repeat
 families (copy number 2-5000, 0-5 % divergence).
 
-The default one-GPU run adds three legs to the same JSON line (skip with --no-extra-legs):
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs: it draws the genome, builds the index
+in HBM (no index directory is written), draws the read batches, warms up, times exactly N steps and prints the line (`metric`, `value`,
+`unit`, `ms_per_step`, `config`, ...).  --dump-outputs DIR also writes what the last timed step computed (dump_outputs()).
+
+Everything else -- the roofline figures and the untimed launches they take, the CPU baseline and the parity check against the
+compiled reference, the extra legs below -- runs only with --full.
+The --full one-GPU run adds three legs to the same JSON line (skip with --no-extra-legs):
   paired       configs[2] (2x150 bp pairs through the paired-end path) over the SAME resident
                index: value, ms_per_step, parity_check and cpu_baseline of its own
   c5           configs[4] on one GPU (2x250 bp pairs, -d 20, insert N(600, 80^2), 0.2 % long
@@ -25,7 +31,7 @@ N > 1: one process per GPU (torch.distributed.run), reads sharded (each rank ali
 --reads reads: weak scaling), no data-path collective; the index is read by rank 0 and
 broadcast once over RCCL into every rank's HBM before the clock starts.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  Extra objects (--full):
   roofline     dominant kernel (k_align_single) against the HBM roofline: algorithmic bytes per
                launch (DESIGN.md "Algorithmic bytes") / average launch duration measured with
                hipEvents on the launch stream inside libsnapgpu.so
@@ -48,6 +54,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md "Chip-level parameters")
+DUMP_MAX_BYTES = 48_000_000    # --dump-outputs: all arrays together stay below this
+DUMP_SEED = 20261015           # --dump-outputs: the sample of units when the whole output is larger
 
 
 _T_PROCESS = time.time()
@@ -85,7 +93,7 @@ def kernel_source_hash():
     return h.hexdigest()[:16]
 
 
-def ensure_index(args, rank, device=0, multi=False, need_dir=True):
+def ensure_index(args, rank, device=0, multi=False, need_dir=True, on_genome=None):
     """Genome + SNAP index directory under /tmp, built once per box.  The directory is in the reference's on-disk format either way:
     --indexer gpu (default) builds it with this repo's GPU index builder (include/snapgpu.h: snapgpu_index_build_from_fasta; parity with
     the reference's builder: tests/test_zx_gpu_index_build.py) and ALSO returns the index still resident in HBM, so that the run aligns
@@ -93,7 +101,8 @@ def ensure_index(args, rank, device=0, multi=False, need_dir=True):
     ~90 s at 256 Mb and ~20 minutes at GRCh38 scale.  The reference (cpu_baseline / parity_check) loads the same directory.
     N > 1 (`multi`): rank 0 draws the genome ONCE and leaves it in a file the other ranks map (they need it to draw their own reads),
     builds the index in its HBM and keeps it there for the RCCL broadcast -- no 31 GB directory is written or read back on that path
-    (only a one-GPU run has a CPU baseline that needs one)."""
+    (only a one-GPU run has a CPU baseline that needs one).  Without `need_dir` a one-process run builds the index in HBM only, too.
+    `on_genome(genome)` is called as soon as the genome exists, so that the caller can draw reads from it while the index is built."""
     from snap_amd import synth
     tag = "g%d_s%d_seed%d_%s" % (args.genome_mb, args.seed_len, args.seed, args.indexer)
     work = os.path.join(args.workdir, tag)
@@ -119,10 +128,12 @@ def ensure_index(args, rank, device=0, multi=False, need_dir=True):
         for nm, ln in meta:
             genome.append((nm, flat[at:at + ln])); at += ln
         log("rank %d: genome mapped from rank 0's file in %.1fs" % (rank, time.time() - t0))
+    if on_genome is not None:
+        on_genome(genome)
     built, info = None, {"indexer": args.indexer, "cached": os.path.exists(done)}
     # A run whose directory is already there (an earlier run on this box) still BUILDS the index in HBM -- 9 s at 3.1 Gb against reading
-    # 31 GB of files back and copying them up -- and just does not save it again; an N > 1 run never saves one.
-    in_hbm_only = args.indexer == "gpu" and (os.path.exists(done) or (multi and not need_dir))
+    # 31 GB of files back and copying them up -- and just does not save it again; a run that needs no directory never saves one.
+    in_hbm_only = args.indexer == "gpu" and (os.path.exists(done) or not need_dir)
     if rank == 0 and (not os.path.exists(done) or in_hbm_only):
         os.makedirs(work, exist_ok=True)
         fa = os.path.join(work, "ref.fa")
@@ -162,6 +173,21 @@ def summarize_launch_profile(lp):
             "worst_reads_fraction_of_longest_wave": [float(lp["wave_worst_read_cycles"][i]) / longest for i in worst_i],
             "worst_reads_ag_calls": [int(lp["wave_worst_read_ag_calls"][i]) for i in worst_i],
             "read_cycles_log2_hist": {str(i): int(v) for i, v in enumerate(lp["read_cycles_log2_hist"]) if v}}
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the result records a caller of the timed path receives (RESULT_DTYPE / PAIRED_RESULT_DTYPE, one per read or pair),
+    one float64 array per field as out_dir/<field>.npy (a pair's two-mate fields have shape (n, 2)).  When the whole batch would exceed
+    DUMP_MAX_BYTES, a fixed sample of units drawn with DUMP_SEED is written instead; out_dir/unit_index.npy says which units they are."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = res.shape[0]
+    per_unit = 8 * (1 + sum(int(np.prod(res.dtype[f].shape)) for f in res.dtype.names))
+    k = min(n, DUMP_MAX_BYTES // per_unit)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    np.save(os.path.join(out_dir, "unit_index.npy"), idx.astype(np.float64))
+    for f in res.dtype.names:
+        np.save(os.path.join(out_dir, f + ".npy"), res[f][idx].astype(np.float64))
+    return k
 
 
 def algorithmic_bytes(c, read_len, n_reads, ref_walk_slots=None):
@@ -220,7 +246,7 @@ def parse_args(argv=None):
     ap.add_argument("--paired-leg-steps", type=int, default=12, help="timed steps of the extra paired-end leg")
     ap.add_argument("--standin-mb", type=int, default=256, help="genome size of the extra `genome_256mb` leg (tests shrink it)")
     ap.add_argument("--standin-leg", action="store_true", help="add the `genome_256mb` leg (the line of rounds 1-3 on the 256 Mb stand-in; in the default run until round 4)")
-    ap.add_argument("--no-c5-leg", action="store_true", help="do not add the `c5` leg (configs[4] on one GPU: 2 x 250 bp pairs, -d 20, insert N(600, 80^2), 0.2 % long indels)")
+    ap.add_argument("--no-c5-leg", action="store_true", help="do not add the `c5` leg (configs[4] on one GPU: 2 x 250 bp pairs, -d 20, insert N(600, 80^2), 0.2 %% long indels)")
     ap.add_argument("--c5-leg-steps", type=int, default=12)
     ap.add_argument("--c5-reads", type=int, default=200_000, help="reads per step of the c5 leg")
     ap.add_argument("--no-e2e-leg", action="store_true", help="do not add the `e2e` leg (FASTQ -> SAM through snap_amd/snapgpu-sam)")
@@ -228,6 +254,13 @@ def parse_args(argv=None):
     ap.add_argument("--e2e-ref-reads", type=int, default=1_000_000, help="leading reads of that FASTQ the reference CLI aligns beside it (its own Reads/s; records compared)")
     ap.add_argument("--e2e-tool-args", default="", help="extra arguments for snapgpu-sam in the e2e leg, one string")
     ap.add_argument("--e2e-passes", type=int, default=3, help="passes of snapgpu-sam over the e2e FASTQ with the index resident (`-passes`): value = the median pass, min / max beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: roofline figures (and their untimed launches), the CPU baseline and parity check against "
+                         "the compiled reference, the index directory on disk and the extra legs; the --skip-* / --no-*-leg / --standin-leg / "
+                         "--cpu-* options apply to this mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result records of the last timed step as DIR/<field>.npy (float64; a fixed, "
+                         "seeded sample of the reads / pairs, DIR/unit_index.npy, when all of them would exceed %d MB)" % (DUMP_MAX_BYTES // 1_000_000))
     args = ap.parse_args(argv)
     if args.steps <= 0:
         args.steps = 6
@@ -240,7 +273,7 @@ class Bed:
     pass
 
 
-def make_bed(args, env, paired_owner):
+def make_bed(args, env, paired_owner, early_batches=False):
     import torch
     from snap_amd import abi
     from snap_amd import dist as sd
@@ -250,12 +283,19 @@ def make_bed(args, env, paired_owner):
     bed = Bed()
     bed.args = args
     bed.pparams = abi.default_paired_params()
+    bed.early_batches = None
     cls = ChimericPairedEndAligner if paired_owner else BaseAligner
     # The index directory is built BEFORE the process group exists: a build can take minutes at GRCh38 scale, and a rank that sits in
     # a collective that long runs into the NCCL watchdog.  Ranks other than 0 wait for the directory's last file on the file system.
-    # (the directory itself is only needed where the reference runs beside the GPU: the CPU baseline of a one-process run)
-    bed.genome, bed.idx_dir, built, bed.index_info = ensure_index(args, rank, local_rank, multi=world > 1 or env["force_dist"],
-                                                                  need_dir=world == 1 and not args.skip_cpu)
+    # (the directory itself is only needed where the reference runs beside the GPU -- the CPU baseline, parity check and e2e leg of a
+    #  --full run -- and a plain run writes none)
+    multi = world > 1 or env["force_dist"]
+
+    def on_genome(genome):          # the line's own leg draws its read batches while the index is built
+        bed.early_batches = start_batches(args, genome, rank, world, args.workload)
+    bed.genome, bed.idx_dir, built, bed.index_info = ensure_index(args, rank, local_rank, multi=multi,
+                                                                  need_dir=args.full and (not multi or (world == 1 and not args.skip_cpu)),
+                                                                  on_genome=on_genome if early_batches else None)
     if (world > 1 or env["force_dist"]) and env.get("dist") is None:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         env["dist"] = sd.init_process_group("nccl")
@@ -314,9 +354,57 @@ def close_bed(bed):
     torch.cuda.empty_cache()
 
 
+def start_batches(args, genome, rank, world, workload):
+    """Start drawing a leg's read batches in a thread pool; returns one future per batch.
+    --batches DISTINCT read batches rotate through the timed steps (step k aligns batch k mod B), so that no step finds the previous
+    step's probes / reference windows in L2 or MALL by construction.  Batch 0 is the first one the parity check and the CPU baseline use."""
+    from concurrent.futures import ThreadPoolExecutor
+    from snap_amd import synth
+    paired = workload == "paired"
+    n_batches = max(1, min(args.batches, args.steps))
+
+    def make_batch(b):
+        sd_ = args.seed + 1000 + rank + 7919 * b
+        if paired:      # FR pairs; C3: insert N(400, 50^2) clipped to [150, 1000] (SURVEY.md 8(d)); C5: N(600, 80^2) + 0.2 % indel events of length 1-10
+            return synth.make_pairs(sd_, genome, args.reads // 2, args.read_len, insert_mean=args.insert_mean, insert_sd=args.insert_sd,
+                                    long_indel_frac=args.long_indel_frac)
+        return synth.make_reads(sd_, genome, args.reads, args.read_len)   # 1% sub, .05% ins/del, 50% RC, Q20-40
+    # (numpy releases the GIL in the large operations: the batches are drawn side by side -- ~5 GB of temporaries each, so fewer at a time
+    #  when several ranks share the host)
+    ex = ThreadPoolExecutor(max_workers=max(1, min(n_batches, 6 if world == 1 else 2)))
+    futs = [ex.submit(make_batch, b) for b in range(n_batches)]
+    ex.shutdown(wait=False)
+    return futs
+
+
+def headline(args, env, bed, paired, n, n_units, n_feed, elapsed):
+    """The line's headline fields -- what a plain run prints and a --full run adds its figures to."""
+    world = env["world"]
+    total_reads = n * world * args.steps
+    value = total_reads / elapsed
+    genome_desc = ("seeded synthetic %d Mb genome with 30%% planted repeats (GRCh38 scale: GRCh38 itself is unavailable here)" % args.genome_mb if args.genome_mb >= 3000
+                   else "seeded synthetic %d Mb genome with 30%% planted repeats (stand-in: %s)" % (args.genome_mb, env.get("genome_choice", "--genome-mb")))
+    return {
+        "metric": "aligned reads/sec (whole node), %d bp %s vs synthetic %d Mb genome (GRCh38 unavailable), seed=20, maxDist=%d"
+                  % (args.read_len, "paired-end (2x%d FR pairs)" % args.read_len if paired else "single-end", args.genome_mb, args.max_k),
+        "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": "u8 bases / int32 DP / f64 match probability", "data": "synthetic",
+        "config": {"workload": ("%s: %d pairs of 2 x %d bp (FR, insert N(%g,%g^2), long-indel fraction %g) per GPU per step, ChimericPairedEndAligner over IntersectingPairedEndAligner defaults (-n 8 -H 4000 -s 0 1000 -i 40, affine gap + soft clipping on), -d %d, index seed %d (directory in the reference's format), genome = %s"
+                                % ("configs[4] on one GPU" if getattr(args, "pmc_tag", "") == "c5" else "configs[2]", n_units, args.read_len, args.insert_mean, args.insert_sd, args.long_indel_frac, args.max_k, args.seed_len, genome_desc)) if paired else
+                               ("configs[1]: %d x %d bp single-end reads per GPU per step, BaseAligner::AlignRead defaults (-n 25 -h 300 -D 1, affine gap on, ALT-aware), -d %d, index seed %d (directory in the reference's format), genome = %s"
+                                % (n, args.read_len, args.max_k, args.seed_len, genome_desc)),
+                   "genome_mb": args.genome_mb, "genome_choice": env.get("genome_choice", "--genome-mb"),
+                   "reads_per_gpu": n, "read_len": args.read_len, "index_bytes_hbm": bed.index_bytes,
+                   "parallelism": "reads sharded over %d GPU(s), index replicated%s" % (world, " by RCCL broadcast" if world > 1 else ""),
+                   "feeders_per_gpu": n_feed, "index_build": bed.index_info, "index_resident_s": getattr(bed, "index_resident_s", None),
+                   "index_path": getattr(bed, "index_path", None), "kernel_source_hash": kernel_source_hash()},
+    }
+
+
 def run_leg(args, env, bed, workload, primary):
-    """One leg = warm-up + exactly args.steps timed steps of `workload` over `bed`, then (rank 0) the untimed diagnostics, the CPU baseline
-    and the parity check.  Returns the JSON object on rank 0, None elsewhere."""
+    """One leg = warm-up + exactly args.steps timed steps of `workload` over `bed`, then -- with --full -- (rank 0) the untimed diagnostics,
+    the CPU baseline and the parity check.  Returns the JSON object on rank 0, None elsewhere."""
     import torch
     from snap_amd import abi, synth
     from snap_amd import dist as sd
@@ -334,23 +422,15 @@ def run_leg(args, env, bed, workload, primary):
             return ChimericPairedEndAligner.over(bed.owner, pparams, params=p_over)
         return bed.owner.replica(params=p_over)
 
-    # --batches DISTINCT read batches rotate through the timed steps (step k aligns batch k mod B), so that no step finds the previous
-    # step's probes / reference windows in L2 or MALL by construction.  Batch 0 is the first one the parity check and the CPU baseline use.
     n_batches = max(1, min(args.batches, args.steps))
-
-    def make_batch(b):
-        sd_ = args.seed + 1000 + rank + 7919 * b
-        if paired:      # FR pairs; C3: insert N(400, 50^2) clipped to [150, 1000]; C5: N(600, 80^2) + 0.2 % indel events of length 1-10
-            return synth.make_pairs(sd_, genome, args.reads // 2, args.read_len, insert_mean=args.insert_mean, insert_sd=args.insert_sd,
-                                    long_indel_frac=args.long_indel_frac)
-        return synth.make_reads(sd_, genome, args.reads, args.read_len)   # 1% sub, .05% ins/del, 50% RC, Q20-40
     t0 = time.time()
-    from concurrent.futures import ThreadPoolExecutor
-    # (numpy releases the GIL in the large operations: the batches are drawn side by side -- ~5 GB of temporaries each, so fewer at a time
-    #  when several ranks share the host)
-    with ThreadPoolExecutor(max_workers=max(1, min(n_batches, 6 if world == 1 else 2))) as ex:
-        batches = list(ex.map(make_batch, range(n_batches)))
-    log("%s: %d read batch(es) generated in %.1fs" % (workload, n_batches, time.time() - t0))
+    pending = getattr(bed, "early_batches", None) if primary else None          # (drawn while the index was built: make_bed)
+    bed.early_batches = None
+    if pending is None:
+        pending = start_batches(args, genome, rank, world, workload)
+    batches = [f_.result() for f_ in pending]
+    del pending
+    log("%s: %d read batch(es) ready after %.1fs" % (workload, n_batches, time.time() - t0))
     reads = batches[0]
     n = args.reads                      # reads per GPU per step (a pair is two reads)
     n_units = n // 2 if paired else n   # alignment problems per launch
@@ -421,6 +501,19 @@ def run_leg(args, env, bed, workload, primary):
     if dist is not None:
         elapsed = sd.max_over_ranks(elapsed, dev)
     log("%s: %d timed steps in %.2fs" % (workload, args.steps, elapsed))
+    if args.dump_outputs and primary and rank == 0:
+        # step steps - 1 was the last one: feeder (steps - 1) mod F ran it, and its result buffer still holds the answer
+        last = np.frombuffer(d_prims[(args.steps - 1) % n_feed].cpu().numpy().tobytes(), dtype=res_dtype)
+        k_ = dump_outputs(args.dump_outputs, last)
+        log("%s: results of the last timed step (%d of its %d %s) written to %s" % (workload, k_, n_units, "pairs" if paired else "reads", args.dump_outputs))
+        del last
+    if not args.full:
+        for a_ in feeders:
+            if a_ is not bed.owner:
+                a_.close()
+        del d_batches, d_prims
+        torch.cuda.empty_cache()
+        return headline(args, env, bed, paired, n, n_units, n_feed, elapsed) if rank == 0 else None
 
     counters = {}
     kernel_ms, launches = sum(m_ for m_, _ in event_ms), sum(n_ for _, n_ in event_ms)
@@ -541,31 +634,14 @@ def run_leg(args, env, bed, workload, primary):
         walker.close()
 
     # ---------------------------------------------------------------- report (rank 0)
-    total_reads = n * world * args.steps
-    value = total_reads / elapsed
     per_launch = {k: v / max(1, launches) for k, v in counters.items()}
     alg_bytes, parts = algorithmic_bytes(per_launch, args.read_len, n, ref_walk_slots)
     avg_ms = kernel_ms / max(1, launches)
     # (with several feeders the launches overlap, so each one's hipEvent time is longer than its share of the chip: the rate is then
     #  taken over the step time, bytes of one batch / (elapsed / steps))
     achieved = alg_bytes / ((avg_ms if n_feed == 1 else 1e3 * elapsed / args.steps) * 1e-3) / 1e9
-    genome_desc = ("seeded synthetic %d Mb genome with 30%% planted repeats (GRCh38 scale: GRCh38 itself is unavailable here)" % args.genome_mb if args.genome_mb >= 3000
-                   else "seeded synthetic %d Mb genome with 30%% planted repeats (stand-in: %s)" % (args.genome_mb, env.get("genome_choice", "--genome-mb")))
-    out = {
-        "metric": "aligned reads/sec (whole node), %d bp %s vs synthetic %d Mb genome (GRCh38 unavailable), seed=20, maxDist=%d"
-                  % (args.read_len, "paired-end (2x%d FR pairs)" % args.read_len if paired else "single-end", args.genome_mb, args.max_k),
-        "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": args.scaling,
-        "vs_baseline": None, "dtype": "u8 bases / int32 DP / f64 match probability", "data": "synthetic",
-        "config": {"workload": ("%s: %d pairs of 2 x %d bp (FR, insert N(%g,%g^2), long-indel fraction %g) per GPU per step, ChimericPairedEndAligner over IntersectingPairedEndAligner defaults (-n 8 -H 4000 -s 0 1000 -i 40, affine gap + soft clipping on), -d %d, index seed %d (directory in the reference's format), genome = %s"
-                                % ("configs[4] on one GPU" if getattr(args, "pmc_tag", "") == "c5" else "configs[2]", n_units, args.read_len, args.insert_mean, args.insert_sd, args.long_indel_frac, args.max_k, args.seed_len, genome_desc)) if paired else
-                               ("configs[1]: %d x %d bp single-end reads per GPU per step, BaseAligner::AlignRead defaults (-n 25 -h 300 -D 1, affine gap on, ALT-aware), -d %d, index seed %d (directory in the reference's format), genome = %s"
-                                % (n, args.read_len, args.max_k, args.seed_len, genome_desc)),
-                   "genome_mb": args.genome_mb, "genome_choice": env.get("genome_choice", "--genome-mb"),
-                   "reads_per_gpu": n, "read_len": args.read_len, "index_bytes_hbm": index_bytes,
-                   "parallelism": "reads sharded over %d GPU(s), index replicated%s" % (world, " by RCCL broadcast" if world > 1 else ""),
-                   "feeders_per_gpu": n_feed, "index_build": index_info, "index_resident_s": getattr(bed, "index_resident_s", None),
-                   "index_path": getattr(bed, "index_path", None), "kernel_source_hash": kernel_source_hash()},
+    out = headline(args, env, bed, paired, n, n_units, n_feed, elapsed)
+    out.update({
         "roofline": {"kernel": "k_align_paired" if paired else "k_align_single", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                      "algorithmic_bytes_per_launch": alg_bytes, "bytes_breakdown": parts, "avg_launch_ms": avg_ms,
@@ -580,7 +656,7 @@ def run_leg(args, env, bed, workload, primary):
                                   "hits": per_launch["n_hits_consumed"] / n, "lv_locations": per_launch["n_lv_locations"] / n,
                                   "ag_locations": per_launch["n_ag_locations"] / n}},
         "aligned_fraction": float((prim["status"] != 0).mean()),
-    }
+    })
     if probe is not None:
         out["roofline"]["probe"] = probe
     if os.environ.get("SNAPGPU_PHASE_TIMERS") == "1" and not paired:      # a diagnostic run: the timed contexts themselves carry the timers
@@ -1015,9 +1091,10 @@ def main():
         log(env["genome_choice"])
 
     # ---------------------------------------------------------------- the line's own leg
-    bed = make_bed(args, env, paired_owner=args.workload == "paired")
+    # (a plain run draws its read batches while the index is built; --full keeps them apart: its index build also saves the directory)
+    bed = make_bed(args, env, paired_owner=args.workload == "paired", early_batches=not args.full)
     out = run_leg(args, env, bed, args.workload, primary=True)
-    extra = world == 1 and not env["force_dist"] and args.workload == "single" and not args.no_extra_legs
+    extra = args.full and world == 1 and not env["force_dist"] and args.workload == "single" and not args.no_extra_legs
     if extra and rank == 0:
         # ---------------------------------------------------------------- configs[2] over the same resident index (so that C3 is in the driver's line)
         try:
@@ -1069,7 +1146,8 @@ def main():
             out["genome_256mb"] = {"error": "%s: %s" % (type(e_).__name__, e_)}
     failures = []
     if rank == 0:
-        failures = parity_verdict(out)
+        if args.full:
+            failures = parity_verdict(out)
         out["bench_wall_s"] = time.time() - _T_PROCESS
         try:
             import resource

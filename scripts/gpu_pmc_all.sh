@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_SALU"; do
   i=$((i+1))
-  timeout 120 rocprofv3 --pmc $grp --output-format csv -d $O/pmc_$i -o bench -- python bench.py --steps 1 --warmup 0 --skip-cpu --skip-probe "$@" > $O/pmc_$i.json 2> $O/pmc_$i.err < /dev/null
+  timeout 120 rocprofv3 --pmc $grp --output-format csv -d $O/pmc_$i -o bench -- python bench.py --full --steps 1 --warmup 0 --skip-cpu --skip-probe "$@" > $O/pmc_$i.json 2> $O/pmc_$i.err < /dev/null
 done
 python - <<PY
 import csv, glob, json, collections

@@ -2,7 +2,7 @@
 # counters only (no trace domains).  Usage: bash scripts/gpu_pmc_traffic.sh <out-dir-under-gpurun_out>
 O=gpurun_out/${1:-pmc}; mkdir -p $O
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 100 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -o bench -- python bench.py --steps 1 --warmup 0 --skip-cpu > $O/pmc_$c.json 2> $O/pmc_$c.err < /dev/null
+  timeout 100 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -o bench -- python bench.py --full --steps 1 --warmup 0 --skip-cpu > $O/pmc_$c.json 2> $O/pmc_$c.err < /dev/null
   python - <<PY
 import csv
 tot = 0.0; n = 0

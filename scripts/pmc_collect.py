@@ -42,7 +42,7 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     from bench import kernel_source_hash
     env = dict(os.environ, TMPDIR="/tmp")
-    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", "0", "--batches", "2", "--skip-cpu", "--skip-refwalk",
+    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(a.steps), "--warmup", "0", "--batches", "2", "--skip-cpu", "--skip-refwalk",
              "--skip-breakdown", "--no-extra-legs", "--genome-mb", str(a.genome_mb), "--workload", a.workload, "--reads", str(a.reads)] + (["--feeders", str(a.feeders)] if a.feeders else []) + a.rest
     tot = collections.defaultdict(float)
     rows = collections.defaultdict(int)

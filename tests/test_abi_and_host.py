@@ -231,3 +231,38 @@ def hashlib_of_repo(root, bench):
         return bench.kernel_source_hash()
     finally:
         bench.ROOT = saved
+
+
+@pytest.mark.parametrize("dtype_name", ["RESULT_DTYPE", "PAIRED_RESULT_DTYPE"])
+def test_bench_dump_outputs_writes_every_field_as_float64_within_the_cap(tmp_path, monkeypatch, dtype_name):
+    """bench.py --dump-outputs: one float64 array per result field, all units while they fit under DUMP_MAX_BYTES, otherwise the same
+    seeded sample every time (unit_index.npy names it), the values exact."""
+    import bench
+    dt = getattr(abi, dtype_name)
+    rng = np.random.default_rng(5)
+    res = np.zeros(1000, dtype=dt)
+    for f in dt.names:                      # every integer field over its whole range (64-bit ones: genome locations, < 2^53)
+        base = dt[f].base
+        if base.kind == "f":
+            res[f] = rng.random(res[f].shape)
+        else:
+            lim = np.iinfo(base)
+            res[f] = rng.integers(max(lim.min, -2 ** 53), min(lim.max, 2 ** 53), size=res[f].shape, dtype=np.int64, endpoint=True)
+    elems = 1 + sum(int(np.prod(dt[f].shape)) for f in dt.names)
+    for cap, want in ((10 ** 9, 1000), (8 * elems * 100, 100)):
+        monkeypatch.setattr(bench, "DUMP_MAX_BYTES", cap)
+        got = []
+        for run in range(2):
+            d = tmp_path / ("%d_%d" % (cap, run))
+            assert bench.dump_outputs(str(d), res) == want
+            assert sorted(os.listdir(d)) == sorted([f + ".npy" for f in dt.names] + ["unit_index.npy"])
+            assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= cap + 4096
+            idx = np.load(d / "unit_index.npy")
+            assert idx.dtype == np.float64 and idx.shape == (want,) and (np.diff(idx) > 0).all()
+            i = idx.astype(np.int64)
+            for f in dt.names:
+                a = np.load(d / (f + ".npy"))
+                assert a.dtype == np.float64 and a.shape == (want,) + dt[f].shape, f
+                assert (a == res[f][i].astype(np.float64)).all() and (a.astype(res[f].dtype) == res[f][i]).all(), f
+            got.append(idx)
+        assert (got[0] == got[1]).all()

@@ -178,13 +178,21 @@ def test_affine_gap_restatement_vs_reference_fresh_fuzz():
 @have_ref
 def test_reference_reproduces_committed_alignread_fixtures(golden_reads, tmp_path):
     """The fixtures really are what the reference computes (guards against stale goldens)."""
-    from snap_amd import abi
-    import subprocess
-    # rebuild the index from the committed genome bytes is not possible without the FASTA; instead
-    # re-run scripts/make_golden.py's reference calls against its cached index if present
-    idx_dir = "/tmp/snap_golden/idx"
-    if not os.path.exists(os.path.join(idx_dir, "GenomeIndex")):
-        pytest.skip("golden working directory not present (run scripts/make_golden.py)")
+    from snap_amd import abi, synth
+    from snap_amd.index import GenomeIndex
+    # the genome of tests/golden/tiny_index.npz, drawn again the way scripts/make_golden.py draws it, and indexed by the reference
+    g = synth.make_genome(20260925, 100_000, n_contigs=2, repeat_frac=0.4, max_copies=60, repeat_len=(150, 1200), n_run_frac=0.004)
+    rng = np.random.default_rng(99)
+    alt = g[0][1][20_000:32_000].copy()
+    mut = rng.random(alt.size) < 0.01
+    alt[mut] = synth._ACGT[rng.integers(0, 4, size=int(mut.sum()))]
+    g.append(("chrA_alt1", alt))
+    synth.write_fasta(str(tmp_path / "ref.fa"), g)
+    idx_dir = str(tmp_path / "idx")
+    ref.build_index(str(tmp_path / "ref.fa"), idx_dir, 20, threads=4, extra=["-altContigName", "chrA_alt1"])
+    gi = GenomeIndex.load_from_directory(idx_dir)
+    golden = util.load_golden_index()
+    assert gi.n_bases == golden.n_bases and (gi.genome_padded == golden.genome_padded).all(), "the committed index is not of this genome"
     ri = ref.RefIndex(idx_dir)
     z = golden_reads
     p = abi.default_params(max_k=8, max_read_len=160)

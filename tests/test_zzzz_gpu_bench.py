@@ -34,10 +34,10 @@ def _run(cmd, env=None, timeout=600):
 
 @pytest.mark.gpu
 def test_bench_line_with_its_extra_legs_small():
-    """The default-shaped run (single-end leg + the paired-end and c5 legs over the same resident index + the FASTQ -> SAM leg through
+    """The --full run (single-end leg + the paired-end and c5 legs over the same resident index + the FASTQ -> SAM leg through
     snap_amd/snapgpu-sam, plus the opt-in stand-in leg), every sampled read and pair compared with the compiled reference inside bench.py
     itself, the e2e leg's records with the reference CLI's."""
-    o = _run([sys.executable, "bench.py"] + SMALL + ["--paired-leg-steps", "2", "--standin-leg", "--standin-mb", "12", "--cpu-seconds", "1",
+    o = _run([sys.executable, "bench.py", "--full"] + SMALL + ["--paired-leg-steps", "2", "--standin-leg", "--standin-mb", "12", "--cpu-seconds", "1",
                                                      "--c5-reads", "6000", "--c5-leg-steps", "2", "--e2e-reads", "300000", "--e2e-ref-reads", "100000"], timeout=900)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "parity_check"):
@@ -79,6 +79,33 @@ def test_bench_line_with_its_extra_legs_small():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run prints the headline fields only -- none of what --full adds -- and times exactly --steps steps; --dump-outputs writes
+    the result records of the last timed step as float64 arrays, the same bytes from run to run."""
+    import numpy as np
+    from snap_amd import abi
+    dumps = []
+    for i in range(2):
+        d = str(tmp_path / ("out%d" % i))
+        o = _run([sys.executable, "bench.py", "--gpus", "1"] + SMALL + ["--dump-outputs", d])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert k in o, k
+        for k in ("roofline", "cpu_baseline", "parity_check", "paired", "c5", "e2e", "genome_256mb", "aligned_fraction"):
+            assert k not in o, k
+        assert o["steps"] == 3 and o["unit"] == "reads/s" and o["higher_is_better"] is True
+        assert abs(o["value"] - 20000 * 3 / (o["ms_per_step"] * 3 / 1e3)) <= 1e-6 * o["value"]
+        files = sorted(os.listdir(d))
+        assert files == sorted([f + ".npy" for f in abi.RESULT_DTYPE.names] + ["unit_index.npy"])
+        arrs = {f: np.load(os.path.join(d, f)) for f in files}
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) < 64e6
+        assert all(a.dtype == np.float64 and a.shape == (20000,) for a in arrs.values())
+        assert set(np.unique(arrs["status.npy"])) <= {0.0, 1.0, 2.0} and (arrs["status.npy"] != 0).mean() > 0.5
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f], equal_nan=True), f
+
+
+@pytest.mark.gpu
 def test_bench_fails_loudly_on_a_kernel_that_answers_differently():
     """snap_amd/ab/libsnapgpu_broken.so (__graft_entry__.build_broken_variant: the product's objects with ONE translation unit rebuilt
     -DSNAPGPU_TEST_BREAK_PARITY, which flips the MAPQ's low bit of every 997th read in the single-end kernel the bench times) under
@@ -88,7 +115,7 @@ def test_bench_fails_loudly_on_a_kernel_that_answers_differently():
         pytest.skip("the broken variant was not built (python -c 'import __graft_entry__ as g; g.build_broken_variant()')")
     e = dict(os.environ)
     e["SNAP_BENCH_DIR"] = e.get("SNAP_BENCH_DIR", "/tmp/snap_bench_test")
-    r = subprocess.run([sys.executable, "scripts/ab_bench.py", "run", "broken"] + SMALL + ["--no-extra-legs", "--cpu-seconds", "1", "--skip-probe", "--skip-refwalk",
+    r = subprocess.run([sys.executable, "scripts/ab_bench.py", "run", "broken", "--full"] + SMALL + ["--no-extra-legs", "--cpu-seconds", "1", "--skip-probe", "--skip-refwalk",
                                                                                           "--skip-breakdown"], cwd=ROOT, env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 3, (r.returncode, r.stderr.decode(errors="replace")[-2000:])
     assert b"PARITY FAILURE" in r.stderr
@@ -105,7 +132,7 @@ def test_bench_multi_gpu_path_on_one_rank():
     blobs go through dist.broadcast into tensors the context then adopts by device pointer (snap_amd/dist.py), timing by barrier + max."""
     port = _free_port()
     o = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-              "bench.py", "--gpus", "1"] + SMALL + ["--skip-probe", "--skip-refwalk", "--skip-breakdown", "--cpu-seconds", "1"],
+              "bench.py", "--gpus", "1", "--full"] + SMALL + ["--skip-probe", "--skip-refwalk", "--skip-breakdown", "--cpu-seconds", "1"],
              env={"SNAP_BENCH_FORCE_DIST": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert o["n_gpus"] == 1 and o["value"] > 0
     assert "paired" not in o and "genome_256mb" not in o and "e2e" not in o and "c5" not in o                               # the extra legs belong to the plain one-GPU run
