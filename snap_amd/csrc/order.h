@@ -1,4 +1,4 @@
-// order.h -- heavy-first dequeue order for a batch (single-end reads or pairs).
+// order.h -- heavy-first dequeue order for a batch of single-end reads.
 //
 // A launch is persistent waves pulling units from a counter, so it lasts until its slowest unit is done; the cost of a unit is heavy-tailed
 // (a read out of a diverged repeat family is scored against every copy: hundreds of affine-gap problems, tens of milliseconds on one wave,
@@ -12,9 +12,9 @@
 #include "dev_common.h"
 #include "probe.h"
 
-// unit i = reads i * rpu .. i * rpu + rpu - 1 (rpu = 1: single end, 2: pairs)
+// unit i = read i
 template <int UNUSED>
-__global__ __launch_bounds__(256) void k_unit_weights(DevIndex ix, const uint8_t *bases, const uint64_t *offsets, uint32_t n_units, uint32_t rpu,
+__global__ __launch_bounds__(256) void k_unit_weights(DevIndex ix, const uint8_t *bases, const uint64_t *offsets, uint32_t n_units,
                                                       uint32_t max_hits, uint32_t *bucket, uint32_t *hist /* [34] */)
 {
     const int lane = lane_id();
@@ -23,18 +23,16 @@ __global__ __launch_bounds__(256) void k_unit_weights(DevIndex ix, const uint8_t
     const int seed_len = (int)ix.seed_len;
     for (uint32_t i = wave; i < n_units; i += n_waves) {
         uint64_t w = 0;
-        for (uint32_t r = 0; r < rpu; r++) {
-            const uint64_t b = first_u64(offsets[(size_t)i * rpu + r]), e = first_u64(offsets[(size_t)i * rpu + r + 1]);
-            const int len = (int)(e - b);
-            for (int off = 0; off + seed_len <= len; off += seed_len) {
-                SeedBits seed = pack_seed(bases + b + off, ix.seed_len);
-                if (!seed.valid) continue;
-                HitList hl[2];
-                lookup_seed(ix, seed, hl);
-                for (int d = 0; d < 2; d++) {
-                    const int64_t nh = (int64_t)first_u64((uint64_t)hl[d].n_hits);
-                    if (nh > 0 && nh <= (int64_t)max_hits) w += (uint64_t)nh;
-                }
+        const uint64_t b = first_u64(offsets[i]), e = first_u64(offsets[(size_t)i + 1]);
+        const int len = (int)(e - b);
+        for (int off = 0; off + seed_len <= len; off += seed_len) {
+            SeedBits seed = pack_seed(bases + b + off, ix.seed_len);
+            if (!seed.valid) continue;
+            HitList hl[2];
+            lookup_seed(ix, seed, hl);
+            for (int d = 0; d < 2; d++) {
+                const int64_t nh = (int64_t)first_u64((uint64_t)hl[d].n_hits);
+                if (nh > 0 && nh <= (int64_t)max_hits) w += (uint64_t)nh;
             }
         }
         const uint32_t ww = w > 0xffffffffull ? 0xffffffffu : (uint32_t)w;

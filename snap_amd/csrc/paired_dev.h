@@ -675,47 +675,12 @@ __global__ __launch_bounds__(256, SNAPGPU_PAIRED_WAVES_PER_SIMD(AGC)) void k_ali
         }
         WAVE_SYNC();
     };
-    using XP = DevPL<AGC, SEC, EXACT>;
     while (true) {
         uint32_t i = 0;
-        if (EXACT && a.rq_mode == 2u) {
-            // pairs arrive while the main pass runs (PairedArgs::rq): take the next entry of the list, or wait for one, until the main pass
-            // has finished all of its pairs and every entry has been taken
-            const uint64_t t_wait0 = wave_clock();
-            uint32_t got = 0xFFFFFFFFu;
-            for (uint32_t round = 0;; round++) {
-                const uint32_t h = XP::aload(a.rq + 1), t = XP::aload(a.rq);
-                if (h < t) {
-                    uint32_t was = 0;
-                    if (lane == 0) was = atomicCAS(a.rq + 1, h, h + 1u);
-                    if (first_u32(was) != h) continue;                    // somebody else took entry h
-                    for (uint32_t w = 0;; w++) {                           // (the index lands right after the count: a very short wait)
-                        got = XP::aload(a.rq_list + h);
-                        if (got != 0xFFFFFFFFu || w > 4000000u) break;
-                        XP::nap();
-                    }
-                    if (got == 0xFFFFFFFFu) { if (lane == 0) atomicAdd(a.rq + 3, 1u); continue; }      // (never seen; the pair stays flagged for the pass after)
-                    break;
-                }
-                if (XP::aload(a.rq + 2) >= a.n_pairs) {                    // the main pass is through: is the list?  (appended before counted)
-                    if (XP::aload(a.rq + 1) >= XP::aload(a.rq)) break;
-                    continue;
-                }
-                if ((round & 63u) == 63u && wave_clock() - t_wait0 > 240000000000ull) {       // ~100 s: give up, leave a trace
-                    if (lane == 0) atomicAdd(a.rq + 3, 0x10000u);
-                    break;
-                }
-                XP::nap(); XP::nap(); XP::nap(); XP::nap();
-            }
-            if (got == 0xFFFFFFFFu) break;
-            XP::fence_acquire();
-            i = got;
-        } else {
-            if (lane == 0) i = atomicAdd(a.work_counter, 1u);
-            i = first_u32(i);
-            if (i >= n_total) break;
-            if (a.remap) i = first_u32(a.remap[i]);
-        }
+        if (lane == 0) i = atomicAdd(a.work_counter, 1u);
+        i = first_u32(i);
+        if (i >= n_total) break;
+        if (a.remap) i = first_u32(a.remap[i]);
         if constexpr (EXACT) {          // newly constructed reference aligners: all four traceback arrays read as zero -- cleared once per
             if (++pl.ag_epoch == 16u) { // fifteen pairs; in between, cells that do not carry this pair's tag read as zero (dev_common.h: bt_cell)
                 if (pl.ag_hw0) wave_zero16(pl.ag_persist0, ((size_t)pl.ag_hw0 + 15) & ~(size_t)15);
@@ -744,8 +709,7 @@ __global__ __launch_bounds__(256, SNAPGPU_PAIRED_WAVES_PER_SIMD(AGC)) void k_ali
         }
         core.align_pair(a.max_k_paired, a.max_k_single);
         core.S()->res.flags = (core.overflow ? SNAPGPU_PAIR_POOL_OVERFLOW : 0) | (core.ref_dep ? SNAPGPU_PAIR_REF_BUFFER_DEPENDENT : 0) |
-                             ((EXACT || core.stale_later || (a.dbg_flag_every != 0u && i % a.dbg_flag_every == 0u)) ? SNAPGPU_PAIR_EXACT_REPLAY : 0) |
-                             ((EXACT && a.rq_mode == 2u) ? SNAPGPU_PAIR_REPLAYED_BESIDE : 0);
+                             ((EXACT || core.stale_later || (a.dbg_flag_every != 0u && i % a.dbg_flag_every == 0u)) ? SNAPGPU_PAIR_EXACT_REPLAY : 0);
         WAVE_SYNC();
         if constexpr (SEC) {        // paired secondary results: sec[sec_ord[k]] -> secondary[i * stride + k]
             const uint32_t n_sec = core.overflow ? 0u : core.n_sec;
@@ -772,22 +736,6 @@ __global__ __launch_bounds__(256, SNAPGPU_PAIRED_WAVES_PER_SIMD(AGC)) void k_ali
         }
         WAVE_SYNC();
         n_done++;
-        if (!EXACT && a.rq_mode == 1u) {
-            // a flagged pair goes to the exact kernel that runs beside this one: the pair's results first (the exact kernel writes the
-            // same records), then the index, then the count of finished pairs (the exact kernel leaves when that count is complete
-            // and the list is empty, so the index must be there before the pair is counted)
-            const uint32_t fl = first_u32(core.S()->res.flags);
-            if ((fl & SNAPGPU_PAIR_EXACT_REPLAY) != 0u && (fl & SNAPGPU_PAIR_POOL_OVERFLOW) == 0u) {
-                XP::stores_done();
-                XP::fence_release();
-                if (lane == 0) {
-                    const uint32_t slot = atomicAdd(a.rq, 1u);
-                    const uint32_t old = atomicExch(a.rq_list + slot, i);
-                    if (old != 0xFFFFFFFFu) atomicAdd(a.rq + 3, 0x1000000u);          // (uses the return value: the exchange has completed)
-                }
-            }
-            if (lane == 0) atomicAdd(a.rq + 2, 1u);
-        }
         if (!EXACT && a.help_done != nullptr && lane == 0) atomicAdd(a.help_done, 1u);
     }
     if constexpr (!EXACT) {
@@ -869,6 +817,5 @@ __global__ void k_collect_flagged(snapgpu_paired_result *primary, uint32_t n, ui
     if (i >= n) return;
     const uint32_t fl = primary[i].flags;
     const bool ov = (fl & SNAPGPU_PAIR_POOL_OVERFLOW) != 0;
-    if (stale && (fl & SNAPGPU_PAIR_REPLAYED_BESIDE)) { primary[i].flags = fl & ~SNAPGPU_PAIR_REPLAYED_BESIDE; return; }   // already redone beside the main pass
     if (stale ? (!ov && (fl & SNAPGPU_PAIR_EXACT_REPLAY) != 0) : ov) list[atomicAdd(count, 1u)] = i;
 }

@@ -177,12 +177,11 @@ def test_emu_paired_end(emu):
     assert (alt["status"] == z[key + "_alt"]["status"][:n]).all()
 
 
-def test_emu_exact_replay_beside_the_main_pass(emu, monkeypatch):
-    """tests/test_gpu_paired.py::test_exact_replay_beside_the_main_pass on the emulated device (the exact kernel there starts when the main
-    kernel has ended: the list protocol, the markers and the pass after it, not the concurrency), first 150 golden pairs."""
+def test_emu_exact_replay_of_flagged_pairs(emu, monkeypatch):
+    """tests/test_gpu_paired.py::test_exact_replay_of_flagged_pairs on the emulated device, first 150 golden pairs."""
     import tests.test_gpu_paired as gp
-    gp.test_exact_replay_beside_the_main_pass(util.load_golden_index("paired_index.npz"), np.load(os.path.join(util.GOLDEN, "paired_reads.npz")),
-                                              monkeypatch, n=150)
+    gp.test_exact_replay_of_flagged_pairs(util.load_golden_index("paired_index.npz"), np.load(os.path.join(util.GOLDEN, "paired_reads.npz")),
+                                          monkeypatch, n=150)
 
 
 def test_emu_paired_end_lv_only_hamming_retry_uses_affine_gap(emu):

@@ -74,7 +74,8 @@ def test_index_shapes_vs_live_reference(tmp_path, seed_len, large):
 @pytest.mark.skipif(not ref.available() or not os.path.exists(ref.CLI_PATH), reason="oracle/_ref not on this box")
 @pytest.mark.parametrize("seed_len,large,extra", WIDE_SHAPES)
 def test_wide_location_indexes_vs_live_reference(tmp_path, seed_len, large, extra):
-    align_and_compare(str(tmp_path), seed_len, large, 6000, genome_bases=1_000_000, extra=extra, from_directory=seed_len == 18)   # (18: through snapgpu_create_from_directory's narrowing)
+    # (seed 18 and -locationSize 7: through snapgpu_create_from_directory's narrowing)
+    align_and_compare(str(tmp_path), seed_len, large, 6000, genome_bases=1_000_000, extra=extra, from_directory=seed_len == 18 or "7" in extra)
 
 
 def paired_over_wide_index(tmp, seed_len, large, extra, n_pairs):
