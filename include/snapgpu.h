@@ -628,8 +628,8 @@ int  snapgpu_get_counters(snapgpu_ctx *ctx, snapgpu_counters *out, int reset);
 int  snapgpu_kernel_time(snapgpu_ctx *ctx, double *total_ms, uint64_t *n_launches, int reset);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
- * The index builder on the GPU.  Replaces, for 4-byte locations and small tables -- the index shape the north star
- * uses: `snap-aligner index <fasta> <dir> -s 8..31 [-keysize 2..8]`, in particular the default -s 20 and the reference's own default -s 24,
+ * The index builder on the GPU.  Replaces `snap-aligner index <fasta> <dir> -s 8..31 [-keysize 2..8] [-large]
+ * [-locationSize 4..8]` -- in particular the north star's -s 20 and the reference's own default -s 24 --
  *   GenomeIndex::runIndexer            SNAPLib/GenomeIndex.cpp:126-506   options, FASTA -> Genome
  *   ReadFASTAGenome                    SNAPLib/FASTA.cpp:188-409         contigs, 'n' padding, ALT contigs last, upper-casing
  *   GenomeIndex::BuildIndexToDirectory SNAPLib/GenomeIndex.cpp:527-1022  hash tables + overflow table, the four files
@@ -639,7 +639,8 @@ int  snapgpu_kernel_time(snapgpu_ctx *ctx, double *total_ms, uint64_t *n_launche
  * table depends on insertion order in both builders).  Hash-table sizes follow the reference's formula with exact distinct-seed counts
  * (its -exact mode; its default estimates them with approximate counters).
  * The build itself (seeds of all locations, radix sort, overflow lists, closed-hash insertion) runs on the device: index_build.h.
- * Anything outside that shape (-large, -locationSize > 4, key sizes other than 4) returns SNAPGPU_E_UNSUPPORTED: use the reference's indexer.
+ * Still refused with SNAPGPU_E_UNSUPPORTED (use the reference's indexer): -s 32, -sm, -H, and genomes whose genome + overflow table do not fit
+ * 32-bit values (the same limit snapgpu_create_from_directory has).
  */
 typedef struct snapgpu_built_index snapgpu_built_index;
 
@@ -658,7 +659,14 @@ typedef struct snapgpu_index_build_params {
     const char *alt_liftover_file;  /* -altLiftoverFile, NULL = none                                                   */
 } snapgpu_index_build_params;
 
-/* what one build did, for logs and the bench line */
+/* The index shape (snapgpu_index_build_shaped): {0, 4} is what snapgpu_index_build builds, whatever the seed length.
+ *   large          -large: a seed and its reverse complement share one slot of two values (GenomeIndex.cpp:1513-1640)
+ *   location_size  -locationSize 4..8: bytes per value and 8-byte overflow entries (> 4) in the saved files.  The built index keeps 4-byte
+ *                  values in HBM (its view has location_size 4, like a directory narrowed on load); snapgpu_built_index_save widens them. */
+typedef struct snapgpu_index_build_shape { uint32_t large; uint32_t location_size; } snapgpu_index_build_shape;
+
+/* what one build did, for logs and the bench line.  Under -large n_distinct_seeds counts occupied slots, i.e. canonical seeds (a seed and its
+ * reverse complement are one), and n_repeated_seeds counts overflow lists (one per strand of a seed that occurs more than once on it). */
 typedef struct snapgpu_index_build_stats {
     uint64_t n_bases, n_seed_locations, n_distinct_seeds, n_repeated_seeds, overflow_table_size, hash_table_slots, hash_blob_bytes;
     double   ms_keys, ms_sort, ms_runs, ms_tables, ms_total_device;
@@ -678,6 +686,11 @@ typedef struct snapgpu_genome_view {
 
 int  snapgpu_index_build(const snapgpu_genome_view *genome, const snapgpu_index_build_params *bp, int device, snapgpu_built_index **out);
 int  snapgpu_index_build_from_fasta(const char *fasta_path, const snapgpu_index_build_params *bp, int device, snapgpu_built_index **out);
+/* The same with an explicit shape (NULL = {0, 4}); the two above are these with {0, 4}. */
+int  snapgpu_index_build_shaped(const snapgpu_genome_view *genome, const snapgpu_index_build_params *bp, const snapgpu_index_build_shape *shape,
+                                int device, snapgpu_built_index **out);
+int  snapgpu_index_build_from_fasta_shaped(const char *fasta_path, const snapgpu_index_build_params *bp, const snapgpu_index_build_shape *shape,
+                                           int device, snapgpu_built_index **out);
 /* The built index as a view with on_device = 1 (feed it to snapgpu_create: no copy, no files); valid until snapgpu_built_index_destroy. */
 int  snapgpu_built_index_view(const snapgpu_built_index *bi, snapgpu_index_view *view);
 /* The four files of a SNAP index directory (GenomeIndex, Genome, OverflowTable, GenomeIndexHash). */

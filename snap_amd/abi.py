@@ -108,6 +108,10 @@ class IndexBuildParams(C.Structure):          # snapgpu_index_build_params
     ]
 
 
+class IndexBuildShape(C.Structure):           # snapgpu_index_build_shape
+    _fields_ = [("large", C.c_uint32), ("location_size", C.c_uint32)]
+
+
 class IndexBuildStats(C.Structure):           # snapgpu_index_build_stats
     _fields_ = [(n, C.c_uint64) for n in ("n_bases", "n_seed_locations", "n_distinct_seeds", "n_repeated_seeds", "overflow_table_size",
                                           "hash_table_slots", "hash_blob_bytes")] + \

@@ -3,7 +3,7 @@
 // Mirrors GenomeIndex::runIndexer (SNAPLib/GenomeIndex.cpp:126-506): same positional arguments, same option spellings for the options that
 // make sense here, same four output files -- a directory this writes is what `snap-aligner single <dir> ...`,
 // `snap-aligner-gpu` and `snapgpu-sam` load.  All work is behind the C ABI (include/snapgpu.h: snapgpu_index_build_from_fasta,
-// snapgpu_built_index_save); this file is option parsing.  Host-only C++; build: g++ -O2 -std=c++17 snapgpu_index.cpp -lsnapgpu
+// snapgpu_index_build_from_fasta_shaped, snapgpu_built_index_save); this file is option parsing.  Host-only C++; build: g++ -O2 -std=c++17 snapgpu_index.cpp -lsnapgpu
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,8 +28,10 @@ static void usage()
             "  -maxAltContigSize <n>, -altContigName <name>, -nonAltContigName <name>, -altContigFile <file>, -nonAltContigFile <file>\n"
             "  -altLiftoverFile <file>\n"
             "  -gpu <n>            HIP device (default 0)\n"
+            "  -large              seeds and their reverse complements share hash-table entries\n"
+            "  -locationSize <n>   bytes per genome location in the index files, 4..8 (default 4)\n"
             "  -exact, -t<n>, -q   accepted and ignored (table sizes are always exact; the build is one GPU)\n"
-            "  not supported: -large, -locationSize other than 4, -sm, -H<file>  (use the reference's indexer)\n");
+            "  not supported: -sm, -H<file>  (use the reference's indexer)\n");
     exit(1);
 }
 
@@ -51,6 +53,7 @@ int main(int argc, char **argv)
     const char *fasta = argv[1], *out_dir = argv[2];
     snapgpu_index_build_params bp;
     snapgpu_default_index_build_params(&bp);
+    snapgpu_index_build_shape shape = {0, 4};
     std::vector<std::string> alt_names, non_alt_names;
     int device = 0; bool quiet = false;
     for (int n = 3; n < argc; n++) {
@@ -59,10 +62,15 @@ int main(int argc, char **argv)
         if (!strcmp(a, "-s")) bp.seed_len = (uint32_t)atoi(need());
         else if (!strcmp(a, "-h")) bp.slack = atof(need());
         else if (!strcasecmp(a, "-keysize")) bp.key_bytes = (uint32_t)atoi(need());
-        else if (!strcasecmp(a, "-locationSize")) { if (atoi(need()) != 4) { fprintf(stderr, "snapgpu-index writes 4-byte genome locations only\n"); return 1; } }
+        else if (!strcasecmp(a, "-locationSize")) {
+            const int ls = atoi(need());
+            if (ls < 4 || ls > 8) { fprintf(stderr, "Location size must be between 4 and 8 inclusive\n"); return 1; }
+            shape.location_size = (uint32_t)ls;
+        }
+        else if (!strcmp(a, "-large")) shape.large = 1;
         else if (!strcmp(a, "-exact") || !strcmp(a, "-hg19")) {}
         else if (!strcmp(a, "-q") || !strcmp(a, "-qq")) quiet = true;
-        else if (!strcmp(a, "-large") || !strncmp(a, "-sm", 3) || !strncmp(a, "-H", 2)) { fprintf(stderr, "%s is not supported by snapgpu-index (use the reference's indexer)\n", a); return 1; }
+        else if (!strncmp(a, "-sm", 3) || !strncmp(a, "-H", 2)) { fprintf(stderr, "%s is not supported by snapgpu-index (use the reference's indexer)\n", a); return 1; }
         else if (!strcmp(a, "-gpu")) device = atoi(need());
         else if (!strcmp(a, "-bSpace")) bp.space_terminates_name = 1;
         else if (!strcmp(a, "-bSpace-")) bp.space_terminates_name = 0;
@@ -87,7 +95,7 @@ int main(int argc, char **argv)
 
     const auto t0 = std::chrono::steady_clock::now();
     snapgpu_built_index *bi = nullptr;
-    int rc = snapgpu_index_build_from_fasta(fasta, &bp, device, &bi);
+    int rc = snapgpu_index_build_from_fasta_shaped(fasta, &bp, &shape, device, &bi);
     if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-index: build failed (%d): %s\n", rc, snapgpu_last_error(nullptr)); return 1; }
     const auto t1 = std::chrono::steady_clock::now();
     rc = snapgpu_built_index_save(bi, out_dir);

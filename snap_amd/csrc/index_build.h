@@ -14,8 +14,12 @@
 //                        tables ARE the reference's format: its loader reads them, and the device-native buckets are built from them
 //                        like from any other index.
 // Slot placement differs from a reference build (it depends on insertion order there too); lookup results do not.
-// Shape built here: 4-byte locations, small tables, any key size the reference accepts for the seed (GenomeIndex.cpp:437-460; -s 20 with its
-// 4-byte keys is the north star's index and keeps the one-compare-and-swap insert; other key sizes claim slots in a bit array, below).
+// Shapes built here: small tables with any key size the reference accepts for the seed (GenomeIndex.cpp:437-460; -s 20 with its 4-byte keys
+// is the north star's index and keeps the one-compare-and-swap insert; other key sizes claim slots in a bit array, below), and -large tables
+// (GenomeIndex.cpp:1513-1640: a seed and its reverse complement share one slot of two values).  Values are 4 bytes on the device; wider
+// locations (-locationSize 5..8) are a file format, widened when the index is saved (index_build.hip).
+// Under -large the sort key is (canonical seed << 1) | strand, so the sorted array has runs at two levels: a (seed, strand) run is one
+// overflow list, a canonical-seed run (one or two strand runs) is one slot.
 // Everything is wave-level: no block barriers, LDS only per wave.
 #pragma once
 #include "dev_common.h"
@@ -41,7 +45,9 @@ static __device__ __forceinline__ uint32_t ib_wave_incl_scan(uint32_t v) {
 // keys[loc] = the seed at loc (first base most significant, A0 G1 C2 T3: Seed.h:48, Tables.cpp:52-58) or IB_INVALID_KEY when one of its
 // bases is not ACGT (GenomeIndex.cpp:1464-1470: such locations are not indexed; that includes every seed that reaches into the 'n'
 // padding between contigs).  genome must be readable up to loc + 127 + seed_len (the context's genome_pad covers it).
-__global__ __launch_bounds__(256) void k_ib_keys(const uint8_t *genome, uint64_t n_locs, uint32_t L, uint64_t *keys)
+// large: keys[loc] = (min(seed, rc) << 1) | (seed > rc) instead (GenomeIndex.cpp:1515, Seed.h:99; a seed that is its own reverse
+// complement gets strand 0).  At most 31 bases, so the key has at most 63 bits and never equals IB_INVALID_KEY.
+__global__ __launch_bounds__(256) void k_ib_keys(const uint8_t *genome, uint64_t n_locs, uint32_t L, uint32_t large, uint64_t *keys)
 {
     const int lane = lane_id();
     const uint64_t mask_l = L >= 64 ? ~0ull : ((1ull << L) - 1ull);
@@ -55,7 +61,13 @@ __global__ __launch_bounds__(256) void k_ib_keys(const uint8_t *genome, uint64_t
         const uint64_t wb = ((lob >> lane) | (lane ? (hib << (64 - lane)) : 0ull)) & mask_l;
         // base i of the window lands at bits 2(L-1-i)+1 .. 2(L-1-i): reverse the planes within L bits, then interleave
         const uint64_t r0 = __brevll(w0) >> (64 - L), r1 = __brevll(w1) >> (64 - L);
-        const uint64_t key = spread_bits(r0) | (spread_bits(r1) << 1);
+        uint64_t key = spread_bits(r0) | (spread_bits(r1) << 1);
+        if (large) {
+            // Seed.h:47: the reverse complement has base i of the window, complemented (code ^ 3), at bits 2i + 1 .. 2i -- the planes
+            // unreversed and inverted
+            const uint64_t rc = spread_bits(~w0 & mask_l) | (spread_bits(~w1 & mask_l) << 1);
+            key = key > rc ? ((rc << 1) | 1ull) : (key << 1);
+        }
         const uint64_t loc = base + (uint64_t)lane;
         if (loc < n_locs) keys[loc] = wb ? IB_INVALID_KEY : key;
     }
@@ -218,20 +230,28 @@ __global__ __launch_bounds__(256) void k_ib_fill_overflow(const uint32_t *vals, 
         }
     }
 }
-// first run whose seed is >= bound[t] (bound[t] = t << key_bits; bound[n_tables] = everything): run-index boundaries of the hash tables
-__global__ __launch_bounds__(256) void k_ib_table_bounds(const uint64_t *keys, const uint32_t *run_start, uint32_t n_runs, uint32_t key_bits,
-                                                         uint32_t n_tables, uint32_t *first_run)
+// -large: seed_head[r] = 1 where strand run r starts a new canonical seed (its key without the strand bit differs from the previous run's)
+__global__ __launch_bounds__(256) void k_ib_seed_heads(const uint64_t *keys, const uint32_t *run_start, uint32_t n_runs, uint32_t *seed_head)
+{
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_runs; r += (uint64_t)gridDim.x * blockDim.x)
+        seed_head[r] = (r == 0 || (keys[run_start[r]] >> 1) != (keys[run_start[r - 1]] >> 1)) ? 1u : 0u;
+}
+// first run whose seed is >= bound[t] (bound[t] = t << table_shift; bound[n_tables] = everything): run-index boundaries of the hash tables.
+// table_shift = key bits, plus the strand bit under -large; there seeds_before (the exclusive scan of k_ib_seed_heads, n_seeds its total)
+// turns the strand-run boundary into a canonical-seed boundary, which is what sizes the tables (GenomeIndex.cpp:1225-1238).
+__global__ __launch_bounds__(256) void k_ib_table_bounds(const uint64_t *keys, const uint32_t *run_start, uint32_t n_runs, uint32_t table_shift,
+                                                         uint32_t n_tables, const uint32_t *seeds_before, uint32_t n_seeds, uint32_t *first_run)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t > n_tables) return;
-    if (t == n_tables) { first_run[t] = n_runs; return; }
-    const uint64_t bound = key_bits >= 64 ? 0ull : (uint64_t)t << key_bits;       // (64 key bits: one table, t = 0)
+    if (t == n_tables) { first_run[t] = seeds_before ? n_seeds : n_runs; return; }
+    const uint64_t bound = table_shift >= 64 ? 0ull : (uint64_t)t << table_shift;    // (64 key bits: one table, t = 0)
     uint32_t lo = 0, hi = n_runs;                      // first run with key >= bound
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
         if (keys[run_start[mid]] < bound) lo = mid + 1; else hi = mid;
     }
-    first_run[t] = lo;
+    first_run[t] = !seeds_before ? lo : lo < n_runs ? seeds_before[lo] : n_seeds;
 }
 __global__ __launch_bounds__(256) void k_ib_fill_empty(unsigned long long *slots, uint64_t n_slots)
 {
@@ -268,28 +288,41 @@ __global__ __launch_bounds__(256) void k_ib_insert(const uint64_t *keys, const u
 }
 
 // The same for entries that are not 8 bytes wide (key sizes other than 4: the reference's default for seeds above 21 is 5 or more,
-// GenomeIndex.cpp:437): entries then straddle words, so a slot is claimed in a bit array (one bit per slot of the whole blob) and its bytes --
-// value, then key_bytes of key, little endian (HashTable.h:148-156) -- are written by the one thread that claimed it.  The invariant is the
-// same: a claimed slot stays claimed, so no key has an empty slot before it on its probe sequence.
-__global__ __launch_bounds__(256) void k_ib_fill_empty_wide(uint32_t *words, uint64_t n_words, uint32_t entry_bytes)
+// GenomeIndex.cpp:437; and every -large table): entries then straddle words, so a slot is claimed in a bit array (one bit per slot of the
+// whole blob) and its bytes -- value_count 4-byte values, then key_bytes of key, little endian (HashTable.h:148-156) -- are written by the
+// one thread that claimed it.  The invariant is the same: a claimed slot stays claimed, so no key has an empty slot before it on its probe
+// sequence.
+__global__ __launch_bounds__(256) void k_ib_fill_empty_wide(uint32_t *words, uint64_t n_words, uint32_t entry_bytes, uint32_t value_bytes)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * blockDim.x) {
         uint32_t w = 0;
-        for (uint32_t b = 0; b < 4; b++) if ((4 * i + b) % entry_bytes < 4) w |= 0xffu << (8 * b);      // value bytes 0xff, key bytes 0 (HashTable.cpp:63-70)
+        for (uint32_t b = 0; b < 4; b++) if ((4 * i + b) % entry_bytes < value_bytes) w |= 0xffu << (8 * b);     // values 0xff.., key bytes 0 (HashTable.cpp:63-70)
         words[i] = w;
     }
 }
+// value_count 1: one thread per run.  value_count 2 (-large, GenomeIndex.cpp:1548-1570): runs are (canonical seed, strand) runs; the thread
+// of the first run of a canonical seed owns the slot and writes value 0 from the forward run, value 1 from the reverse-complement run, and
+// 0xfffffffe where a strand does not occur.
 __global__ __launch_bounds__(256) void k_ib_insert_wide(const uint64_t *keys, const uint32_t *vals, const uint32_t *run_start, const uint32_t *ovf_off,
                                                         uint32_t n_runs, uint32_t key_bits, uint32_t n_bases32, uint8_t *blob, uint32_t entry_bytes,
-                                                        uint32_t *claim, const uint64_t *table_slot0, const uint64_t *table_size, uint32_t *fail)
+                                                        uint32_t value_count, uint32_t *claim, const uint64_t *table_slot0, const uint64_t *table_size,
+                                                        uint32_t *fail)
 {
     const uint64_t key_mask = key_bits >= 64 ? ~0ull : ((1ull << key_bits) - 1ull);
+    const uint32_t strand_bits = value_count == 2 ? 1u : 0u;
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_runs; r += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t s = run_start[r], len = run_start[r + 1] - s;
-        const uint64_t seed = keys[s];
+        const uint64_t seed = keys[s] >> strand_bits;
+        if (strand_bits && r > 0 && (keys[run_start[r - 1]] >> 1) == seed) continue;       // the previous run owns this canonical seed
+        const uint32_t v = len == 1 ? vals[s] : n_bases32 + ovf_off[r];
+        uint32_t v0 = v, v1 = 0xfffffffeu;                                                 // (0xfffffffe: this strand does not occur)
+        if (strand_bits && (keys[s] & 1ull)) { v0 = 0xfffffffeu; v1 = v; }
+        if (strand_bits && r + 1 < n_runs) {
+            const uint32_t s1 = run_start[r + 1], len1 = run_start[r + 2] - s1;
+            if ((keys[s1] >> 1) == seed) v1 = len1 == 1 ? vals[s1] : n_bases32 + ovf_off[r + 1];       // (sorted: strand 1 comes second)
+        }
         const uint64_t key = seed & key_mask;
         const uint32_t t = key_bits >= 64 ? 0u : (uint32_t)(seed >> key_bits);
-        const uint32_t value = len == 1 ? vals[s] : n_bases32 + ovf_off[r];
         const uint64_t size = table_size[t], slot0 = table_slot0[t];
         uint64_t idx = murmur_finalizer(key) % size;
         uint64_t probes = 0;
@@ -298,8 +331,9 @@ __global__ __launch_bounds__(256) void k_ib_insert_wide(const uint64_t *keys, co
             const uint32_t bit = 1u << (g & 31);
             if (!(atomicOr(&claim[g >> 5], bit) & bit)) {
                 uint8_t *e = blob + g * entry_bytes;
-                for (uint32_t b = 0; b < 4; b++) e[b] = (uint8_t)(value >> (8 * b));
-                for (uint32_t b = 4; b < entry_bytes; b++) e[b] = (uint8_t)(key >> (8 * (b - 4)));
+                for (uint32_t b = 0; b < 4; b++) e[b] = (uint8_t)(v0 >> (8 * b));
+                if (strand_bits) for (uint32_t b = 0; b < 4; b++) e[4 + b] = (uint8_t)(v1 >> (8 * b));
+                for (uint32_t b = 4 * value_count; b < entry_bytes; b++) e[b] = (uint8_t)(key >> (8 * (b - 4 * value_count)));
                 break;
             }
             probes++;

@@ -39,6 +39,7 @@ struct IBContig {
 struct snapgpu_built_index {
     int device = 0;
     uint32_t seed_len = 0, key_bytes = 0, chromosome_padding = 0, n_tables = 0;
+    uint32_t large = 0, location_size = 4;       // the shape (snapgpu_index_build_shape); values are 4 bytes on the device whatever location_size
     uint64_t n_bases = 0;
     uint32_t genome_pad = 1024;
     uint8_t *d_genome_padded = nullptr;          // genome_pad + n_bases + genome_pad bytes
@@ -115,8 +116,9 @@ int ib_exclusive_scan(const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *p
 // The device part: genome image (already on the device inside bi) -> hash blob + overflow table.
 static int ib_build_on_device(snapgpu_built_index *bi, double slack)
 {
-    const uint32_t L = bi->seed_len, key_bits = bi->key_bytes * 8;
-    const uint32_t entry_bytes = 4 + bi->key_bytes;             // one 4-byte value, then the key (HashTable.h:148-156)
+    const uint32_t L = bi->seed_len, key_bits = bi->key_bytes * 8, large = bi->large;
+    const uint32_t value_count = large ? 2 : 1;
+    const uint32_t entry_bytes = 4 * value_count + bi->key_bytes;       // 4-byte values (forward, then reverse complement), then the key (HashTable.h:148-156)
     const uint64_t n_bases = bi->n_bases;
     // locations [0, nBases - seedLen - 1): the last chunk of the reference's scan ends there (GenomeIndex.cpp:667-670, 1455)
     const uint64_t n_locs = n_bases > (uint64_t)L + 1 ? n_bases - L - 1 : 0;
@@ -137,7 +139,7 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
     uint64_t *d_keys_a = nullptr, *d_keys_b = nullptr; uint32_t *d_vals_a = nullptr, *d_vals_b = nullptr;
     IBCHK(mem.alloc(&d_keys_a, n_locs * 8), SNAPGPU_E_NOMEM);
     IBCHK(hipEventRecord(ev[0], s), SNAPGPU_E_LAUNCH);
-    if (n_locs) hipLaunchKernelGGL(k_ib_keys, dim3(grid), dim3(256), 0, s, d_genome, n_locs, L, d_keys_a);
+    if (n_locs) hipLaunchKernelGGL(k_ib_keys, dim3(grid), dim3(256), 0, s, d_genome, n_locs, L, large, d_keys_a);
     IBCHK(hipGetLastError(), SNAPGPU_E_LAUNCH);
     IBCHK(hipEventRecord(ev[1], s), SNAPGPU_E_LAUNCH);
 
@@ -149,7 +151,7 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
     IBCHK(mem.alloc(&d_partial, ((size_t)64 * (n_tiles0 ? n_tiles0 : 1) / IB_TILE + n_locs / IB_TILE + 16) * 4), SNAPGPU_E_NOMEM);
     IBCHK(mem.alloc(&d_total, 64), SNAPGPU_E_NOMEM);
     uint64_t m = n_locs;                                   // elements alive (all of them, the non-seeds included, until the first scatter)
-    const uint32_t key_total_bits = 2 * L;
+    const uint32_t key_total_bits = 2 * L + large;          // (-large: the strand bit below the canonical seed)
     bool first = true;
     uint64_t *kin = d_keys_a, *kout = nullptr; uint32_t *vin = nullptr, *vout = nullptr;
     for (uint32_t shift = 0; shift < key_total_bits && n_locs; shift += IB_BITS) {
@@ -186,9 +188,9 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
     mem.release(d_hist); d_hist = nullptr;
     mem.release((void *)kout); mem.release((void *)vout);                 // the other halves of the double buffers
 
-    // ---- 3. runs of equal seeds
+    // ---- 3. runs of equal seeds (under -large: of equal (canonical seed, strand); n_seeds counts the canonical seeds)
     uint32_t *d_head = nullptr, *d_before = nullptr, *d_run_start = nullptr, *d_need = nullptr, *d_ovf_off = nullptr;
-    uint32_t n_runs = 0, ovf_words = 0;
+    uint32_t n_runs = 0, ovf_words = 0, n_seeds = 0;
     unsigned long long ovf_words64 = 0;
     if (m) {
         IBCHK(mem.alloc(&d_head, (size_t)m * 4), SNAPGPU_E_NOMEM);
@@ -212,19 +214,28 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
         IBCHK(hipMemsetAsync(d_sum64, 0, 8, s), SNAPGPU_E_LAUNCH);
         hipLaunchKernelGGL(k_ib_sum64, dim3(grid), dim3(256), 0, s, (const uint32_t *)d_need, n_runs, d_sum64);
         IBCHK(hipMemcpyAsync(&ovf_words64, d_sum64, 8, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
+        n_seeds = n_runs;
+        if (large) {        // d_need has served its two reductions: it becomes seeds_before (canonical seeds before each strand run)
+            hipLaunchKernelGGL(k_ib_seed_heads, dim3(grid), dim3(256), 0, s, d_keys, (const uint32_t *)d_run_start, n_runs, d_need);
+            rc = ib_exclusive_scan(d_need, n_runs, d_need, d_partial, d_total, grid, s);
+            if (rc) return rc;
+            IBCHK(hipMemcpyAsync(&n_seeds, d_total, 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
+        }
         IBCHK(hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
     }
     // value = nBases + overflow index must stay below the two reserved values (GenomeIndex.cpp:777)
     if (ovf_words64 + n_bases >= 0xFFFFFFFFull - 15 || ovf_words64 != ovf_words) return ib_fail(SNAPGPU_E_UNSUPPORTED, "not enough 32-bit address space for genome + overflow table (GenomeIndex.cpp:777): larger seed or location size needed");
-    bi->stats.n_distinct_seeds = n_runs; bi->overflow_words = ovf_words; bi->stats.overflow_table_size = ovf_words;
+    bi->stats.n_distinct_seeds = n_seeds; bi->overflow_words = ovf_words; bi->stats.overflow_table_size = ovf_words;
     IBCHK(hipEventRecord(ev[3], s), SNAPGPU_E_LAUNCH);
 
-    // ---- 4. tables: sizes from the exact distinct-seed counts (allocateHashTables, GenomeIndex.cpp:1084-1100 with bias = count * nTables / nBases)
+    // ---- 4. tables: sizes from the exact distinct-seed counts (allocateHashTables, GenomeIndex.cpp:1084-1100 with bias = count * nTables / nBases;
+    //      first_run[] counts canonical seeds under -large)
     std::vector<uint32_t> first_run((size_t)n_tables + 1, 0);
     if (m) {
         uint32_t *d_first = nullptr;
         IBCHK(mem.alloc(&d_first, ((size_t)n_tables + 1) * 4), SNAPGPU_E_NOMEM);
-        hipLaunchKernelGGL(k_ib_table_bounds, dim3((n_tables + 1 + 255) / 256), dim3(256), 0, s, d_keys, (const uint32_t *)d_run_start, n_runs, key_bits, n_tables, d_first);
+        hipLaunchKernelGGL(k_ib_table_bounds, dim3((n_tables + 1 + 255) / 256), dim3(256), 0, s, d_keys, (const uint32_t *)d_run_start, n_runs,
+                           key_bits + large, n_tables, large ? (const uint32_t *)d_need : nullptr, n_seeds, d_first);
         IBCHK(hipMemcpyAsync(first_run.data(), d_first, ((size_t)n_tables + 1) * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
         IBCHK(hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
     }
@@ -246,8 +257,9 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
     IBCHK(hipMalloc((void **)&bi->d_hash, (size_t)bi->hash_bytes + 64), SNAPGPU_E_NOMEM);
     IBCHK(hipMalloc((void **)&bi->d_overflow, ((size_t)ovf_words + 4) * 4), SNAPGPU_E_NOMEM);
     IBCHK(hipMemsetAsync(bi->d_overflow, 0, ((size_t)ovf_words + 4) * 4, s), SNAPGPU_E_LAUNCH);
-    if (entry_bytes == 8) hipLaunchKernelGGL(k_ib_fill_empty, dim3(grid), dim3(256), 0, s, bi->d_hash, total_slots + 8);
-    else hipLaunchKernelGGL(k_ib_fill_empty_wide, dim3(grid), dim3(256), 0, s, (uint32_t *)bi->d_hash, (total_slots * entry_bytes + 63) / 4, entry_bytes);
+    const bool cas_insert = entry_bytes == 8;           // (small tables with 4-byte keys: one compare-and-swap per seed)
+    if (cas_insert) hipLaunchKernelGGL(k_ib_fill_empty, dim3(grid), dim3(256), 0, s, bi->d_hash, total_slots + 8);
+    else hipLaunchKernelGGL(k_ib_fill_empty_wide, dim3(grid), dim3(256), 0, s, (uint32_t *)bi->d_hash, (total_slots * entry_bytes + 63) / 4, entry_bytes, 4 * value_count);
     if (m) {
         uint64_t *d_slot0 = nullptr, *d_tsize = nullptr; uint32_t *d_fail = nullptr;
         IBCHK(mem.alloc(&d_slot0, (size_t)n_tables * 8), SNAPGPU_E_NOMEM);
@@ -258,7 +270,7 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
         IBCHK(hipMemsetAsync(d_fail, 0, 4, s), SNAPGPU_E_LAUNCH);
         hipLaunchKernelGGL(k_ib_fill_overflow, dim3(grid), dim3(256), 0, s, d_vals, (const uint32_t *)d_head, (const uint32_t *)d_before, m,
                            (const uint32_t *)d_run_start, (const uint32_t *)d_ovf_off, bi->d_overflow);
-        if (entry_bytes == 8) {
+        if (cas_insert) {
             hipLaunchKernelGGL(k_ib_insert, dim3(grid), dim3(256), 0, s, d_keys, d_vals, (const uint32_t *)d_run_start, (const uint32_t *)d_ovf_off, n_runs,
                                key_bits, (uint32_t)n_bases, bi->d_hash, (const uint64_t *)d_slot0, (const uint64_t *)d_tsize, d_fail);
         } else {
@@ -267,7 +279,7 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
             IBCHK(mem.alloc(&d_claim, claim_bytes), SNAPGPU_E_NOMEM);
             IBCHK(hipMemsetAsync(d_claim, 0, claim_bytes, s), SNAPGPU_E_LAUNCH);
             hipLaunchKernelGGL(k_ib_insert_wide, dim3(grid), dim3(256), 0, s, d_keys, d_vals, (const uint32_t *)d_run_start, (const uint32_t *)d_ovf_off,
-                               n_runs, key_bits, (uint32_t)n_bases, (uint8_t *)bi->d_hash, entry_bytes, d_claim, (const uint64_t *)d_slot0,
+                               n_runs, key_bits, (uint32_t)n_bases, (uint8_t *)bi->d_hash, entry_bytes, value_count, d_claim, (const uint64_t *)d_slot0,
                                (const uint64_t *)d_tsize, d_fail);
         }
         IBCHK(hipGetLastError(), SNAPGPU_E_LAUNCH);
@@ -286,6 +298,7 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
     (void)hipEventElapsedTime(&ms, ev[0], ev[4]); bi->stats.ms_total_device = ms;
     uint64_t repeated = 0;
     {   // seeds with more than one occurrence = runs that needed overflow space: overflow words = repeated + their locations
+        // (under -large a run is a (seed, strand) run, so this counts overflow lists)
         // (kept cheap: derived on the host from what is already known)
         repeated = 0;
         if (ovf_words) {
@@ -299,7 +312,7 @@ static int ib_build_on_device(snapgpu_built_index *bi, double slack)
     return SNAPGPU_OK;
 }
 
-static int ib_check_shape(const snapgpu_index_build_params *bp, uint32_t *key_bytes)
+static int ib_check_shape(const snapgpu_index_build_params *bp, const snapgpu_index_build_shape *shape, uint32_t *key_bytes)
 {
     if (bp->seed_len < 8 || bp->seed_len > 32) return ib_fail(SNAPGPU_E_INVALID, "seed length must be between 8 and 32 (GenomeIndex.cpp:429)");
     uint32_t kb = bp->key_bytes;
@@ -309,9 +322,10 @@ static int ib_check_shape(const snapgpu_index_build_params *bp, uint32_t *key_by
     if (kb < 2 || kb > 8) return ib_fail(SNAPGPU_E_INVALID, "key size must be between 2 and 8 bytes (GenomeIndex.cpp:437, HashTable.h:148)");
     // a seed of 32 T's is the value this builder marks "no seed at this location" with (index_build.h: IB_INVALID_KEY)
     if (bp->seed_len == 32) return ib_fail(SNAPGPU_E_UNSUPPORTED, "the GPU index builder takes seeds up to 31 bases; use the reference's indexer for -s 32");
-    if (bp->seed_len < 20) {
-        // the reference picks 5-byte locations below seed 20 unless told otherwise (GenomeIndex.cpp:442-449); this builder always writes 4
-    }
+    // (the reference picks 5-byte locations below seed 20 unless told otherwise, GenomeIndex.cpp:442-449; here the caller's shape decides,
+    // and {0, 4} is the default)
+    if (shape->large > 1) return ib_fail(SNAPGPU_E_INVALID, "shape.large must be 0 or 1");
+    if (shape->location_size < 4 || shape->location_size > 8) return ib_fail(SNAPGPU_E_INVALID, "location size must be between 4 and 8 (GenomeIndex.cpp:196)");
     if (!(bp->slack > 0)) return ib_fail(SNAPGPU_E_INVALID, "slack must be positive (GenomeIndex.cpp:1040)");
     if (bp->chromosome_padding == 0) return ib_fail(SNAPGPU_E_INVALID, "chromosome padding must be at least one (GenomeIndex.cpp:216)");
     *key_bytes = kb;
@@ -339,12 +353,16 @@ static void ib_finish_contigs(snapgpu_built_index *bi)
     if (bi->cigar_ops.empty()) bi->cigar_ops.push_back(0);
 }
 
-extern "C" int snapgpu_index_build(const snapgpu_genome_view *g, const snapgpu_index_build_params *bp, int device, snapgpu_built_index **out)
+static const snapgpu_index_build_shape ib_default_shape = {0, 4};
+
+extern "C" int snapgpu_index_build_shaped(const snapgpu_genome_view *g, const snapgpu_index_build_params *bp, const snapgpu_index_build_shape *shape,
+                                         int device, snapgpu_built_index **out)
 {
     if (!g || !bp || !out || !g->bases) return ib_fail(SNAPGPU_E_INVALID, "snapgpu_index_build: null argument");
     *out = nullptr;
+    if (!shape) shape = &ib_default_shape;
     uint32_t kb = 0;
-    int rc = ib_check_shape(bp, &kb);
+    int rc = ib_check_shape(bp, shape, &kb);
     if (rc) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ib_fail(SNAPGPU_E_NODEVICE, "no HIP device available (the index builder has no CPU path)");
@@ -352,6 +370,7 @@ extern "C" int snapgpu_index_build(const snapgpu_genome_view *g, const snapgpu_i
     IBCHK(hipSetDevice(device), SNAPGPU_E_NODEVICE);
     snapgpu_built_index *bi = new snapgpu_built_index();
     bi->device = device; bi->seed_len = bp->seed_len; bi->key_bytes = kb; bi->chromosome_padding = bp->chromosome_padding; bi->n_bases = g->n_bases;
+    bi->large = shape->large; bi->location_size = shape->location_size;
     for (uint32_t i = 0; i < g->n_contigs; i++) {
         IBContig c;
         c.name = g->contig_name ? g->contig_name[i] : ("contig" + std::to_string(i));
@@ -373,6 +392,11 @@ extern "C" int snapgpu_index_build(const snapgpu_genome_view *g, const snapgpu_i
     if (rc) { snapgpu_built_index_destroy(bi); return rc; }
     *out = bi;
     return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_index_build(const snapgpu_genome_view *g, const snapgpu_index_build_params *bp, int device, snapgpu_built_index **out)
+{
+    return snapgpu_index_build_shaped(g, bp, &ib_default_shape, device, out);
 }
 
 // ---------------------------------------------------------------- FASTA -> genome image (ReadFASTAGenome, FASTA.cpp:188-409)
@@ -415,12 +439,14 @@ bool ib_read_liftover(const char *path, std::vector<Liftover> &out, std::string 
 
 }  // namespace
 
-extern "C" int snapgpu_index_build_from_fasta(const char *fasta_path, const snapgpu_index_build_params *bp, int device, snapgpu_built_index **out)
+extern "C" int snapgpu_index_build_from_fasta_shaped(const char *fasta_path, const snapgpu_index_build_params *bp, const snapgpu_index_build_shape *shape,
+                                                    int device, snapgpu_built_index **out)
 {
     if (!fasta_path || !bp || !out) return ib_fail(SNAPGPU_E_INVALID, "snapgpu_index_build_from_fasta: null argument");
     *out = nullptr;
+    if (!shape) shape = &ib_default_shape;
     uint32_t kb = 0;
-    int rc = ib_check_shape(bp, &kb);
+    int rc = ib_check_shape(bp, shape, &kb);
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     FILE *f = fopen(fasta_path, "rb");
@@ -503,9 +529,14 @@ extern "C" int snapgpu_index_build_from_fasta(const char *fasta_path, const snap
     g.contig_begin = begin.data(); g.contig_name = names.data(); g.contig_is_alt = alt.data(); g.contig_original_number = orig.data();
     g.contig_proj_begin = pbeg.data(); g.contig_proj_rc = prc.data(); g.contig_proj_cigar = pcig.data();
     const double s_fasta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    rc = snapgpu_index_build(&g, bp, device, out);
+    rc = snapgpu_index_build_shaped(&g, bp, shape, device, out);
     if (rc == SNAPGPU_OK) (*out)->stats.s_fasta = s_fasta;
     return rc;
+}
+
+extern "C" int snapgpu_index_build_from_fasta(const char *fasta_path, const snapgpu_index_build_params *bp, int device, snapgpu_built_index **out)
+{
+    return snapgpu_index_build_from_fasta_shaped(fasta_path, bp, &ib_default_shape, device, out);
 }
 
 extern "C" int snapgpu_built_index_stats(const snapgpu_built_index *bi, snapgpu_index_build_stats *out)
@@ -519,7 +550,7 @@ extern "C" int snapgpu_built_index_view(const snapgpu_built_index *bi, snapgpu_i
 {
     if (!bi || !v) return ib_fail(SNAPGPU_E_INVALID, "snapgpu_built_index_view: null argument");
     memset(v, 0, sizeof(*v));
-    v->seed_len = bi->seed_len; v->key_bytes = bi->key_bytes; v->n_hash_tables = bi->n_tables; v->large_hash_table = 0; v->location_size = 4;
+    v->seed_len = bi->seed_len; v->key_bytes = bi->key_bytes; v->n_hash_tables = bi->n_tables; v->large_hash_table = bi->large; v->location_size = 4;
     v->chromosome_padding = bi->chromosome_padding; v->overflow_table_size = bi->overflow_words;
     v->hash_blob = (const uint8_t *)bi->d_hash; v->hash_blob_bytes = bi->hash_bytes + 16;
     v->table_offset = bi->table_offset.data(); v->table_size = bi->table_size.data();
@@ -548,6 +579,31 @@ int ib_copy_out(FILE *f, const void *d_src, size_t bytes, std::vector<uint8_t> &
     }
     return SNAPGPU_OK;
 }
+// The same for -locationSize 5..8: n 4-byte words of `d_src` -- hash-table entries of value_count values and key_bytes of key, or (key_bytes
+// 0, value_count 1) overflow words -- go out with every value widened to out_bytes: 0xffffffff (unused) and 0xfffffffe (-large: the other
+// strand only) become all ones and all ones minus one (GenomeIndex.cpp:511-517, :1566), anything else is zero-extended (GenomeIndex.cpp:
+// 855-868).  Chunk by chunk through `buf`: no second copy of the table in host memory.
+int ib_copy_out_widened(FILE *f, const void *d_src, uint64_t n, uint32_t value_count, uint32_t key_bytes, uint32_t out_bytes, std::vector<uint8_t> &buf) {
+    const uint32_t in_entry = 4 * value_count + key_bytes, out_entry = out_bytes * value_count + key_bytes;
+    const uint64_t ones = out_bytes == 8 ? ~0ull : (1ull << (8 * out_bytes)) - 1;
+    const size_t per_chunk = buf.size() / (in_entry + out_entry);               // entries per chunk: source, then its widened form, in buf
+    uint8_t *in = buf.data(), *out = buf.data() + per_chunk * in_entry;
+    for (uint64_t first = 0; first < n; first += per_chunk) {
+        const size_t k = n - first < per_chunk ? (size_t)(n - first) : per_chunk;
+        if (hipMemcpy(in, (const uint8_t *)d_src + first * in_entry, k * in_entry, hipMemcpyDeviceToHost) != hipSuccess) return ib_fail(SNAPGPU_E_NODEVICE, "device-to-host copy failed while saving the index");
+        for (size_t i = 0; i < k; i++) {
+            const uint8_t *e = in + i * in_entry; uint8_t *o = out + i * out_entry;
+            for (uint32_t v = 0; v < value_count; v++) {
+                uint32_t x; memcpy(&x, e + 4 * v, 4);
+                const uint64_t w = x == 0xffffffffu ? ones : x == 0xfffffffeu ? ones - 1 : (uint64_t)x;
+                for (uint32_t b = 0; b < out_bytes; b++) o[out_bytes * v + b] = (uint8_t)(w >> (8 * b));
+            }
+            memcpy(o + out_bytes * value_count, e + 4 * value_count, key_bytes);
+        }
+        if (!ib_write_all(f, out, k * out_entry)) return ib_fail(SNAPGPU_E_INVALID, std::string("write failed while saving the index: ") + strerror(errno));
+    }
+    return SNAPGPU_OK;
+}
 }  // namespace
 
 extern "C" int snapgpu_built_index_save(const snapgpu_built_index *bi, const char *directory)
@@ -572,25 +628,30 @@ extern "C" int snapgpu_built_index_save(const snapgpu_built_index *bi, const cha
         fclose(f);
         if (rc) return rc;
     }
+    // values: 4 bytes on the device, location_size bytes in the files
+    const uint32_t vs = bi->location_size, vc = bi->large ? 2 : 1, ks = bi->key_bytes;
     size_t hash_file_bytes = 0;
     {   // GenomeIndexHash: per table magic, tableSize, usedElementCount, keySize, valueSize, valueCount, invalidValue, slots (HashTable.cpp:199-262)
         FILE *f = fopen((dir + "/GenomeIndexHash").c_str(), "wb");
         if (!f) return ib_fail(SNAPGPU_E_INVALID, "unable to open " + dir + "/GenomeIndexHash");
+        const uint8_t inv[8] = {0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff};      // invalidValue: vs bytes of ones
         for (uint32_t t = 0; t < bi->n_tables; t++) {
-            const uint32_t magic = 0xb111b010u, ks = bi->key_bytes, vs = 4, vc = 1, inv = 0xffffffffu;
+            const uint32_t magic = 0xb111b010u;
             const uint64_t size = bi->table_size[t], used = bi->table_used[t];
             if (!ib_write_all(f, &magic, 4) || !ib_write_all(f, &size, 8) || !ib_write_all(f, &used, 8) || !ib_write_all(f, &ks, 4) ||
-                !ib_write_all(f, &vs, 4) || !ib_write_all(f, &vc, 4) || !ib_write_all(f, &inv, 4)) { fclose(f); return ib_fail(SNAPGPU_E_INVALID, "write failed (GenomeIndexHash)"); }
-            rc = ib_copy_out(f, (const uint8_t *)bi->d_hash + bi->table_offset[t], (size_t)size * (4 + ks), buf);
+                !ib_write_all(f, &vs, 4) || !ib_write_all(f, &vc, 4) || !ib_write_all(f, inv, vs)) { fclose(f); return ib_fail(SNAPGPU_E_INVALID, "write failed (GenomeIndexHash)"); }
+            const uint8_t *src = (const uint8_t *)bi->d_hash + bi->table_offset[t];
+            rc = vs == 4 ? ib_copy_out(f, src, (size_t)size * (4 * vc + ks), buf) : ib_copy_out_widened(f, src, size, vc, ks, vs, buf);
             if (rc) { fclose(f); return rc; }
-            hash_file_bytes += 36 + (size_t)size * (4 + ks);
+            hash_file_bytes += 32 + vs + (size_t)size * (vs * vc + ks);
         }
         fclose(f);
     }
-    {   // OverflowTable
+    {   // OverflowTable: 4-byte words, or 8-byte ones for wider locations (GenomeIndex.cpp:973)
         FILE *f = fopen((dir + "/OverflowTable").c_str(), "wb");
         if (!f) return ib_fail(SNAPGPU_E_INVALID, "unable to open " + dir + "/OverflowTable");
-        rc = ib_copy_out(f, bi->d_overflow, (size_t)bi->overflow_words * 4, buf);
+        rc = vs == 4 ? ib_copy_out(f, bi->d_overflow, (size_t)bi->overflow_words * 4, buf)
+                     : ib_copy_out_widened(f, bi->d_overflow, bi->overflow_words, 1, 0, 8, buf);
         fclose(f);
         if (rc) return rc;
     }
@@ -598,7 +659,7 @@ extern "C" int snapgpu_built_index_save(const snapgpu_built_index *bi, const cha
         FILE *f = fopen((dir + "/GenomeIndex").c_str(), "w");
         if (!f) return ib_fail(SNAPGPU_E_INVALID, "unable to open " + dir + "/GenomeIndex");
         fprintf(f, "%d %d %d %lld %d %d %d %lld %d %d", 7, 1, (int)bi->n_tables, (long long)bi->overflow_words, (int)bi->seed_len,
-                (int)bi->chromosome_padding, (int)bi->key_bytes, (long long)hash_file_bytes, 1, 4);
+                (int)bi->chromosome_padding, (int)bi->key_bytes, (long long)hash_file_bytes, bi->large ? 0 : 1, (int)vs);
         fclose(f);
     }
     return SNAPGPU_OK;

@@ -226,17 +226,20 @@ class GenomeIndex:
 
 def build_index(fasta: str, out_dir: str | None, seed_len: int = 20, slack: float = 0.3, key_bytes: int = 0, padding: int = 2000,
                 device: int = 0, alt_liftover_file: str | None = None, alt_contig_names=(), non_alt_contig_names=(), auto_alt: bool = True,
-                max_alt_contig_size: int = -1, space_terminates_name: bool = True, lib=None, keep: bool = False):
+                max_alt_contig_size: int = -1, space_terminates_name: bool = True, large: bool = False, location_size: int = 4,
+                lib=None, keep: bool = False):
     """`snap-aligner index <fasta> <out_dir> -s <seed_len> ...` with the build on the GPU (GenomeIndex::runIndexer,
-    SNAPLib/GenomeIndex.cpp:126-506; include/snapgpu.h: snapgpu_index_build_from_fasta / snapgpu_built_index_save).
+    SNAPLib/GenomeIndex.cpp:126-506; include/snapgpu.h: snapgpu_index_build_from_fasta_shaped / snapgpu_built_index_save).
+    large / location_size: `-large` and `-locationSize 4..8` (the default stays 4 whatever the seed length).
     Writes the reference's four files into out_dir (None: nothing is written) and returns the build's statistics; with keep=True returns
     (stats, BuiltIndex) -- the index still resident in HBM, to hand to an aligner without going through the files."""
     import ctypes as C
-    from .abi import IndexBuildParams, IndexBuildStats
+    from .abi import IndexBuildParams, IndexBuildShape, IndexBuildStats
     if lib is None:
         from .aligner import load_library
         lib = load_library()
-    lib.snapgpu_index_build_from_fasta.argtypes = [C.c_char_p, C.POINTER(IndexBuildParams), C.c_int, C.POINTER(C.c_void_p)]
+    lib.snapgpu_index_build_from_fasta_shaped.argtypes = [C.c_char_p, C.POINTER(IndexBuildParams), C.POINTER(IndexBuildShape), C.c_int,
+                                                          C.POINTER(C.c_void_p)]
     lib.snapgpu_built_index_save.argtypes = [C.c_void_p, C.c_char_p]
     lib.snapgpu_built_index_stats.argtypes = [C.c_void_p, C.POINTER(IndexBuildStats)]
     lib.snapgpu_built_index_destroy.argtypes = [C.c_void_p]
@@ -260,10 +263,11 @@ def build_index(fasta: str, out_dir: str | None, seed_len: int = 20, slack: floa
             keepalive.append(arr)
             setattr(bp, field, arr)
             setattr(bp, "n_" + field, len(names))
+    shape = IndexBuildShape(1 if large else 0, location_size)
     h = C.c_void_p()
-    rc = lib.snapgpu_index_build_from_fasta(fasta.encode(), C.byref(bp), C.c_int(device), C.byref(h))
+    rc = lib.snapgpu_index_build_from_fasta_shaped(fasta.encode(), C.byref(bp), C.byref(shape), C.c_int(device), C.byref(h))
     if rc != 0:
-        raise RuntimeError("snapgpu_index_build_from_fasta failed (%d): %s" % (rc, (lib.snapgpu_last_error(None) or b"").decode()))
+        raise RuntimeError("snapgpu_index_build_from_fasta_shaped failed (%d): %s" % (rc, (lib.snapgpu_last_error(None) or b"").decode()))
     try:
         if out_dir is not None:
             rc = lib.snapgpu_built_index_save(h, out_dir.encode())
