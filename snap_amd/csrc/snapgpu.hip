@@ -281,7 +281,7 @@ struct DevPool {
         slots.push_back(Slot{p, cap, true, 0ull});
         return p;
     }
-    // (a buffer comes back with whatever its last user left in it: DevBuf memory is UNINITIALISED, every kernel clears what it needs)
+    // (a buffer comes back with whatever its last user left in it: pool memory is UNINITIALISED, every kernel clears what it needs)
     // Idle buffers are kept for the next call of a similar size, but not without bound: batches of varying size (a last short one, a retry
     // with a larger cigar stride, one-read calls of the host record loop) would otherwise leave gigabytes of per-wave scratch pinned next to
     // the index.  More than MAX_IDLE idle buffers, or more than MAX_IDLE_BYTES of them: the largest idle ones go.
@@ -341,9 +341,6 @@ struct snapgpu_ctx {
     uint32_t n_wave_slots = 0;
     uint32_t *d_work = nullptr;
     unsigned long long *d_counters = nullptr;
-    // staging for the host-pointer entry points
-    void *d_stage[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t stage_cap[5] = {0, 0, 0, 0, 0};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double kernel_ms = 0.0;
     uint64_t kernel_launches = 0;
@@ -356,8 +353,6 @@ struct snapgpu_ctx {
     SecCfg sec_cfg{};
     uint8_t *d_sec_scratch = nullptr;
     uint64_t sec_stride_bytes = 0;
-    void *d_sec_stage[2] = {nullptr, nullptr};       // secondary records, counts (host-pointer entry point)
-    size_t sec_stage_cap[2] = {0, 0};
     // paired-end path (snapgpu_enable_paired)
     bool paired = false;
     snapgpu_paired_params pparams{};
@@ -398,8 +393,6 @@ struct snapgpu_ctx {
     uint8_t *d_pscratch_sec = nullptr, *d_pscratch_sec_big = nullptr;
     uint32_t p_sec_slots = 0, p_sec_big_slots = 0;
     int paired_share = 1;               // calls in flight on the device when this context's current paired-end call began (PairedInFlight)
-    void *d_psec_stage[4] = {nullptr, nullptr, nullptr, nullptr};      // paired secondary, counts, single secondary, counts
-    size_t psec_stage_cap[4] = {0, 0, 0, 0};
     // what snapgpu_create was given, minus the blobs: lets snapgpu_create_replica build another context over the same index
     snapgpu_index_view view_meta{};
     std::vector<uint64_t> h_table_offset, h_table_size, h_contig_begin, h_proj_begin;
@@ -407,22 +400,18 @@ struct snapgpu_ctx {
     std::string err;
 };
 
-#define HIPCHK(ctx, call, code)                                                                   \
-    do {                                                                                          \
-        hipError_t _e = (call);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            std::string m = std::string(#call) + ": " + hipGetErrorString(_e);                    \
-            if (ctx) (ctx)->err = m;                                                              \
-            g_last_error = m;                                                                     \
-            return (code);                                                                        \
-        }                                                                                         \
-    } while (0)
-
 static int fail(snapgpu_ctx *ctx, int code, const std::string &msg) {
     if (ctx) ctx->err = msg;
     g_last_error = msg;
     return code;
 }
+static int hip_fail(snapgpu_ctx *ctx, const char *call, hipError_t e, int code) { return fail(ctx, code, std::string(call) + ": " + hipGetErrorString(e)); }
+
+#define HIPCHK(ctx, call, code)                                                                   \
+    do {                                                                                          \
+        hipError_t _e = (call);                                                                   \
+        if (_e != hipSuccess) return hip_fail(ctx, #call, _e, code);                              \
+    } while (0)
 
 // The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and a hardware queue runs its kernels in
 // order: two feeders whose streams land on one queue take turns, whatever their grids ask for.  Seen in the driver's bench command, whose paired-end
@@ -524,16 +513,6 @@ static void build_tables(DevTables &t, unsigned seed_len) {
 
 static uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 
-static int ensure_stage(snapgpu_ctx *ctx, int which, size_t bytes) {
-    if (ctx->stage_cap[which] >= bytes) return 0;
-    if (ctx->d_stage[which]) (void)hipFree(ctx->d_stage[which]);
-    ctx->d_stage[which] = nullptr; ctx->stage_cap[which] = 0;
-    size_t cap = bytes + bytes / 4 + 4096;
-    HIPCHK(ctx, hipMalloc(&ctx->d_stage[which], cap), SNAPGPU_E_NOMEM);
-    ctx->stage_cap[which] = cap;
-    return 0;
-}
-
 extern "C" void snapgpu_destroy(snapgpu_ctx *ctx) {
     if (!ctx) return;
     if (ctx->device >= 0) (void)hipSetDevice(ctx->device);
@@ -548,7 +527,6 @@ extern "C" void snapgpu_destroy(snapgpu_ctx *ctx) {
         if (ctx->d_n_buckets) (void)hipFree(ctx->d_n_buckets);
     }
     if (ctx->d_sec_scratch) (void)hipFree(ctx->d_sec_scratch);
-    for (int i = 0; i < 2; i++) if (ctx->d_sec_stage[i]) (void)hipFree(ctx->d_sec_stage[i]);
     if (ctx->d_table_offset) (void)hipFree(ctx->d_table_offset);
     if (ctx->d_table_size) (void)hipFree(ctx->d_table_size);
     if (ctx->d_contig_begin) (void)hipFree(ctx->d_contig_begin);
@@ -559,7 +537,6 @@ extern "C" void snapgpu_destroy(snapgpu_ctx *ctx) {
     if (ctx->d_pscratch_big) (void)hipFree(ctx->d_pscratch_big);
     if (ctx->d_pscratch_sec) (void)hipFree(ctx->d_pscratch_sec);
     if (ctx->d_pscratch_sec_big) (void)hipFree(ctx->d_pscratch_sec_big);
-    for (int i = 0; i < 4; i++) if (ctx->d_psec_stage[i]) (void)hipFree(ctx->d_psec_stage[i]);
     if (ctx->d_flag_list) (void)hipFree(ctx->d_flag_list);
     if (ctx->d_exact_persist) (void)hipFree(ctx->d_exact_persist);
     if (ctx->d_pexact_persist) (void)hipFree(ctx->d_pexact_persist);
@@ -577,7 +554,6 @@ extern "C" void snapgpu_destroy(snapgpu_ctx *ctx) {
     ctx->pool.free_all();
     if (ctx->d_work) (void)hipFree(ctx->d_work);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-    for (int i = 0; i < 5; i++) if (ctx->d_stage[i]) (void)hipFree(ctx->d_stage[i]);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1261,1063 +1237,8 @@ extern "C" int snapgpu_index_device_ptrs(snapgpu_ctx *ctx, void **hash_blob, voi
     return SNAPGPU_OK;
 }
 
-// the index-probe kernel: sixteen probes per wave pass (lookup16.h) for the shape the north star uses, k_lookup_seeds for every other
-static void launch_lookup(snapgpu_ctx *ctx, uint32_t n, const void *d_seeds, void *d_n_hits, void *d_hits, uint32_t max_hits_out,
-                          unsigned long long *d_counters, hipStream_t s)
-{
-    const uint32_t maxb = (uint32_t)ctx->num_cus * 8;                                   // 32 waves per CU
-    if (ctx->ix.bucket_blob && ctx->ix.seed_len == 20 && ctx->ix.key_bytes == 4 && ((uintptr_t)d_seeds & 3) == 0 && !getenv("SNAPGPU_LOOKUP8")) {
-        uint32_t blocks = (n + 31) / 32; if (blocks > maxb) blocks = maxb;
-        // as many blocks as are resident at once (see the kernel): every wave then does an equal share of the passes from the start
-        // (per context: contexts live on different devices and are driven by different threads)
-        if (ctx->lookup_blocks_per_cu == 0) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_lookup_seeds20, 256, 0) != hipSuccess || nb <= 0) nb = 4;
-            if (const char *e = getenv("SNAPGPU_LOOKUP_BLOCKS_PER_CU")) { const int v = atoi(e); if (v >= 1 && v <= 8) nb = v; }
-            ctx->lookup_blocks_per_cu = nb > 8 ? 8 : nb;
-        }
-        const uint32_t fit = (uint32_t)ctx->num_cus * (uint32_t)ctx->lookup_blocks_per_cu;
-        if (blocks > fit) blocks = fit;
-        hipLaunchKernelGGL(k_lookup_seeds20, dim3(blocks), dim3(256), 0, s, ctx->ix, n, (const uint8_t *)d_seeds, (long long *)d_n_hits,
-                           (uint32_t *)d_hits, max_hits_out, d_counters);
-    } else {
-        uint32_t blocks = (n + 3) / 4; if (blocks > maxb) blocks = maxb;
-        hipLaunchKernelGGL(k_lookup_seeds, dim3(blocks), dim3(256), 0, s, ctx->ix, n, (const uint8_t *)d_seeds, (long long *)d_n_hits,
-                           (uint32_t *)d_hits, max_hits_out, d_counters);
-    }
-}
-
-extern "C" int snapgpu_lookup_seeds(snapgpu_ctx *ctx, uint32_t n, const char *seeds, int64_t *n_hits,
-                                    uint32_t *hits, uint32_t max_hits_out)
-{
-    if (!ctx || !seeds || !n_hits || !hits || max_hits_out == 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_lookup_seeds: bad argument");
-    if (n == 0) return SNAPGPU_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    size_t sb = (size_t)n * ctx->ix.seed_len, nb = (size_t)n * 2 * 8, hb = (size_t)n * 2 * max_hits_out * 4;
-    int rc;
-    if ((rc = ensure_stage(ctx, 0, sb)) || (rc = ensure_stage(ctx, 1, nb)) || (rc = ensure_stage(ctx, 2, hb))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[0], seeds, sb, hipMemcpyHostToDevice, ctx->stream), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_stage[2], 0, hb, ctx->stream), SNAPGPU_E_LAUNCH);
-    launch_lookup(ctx, n, ctx->d_stage[0], ctx->d_stage[1], ctx->d_stage[2], max_hits_out, nullptr, ctx->stream);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_hits, ctx->d_stage[1], nb, hipMemcpyDeviceToHost, ctx->stream), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(hits, ctx->d_stage[2], hb, hipMemcpyDeviceToHost, ctx->stream), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), SNAPGPU_E_LAUNCH);
-    return SNAPGPU_OK;
-}
-
-static int finish_timing(snapgpu_ctx *ctx);
-// Device-pointer form of snapgpu_lookup_seeds: seeds, hit counts and (optionally) hits already in HBM.  d_hits == NULL: counts only
-// (the lists are read, not stored).  Timed with hipEvents like the align kernels (snapgpu_kernel_time) and counted into
-// snapgpu_counters (lookups, slots, hits, overflow lists): the index-probe kernel on its own, for its HBM roofline (bench.py).
-extern "C" int snapgpu_lookup_seeds_device(snapgpu_ctx *ctx, uint32_t n, const void *d_seeds, void *d_n_hits, void *d_hits,
-                                           uint32_t max_hits_out, void *stream)
-{
-    if (!ctx || !d_seeds || !d_n_hits || max_hits_out == 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_lookup_seeds_device: bad argument");
-    if (n == 0) return SNAPGPU_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    launch_lookup(ctx, n, d_seeds, d_n_hits, d_hits, max_hits_out, ctx->d_counters, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    if (!stream) return finish_timing(ctx);
-    return SNAPGPU_OK;
-}
-
-// small RAII helper for per-call device buffers of the (test-oriented) batch primitives
-// Device buffers of the host-pointer entry points.  Until round 4 each call hipMalloc'ed its buffers and hipFree'd them on return -- fifteen
-// of them in snapgpu_sam_fields_single, half a gigabyte of per-wave scratch among them, and every hipFree synchronises the device: at 65 536
-// reads per batch snapgpu-sam spent ~200 ms per batch there against ~25 ms of kernels (profiles/r04j: 0.58 M reads/s end to end).  Now a
-// context keeps what it has allocated: a buffer goes back to the context's pool when the call returns and the next call of a similar size
-// takes it again.  (Calls on one context are serial, and every entry point synchronises its stream before it returns.)
-static thread_local DevPool *t_pool = nullptr;
-// blocks per CU of the SAM-field kernels' persistent grids (SNAPGPU_SAMF_BLOCKS_PER_CU: measurement knob; default 8 = the kernels' launch bounds)
-static uint32_t samf_blocks_per_cu() { static int v = 0; if (!v) { const char *e = getenv("SNAPGPU_SAMF_BLOCKS_PER_CU"); v = e ? atoi(e) : 8; if (v < 1 || v > 8) v = 8; } return (uint32_t)v; }       // the pool of the context whose entry point this thread is in
-struct PoolScope {
-    DevPool *prev;
-    explicit PoolScope(DevPool *p) : prev(t_pool) { t_pool = p; }
-    ~PoolScope() { t_pool = prev; }
-};
-struct DevBuf {
-    void *p = nullptr;
-    DevPool *from = nullptr;
-    ~DevBuf() { if (p) { if (from) from->release(p); else (void)hipFree(p); } }
-    hipError_t put(const void *src, size_t bytes, hipStream_t s, size_t slack = 0) {      // slack: bytes allocated beyond what is copied
-        hipError_t e;
-        if (t_pool) { from = t_pool; p = from->acquire(bytes + slack ? bytes + slack : 16, &e); }
-        else e = hipMalloc(&p, bytes + slack ? bytes + slack : 16);
-        if (e != hipSuccess) return e;
-        if (src && bytes) return hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s);
-        return hipSuccess;
-    }
-};
-
-extern "C" int snapgpu_landau_vishkin(snapgpu_ctx *ctx, int dir, uint32_t n,
-                                      const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,
-                                      const char *patterns, const char *quals, uint64_t patterns_bytes,
-                                      const uint32_t *pat_off, const int32_t *pat_len, const int32_t *k,
-                                      int32_t *score, double *match_probability, int32_t *net_indel,
-                                      int32_t *total_indels, int32_t *text_span)
-{
-    if (!ctx || (dir != 1 && dir != -1)) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_landau_vishkin: bad argument");
-    if (n == 0) return SNAPGPU_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    uint32_t kmax = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (pat_len[i] < 0 || pat_len[i] > 1000) return fail(ctx, SNAPGPU_E_INVALID, "pattern length out of range");
-        int kk = k[i] > 126 ? 126 : k[i];
-        if (kk > (int)kmax) kmax = (uint32_t)kk;
-    }
-    hipStream_t s = ctx->stream;
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf dt, dto, dtl, dp, dq, dpo, dpl, dk, ds, dpr, dni, dti, dts;
-    HIPCHK(ctx, dt.put(texts, texts_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dto.put(text_off, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dtl.put(text_len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dp.put(patterns, patterns_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dq.put(quals, patterns_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpo.put(pat_off, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpl.put(pat_len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dk.put(k, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, ds.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpr.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dni.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dti.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dts.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    LVBatchArgs a;
-    a.dir = dir; a.n = n; a.kmax = kmax;
-    uint32_t pcap = 64;
-    for (uint32_t i = 0; i < n; i++) if ((uint32_t)pat_len[i] > pcap) pcap = (uint32_t)pat_len[i];
-    a.pcap = (pcap + 63) & ~63u;
-    a.texts = (const uint8_t *)dt.p; a.text_off = (const uint32_t *)dto.p; a.text_len = (const int32_t *)dtl.p;
-    a.patterns = (const uint8_t *)dp.p; a.quals = (const uint8_t *)dq.p; a.pat_off = (const uint32_t *)dpo.p;
-    a.pat_len = (const int32_t *)dpl.p; a.k = (const int32_t *)dk.p;
-    a.score = (int32_t *)ds.p; a.prob = (double *)dpr.p; a.net_indel = (int32_t *)dni.p;
-    a.total_indels = (int32_t *)dti.p; a.text_span = (int32_t *)dts.p; a.tab = ctx->d_tab;
-    uint32_t per_wave = (lv_lds_bytes(kmax, a.pcap) + 15) & ~15u;
-    uint32_t waves_per_block = 4;
-    while (waves_per_block > 1 && (size_t)waves_per_block * per_wave > 64 * 1024) waves_per_block >>= 1;
-    if ((size_t)waves_per_block * per_wave > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "k too large for the LDS triangle");
-    uint32_t blocks = (n + waves_per_block - 1) / waves_per_block; uint32_t maxb = (uint32_t)ctx->num_cus * 8; if (blocks > maxb) blocks = maxb;
-    hipLaunchKernelGGL(k_lv_batch, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * per_wave, s, a);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(score, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(match_probability, dpr.p, (size_t)n * 8, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(net_indel, dni.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(total_indels, dti.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(text_span, dts.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return SNAPGPU_OK;
-}
-
-// kernel time of the SAM-side launches, into the same accumulator snapgpu_kernel_time reads (events recorded around the launch)
-static int sam_side_kernel_time(snapgpu_ctx *ctx)
-{
-    float ms = 0.f;
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1), SNAPGPU_E_LAUNCH);
-    ctx->kernel_ms += ms; ctx->kernel_launches++;
-    return SNAPGPU_OK;
-}
-
-// SAMFormat::computeCigar, Landau-Vishkin variant, for a batch of written reads (cigar_lv.h, cigar_k.hip).
-extern "C" int snapgpu_compute_cigar_lv(snapgpu_ctx *ctx, uint32_t n, const char *data, uint64_t data_bytes, const uint64_t *off,
-                                        const int32_t *len, const int64_t *loc, const int32_t *extra_before, int use_m,
-                                        uint32_t *ops, uint32_t ops_stride, int32_t *n_ops, int32_t *edit_distance,
-                                        int32_t *add_front_clipping, int64_t *extra_clipped_after)
-{
-    if (!ctx || (n && (!data || !off || !len || !loc || !extra_before || !ops || !n_ops || !edit_distance || !add_front_clipping || !extra_clipped_after)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: null argument");
-    if (ops_stride == 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: ops_stride must be positive");
-    if (n == 0) return SNAPGPU_OK;
-    uint32_t RL = 64;
-    for (uint32_t i = 0; i < n; i++) {
-        if (len[i] < 0 || len[i] > 4000) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: read length out of range");
-        if (extra_before[i] < 0 || extra_before[i] > len[i]) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: extra_before out of range");
-        if (off[i] + (uint64_t)len[i] > data_bytes) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: read outside the data buffer");
-        if (loc[i] < 0 || (uint64_t)loc[i] >= ctx->ix.n_bases) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: location outside the genome");
-        if ((uint32_t)len[i] > RL) RL = (uint32_t)len[i];
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = ctx->stream;
-    const uint32_t per_wave = lvc_lds_bytes(RL);
-    uint32_t blocks = (uint32_t)ctx->num_cus * 4;                    // persistent grid: 16 waves per CU
-    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf dd, doff, dlen, dloc, dxb, dscr, dops, dno, ded, dafc, dxa;
-    HIPCHK(ctx, dd.put(data, data_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, doff.put(off, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dlen.put(len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dloc.put(loc, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dxb.put(extra_before, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dscr.put(nullptr, (size_t)blocks * 4 * lvc_scratch_bytes(), s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dops.put(nullptr, (size_t)n * ops_stride * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dno.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, ded.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dafc.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dxa.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, hipMemsetAsync(dops.p, 0, (size_t)n * ops_stride * 4, s), SNAPGPU_E_LAUNCH);
-    CigarArgs a;
-    a.ix = ctx->ix; a.n = n; a.RL = RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u;
-    a.data = (const uint8_t *)dd.p; a.off = (const uint64_t *)doff.p; a.len = (const int32_t *)dlen.p; a.loc = (const int64_t *)dloc.p;
-    a.extra_before = (const int32_t *)dxb.p; a.scratch = (uint8_t *)dscr.p; a.work_counter = ctx->d_work;
-    a.ops = (uint32_t *)dops.p; a.n_ops = (int32_t *)dno.p; a.edit_distance = (int32_t *)ded.p;
-    a.add_front_clipping = (int32_t *)dafc.p; a.extra_after = (int64_t *)dxa.p;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    snapgpu_launch_cigar_lv(&a, blocks, (size_t)4 * per_wave, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ops, dops.p, (size_t)n * ops_stride * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_ops, dno.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(edit_distance, ded.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(add_front_clipping, dafc.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(extra_clipped_after, dxa.p, (size_t)n * 8, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return sam_side_kernel_time(ctx);
-}
-
-// AlignmentAdjuster::AdjustAlignment for a batch of results (adjust.h, cigar_k.hip)
-extern "C" int snapgpu_adjust_alignments(snapgpu_ctx *ctx, uint32_t n, const char *data, uint64_t data_bytes, const uint64_t *off, const int32_t *len,
-                                         snapgpu_single_result *results)
-{
-    if (!ctx || (n && (!data || !off || !len || !results))) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: null argument");
-    if (n == 0) return SNAPGPU_OK;
-    uint32_t RL = 64;
-    for (uint32_t i = 0; i < n; i++) {
-        if (len[i] < 1 || len[i] > 4000) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: read length out of range");
-        if (off[i] + (uint64_t)len[i] > data_bytes) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: read outside the data buffer");
-        if (results[i].status != SNAPGPU_NotFound && (results[i].location < 0 || (uint64_t)results[i].location >= ctx->ix.n_bases))
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: location outside the genome");
-        if (results[i].direction != 0 && results[i].direction != 1) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: direction must be 0 (forward) or 1 (reverse complement)");
-        if ((uint32_t)len[i] > RL) RL = (uint32_t)len[i];
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = ctx->stream;
-    uint32_t blocks = (uint32_t)ctx->num_cus * 4;
-    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
-    const uint64_t stride = 2 * (uint64_t)((RL + 255) & ~255u) + ((adjust_scratch_bytes(RL) + 255) & ~(uint64_t)255);
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf dd, doff, dlen, dres, dscr;
-    HIPCHK(ctx, dd.put(data, data_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, doff.put(off, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dlen.put(len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dres.put(results, (size_t)n * sizeof(snapgpu_single_result), s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dscr.put(nullptr, (size_t)blocks * 4 * stride, s), SNAPGPU_E_NOMEM);
-    AdjustArgs a;
-    a.ix = ctx->ix; a.n = n; a.RL = RL; a.data = (const uint8_t *)dd.p; a.off = (const uint64_t *)doff.p; a.len = (const int32_t *)dlen.p;
-    a.results = (snapgpu_single_result *)dres.p; a.scratch = (uint8_t *)dscr.p; a.scratch_stride = stride; a.work_counter = ctx->d_work;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    snapgpu_launch_adjust_alignments(&a, blocks, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(results, dres.p, (size_t)n * sizeof(snapgpu_single_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return sam_side_kernel_time(ctx);
-}
-
-// SAMFormat::computeCigar, affine-gap variant, for a batch of written reads (cigar_ag.h, cigar_k.hip).
-extern "C" int snapgpu_compute_cigar_ag(snapgpu_ctx *ctx, uint32_t n, const char *data, const char *quals, uint64_t data_bytes,
-                                        const uint64_t *off, const int32_t *len, const int64_t *loc, const int32_t *extra_before,
-                                        const int32_t *score, int use_m, uint32_t *ops, uint32_t ops_stride, int32_t *n_ops,
-                                        int32_t *edit_distance, int32_t *add_front_clipping, int64_t *extra_clipped_after,
-                                        int32_t *back_clipping_missed, int32_t *reference_history_dependent)
-{
-    if (!ctx || (n && (!data || !quals || !off || !len || !loc || !extra_before || !score || !ops || !n_ops || !edit_distance ||
-                       !add_front_clipping || !extra_clipped_after || !back_clipping_missed || !reference_history_dependent)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: null argument");
-    if (ops_stride == 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: ops_stride must be positive");
-    if (n == 0) return SNAPGPU_OK;
-    uint32_t RL = 64;
-    for (uint32_t i = 0; i < n; i++) {
-        if (len[i] < 0 || len[i] > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: read length out of range");
-        if (extra_before[i] < 0 || extra_before[i] > len[i]) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: extra_before out of range");
-        if (off[i] + (uint64_t)len[i] > data_bytes) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: read outside the data buffer");
-        if (loc[i] < 0 || (uint64_t)loc[i] >= ctx->ix.n_bases) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: location outside the genome");
-        if (score[i] < 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: negative score");
-        if ((uint32_t)len[i] > RL) RL = (uint32_t)len[i];
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = ctx->stream;
-    const uint32_t per_wave = agc_lds_bytes(RL);
-    uint32_t waves_per_block = 4;
-    if ((size_t)waves_per_block * per_wave > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "snapgpu_compute_cigar_ag: reads too long for the LDS rows");
-    uint32_t blocks = (uint32_t)ctx->num_cus * 4;
-    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
-    const uint64_t scratch_stride = (agc_scratch_bytes(RL) + 255) & ~(uint64_t)255;
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf dd, dq, doff, dlen, dloc, dxb, dsc, dscr, dops, dno, ded, dafc, dxa, dti, dst;
-    HIPCHK(ctx, dd.put(data, data_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dq.put(quals, data_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, doff.put(off, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dlen.put(len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dloc.put(loc, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dxb.put(extra_before, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dsc.put(score, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dscr.put(nullptr, (size_t)blocks * 4 * scratch_stride, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dops.put(nullptr, (size_t)n * ops_stride * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dno.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, ded.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dafc.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dxa.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dti.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dst.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, hipMemsetAsync(dops.p, 0, (size_t)n * ops_stride * 4, s), SNAPGPU_E_LAUNCH);
-    CigarAGArgs a;
-    a.ix = ctx->ix;
-    // AffineGapVectorizedWithCigar's constructor (AffineGapVectorized.cpp:15-23): subPenalty negated, gapOpen = open + extend
-    a.prm.match = (int)ctx->params.match_reward; a.prm.sub = -(int)ctx->params.sub_penalty;
-    a.prm.gap_open = (int)ctx->params.gap_open_penalty + (int)ctx->params.gap_extend_penalty; a.prm.gap_ext = (int)ctx->params.gap_extend_penalty;
-    a.n = n; a.RL = RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u;
-    a.data = (const uint8_t *)dd.p; a.quals = (const uint8_t *)dq.p; a.off = (const uint64_t *)doff.p; a.len = (const int32_t *)dlen.p;
-    a.loc = (const int64_t *)dloc.p; a.extra_before = (const int32_t *)dxb.p; a.score = (const int32_t *)dsc.p;
-    a.scratch = (uint8_t *)dscr.p; a.scratch_stride = scratch_stride; a.work_counter = ctx->d_work;
-    a.ops = (uint32_t *)dops.p; a.n_ops = (int32_t *)dno.p; a.edit_distance = (int32_t *)ded.p; a.add_front_clipping = (int32_t *)dafc.p;
-    a.extra_after = (int64_t *)dxa.p; a.tail_ins = (int32_t *)dti.p; a.stale = (int32_t *)dst.p;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    snapgpu_launch_cigar_ag(&a, blocks, (size_t)waves_per_block * per_wave, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ops, dops.p, (size_t)n * ops_stride * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_ops, dno.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(edit_distance, ded.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(add_front_clipping, dafc.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(extra_clipped_after, dxa.p, (size_t)n * 8, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(back_clipping_missed, dti.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(reference_history_dependent, dst.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return sam_side_kernel_time(ctx);
-}
-
-// The banded row loops of a batch's records ahead of the records themselves, eight reads to a wavefront (cigar_ag.h: SamfPre, cigar_k.hip:
-// k_samf_dp8): fills a.pre / a.pre_stride / a.pre_counter and launches the kernel on `s`.  `buf` keeps the per-read results alive until the
-// caller has synchronised.  SNAPGPU_SAMF_DP8=0 (measurement knob) or reads beyond 400 bp: nothing is launched and a.pre stays NULL.
-static bool samf_dp8_enabled() { static int v = -1; if (v < 0) { const char *e = getenv("SNAPGPU_SAMF_DP8"); v = e ? (atoi(e) != 0 ? 1 : 0) : 1; } return v == 1; }
-static int launch_samf_dp8(snapgpu_ctx *ctx, SamFieldsArgs &a, DevBuf &buf, hipStream_t s)
-{
-    a.pre = nullptr; a.pre_stride = 0; a.pre_counter = ctx->d_work + 2;
-    if (!samf_dp8_enabled() || !a.use_affine_gap || a.RL > 400 || a.n == 0) return SNAPGPU_OK;
-    // Best effort (a.pre == NULL is a valid mode: k_sam_fields then runs the row loops itself): not beyond the 64 KiB of LDS per workgroup that k_sam_fields is
-    // held to, not beyond a bounded pre-buffer (5 - 13 KB per read: a fraction of what is free, 12 GiB at most), and an allocation that fails is not an error.
-    const size_t stride = samf_pre_stride(a.RL);
-    const size_t lds = 4 * snapgpu_samf_dp8_lds_per_wave(a.RL);
-    if (lds > 64 * 1024) return SNAPGPU_OK;
-    const size_t want = (size_t)a.n * stride;
-    if (want > ((size_t)12 << 30)) return SNAPGPU_OK;
-    if (buf.put(nullptr, want, s) != hipSuccess) { (void)hipGetLastError(); buf.p = nullptr; return SNAPGPU_OK; }
-    a.pre = (uint8_t *)buf.p; a.pre_stride = stride;
-    uint32_t per_cu = (uint32_t)((size_t)160 * 1024 / (lds ? lds : 1)); if (per_cu > 8) per_cu = 8; if (per_cu < 1) per_cu = 1;
-    uint32_t blocks = (uint32_t)ctx->num_cus * per_cu;
-    const uint32_t need = (a.n + 31) / 32; if (blocks > need) blocks = need;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work + 2, 0, 4, s), SNAPGPU_E_LAUNCH);
-    snapgpu_launch_samf_dp8(&a, blocks, lds, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    return SNAPGPU_OK;
-}
-
-// result -> FLAG / RNAME index / POS / MAPQ / CIGAR / NM of the SAM record (sam_fields.h, cigar_k.hip)
-extern "C" int snapgpu_sam_fields_single(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
-                                         const int32_t *front_clip, const int32_t *data_len, const snapgpu_single_result *results, int use_m,
-                                         int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
-                                         int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent)
-{
-    if (!ctx || (n && (!bases || !quals || !offsets || !front_clip || !data_len || !results || !flag || !contig || !pos || !mapq || !ops || !n_ops ||
-                       !nm || !reference_history_dependent)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: ops_stride must be at least 3");
-    if (n == 0) return SNAPGPU_OK;
-    uint32_t RL = 64;
-    for (uint32_t i = 0; i < n; i++) {
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > AGC_MAX_READ_LENGTH)
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: read length out of range");
-        const int64_t U = (int64_t)(offsets[i + 1] - offsets[i]);
-        if (front_clip[i] < 0 || data_len[i] < 0 || (int64_t)front_clip[i] + data_len[i] > U)
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: clipping outside the read");
-        if (results[i].status != SNAPGPU_NotFound && (results[i].location < 0 || (uint64_t)results[i].location >= ctx->ix.n_bases))
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: location outside the genome");
-        if ((uint32_t)U > RL) RL = (uint32_t)U;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = ctx->stream;
-    const uint32_t per_wave = agc_lds_bytes(RL);
-    if ((size_t)4 * per_wave > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "snapgpu_sam_fields_single: reads too long for the LDS rows");
-    uint32_t blocks = (uint32_t)ctx->num_cus * samf_blocks_per_cu();
-    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
-    const uint64_t scratch_stride = ((2 * (uint64_t)RL + 255) & ~(uint64_t)255) + ((lvc_scratch_bytes() + 255) & ~255u) + ((agc_scratch_bytes(RL) + 255) & ~(uint64_t)255);
-    const uint64_t total = offsets[n];
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf db, dq, doff, dfc, ddl, dres, dscr, dflag, dctg, dpos, dmq, dops, dno, dnm, dst;
-    HIPCHK(ctx, db.put(bases, total, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dq.put(quals, total, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, doff.put(offsets, (size_t)(n + 1) * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dfc.put(front_clip, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, ddl.put(data_len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dres.put(results, (size_t)n * sizeof(snapgpu_single_result), s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dscr.put(nullptr, (size_t)blocks * 4 * scratch_stride, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dflag.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dctg.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpos.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dmq.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dops.put(nullptr, (size_t)n * ops_stride * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dno.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dnm.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dst.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, hipMemsetAsync(dops.p, 0, (size_t)n * ops_stride * 4, s), SNAPGPU_E_LAUNCH);
-    SamFieldsArgs a;
-    a.ix = ctx->ix;
-    a.prm.match = (int)ctx->params.match_reward; a.prm.sub = -(int)ctx->params.sub_penalty;
-    a.prm.gap_open = (int)ctx->params.gap_open_penalty + (int)ctx->params.gap_extend_penalty; a.prm.gap_ext = (int)ctx->params.gap_extend_penalty;
-    a.n = n; a.RL = RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u; a.use_affine_gap = ctx->params.use_affine_gap ? 1u : 0u;
-    a.bases = (const uint8_t *)db.p; a.quals = (const uint8_t *)dq.p; a.offsets = (const uint64_t *)doff.p;
-    a.front_clip = (const int32_t *)dfc.p; a.data_len = (const int32_t *)ddl.p; a.results = (const snapgpu_single_result *)dres.p;
-    a.scratch = (uint8_t *)dscr.p; a.scratch_stride = scratch_stride; a.work_counter = ctx->d_work;
-    a.flag = (int32_t *)dflag.p; a.contig = (int32_t *)dctg.p; a.pos = (int64_t *)dpos.p; a.mapq = (int32_t *)dmq.p;
-    a.ops = (uint32_t *)dops.p; a.n_ops = (int32_t *)dno.p; a.nm = (int32_t *)dnm.p; a.stale = (int32_t *)dst.p;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    DevBuf dpre;
-    { const int prc = launch_samf_dp8(ctx, a, dpre, s); if (prc) return prc; }
-    snapgpu_launch_sam_fields(&a, blocks, (size_t)4 * per_wave, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(flag, dflag.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(contig, dctg.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(pos, dpos.p, (size_t)n * 8, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(mapq, dmq.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ops, dops.p, (size_t)n * ops_stride * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_ops, dno.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(nm, dnm.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(reference_history_dependent, dst.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return sam_side_kernel_time(ctx);
-}
-
-// device-pointer form of snapgpu_sam_fields_single: reads, clipping and results already in HBM (e.g. right after
-// snapgpu_align_single_device), outputs left in HBM.  max_read_len sizes the per-wave LDS rows and the scratch slab.
-extern "C" int snapgpu_sam_fields_single_device(snapgpu_ctx *ctx, uint32_t n, uint32_t max_read_len, const void *d_bases, const void *d_quals,
-                                                const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_results, int use_m,
-                                                void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
-                                                void *d_n_ops, void *d_nm, void *d_reference_history_dependent, void *stream)
-{
-    if (!ctx || (n && (!d_bases || !d_quals || !d_offsets || !d_front_clip || !d_data_len || !d_results || !d_flag || !d_contig || !d_pos || !d_mapq ||
-                       !d_ops || !d_n_ops || !d_nm || !d_reference_history_dependent)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: ops_stride must be at least 3");
-    if (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: max_read_len out of range");
-    if (n == 0) return SNAPGPU_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const uint32_t RL = max_read_len < 64 ? 64 : max_read_len;
-    const uint32_t per_wave = agc_lds_bytes(RL);
-    if ((size_t)4 * per_wave > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "snapgpu_sam_fields_single_device: reads too long for the LDS rows");
-    uint32_t blocks = (uint32_t)ctx->num_cus * samf_blocks_per_cu();
-    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
-    const uint64_t scratch_stride = ((2 * (uint64_t)RL + 255) & ~(uint64_t)255) + ((lvc_scratch_bytes() + 255) & ~255u) + ((agc_scratch_bytes(RL) + 255) & ~(uint64_t)255);
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf dscr;
-    HIPCHK(ctx, dscr.put(nullptr, (size_t)blocks * 4 * scratch_stride, s), SNAPGPU_E_NOMEM);
-    SamFieldsArgs a;
-    a.ix = ctx->ix;
-    a.prm.match = (int)ctx->params.match_reward; a.prm.sub = -(int)ctx->params.sub_penalty;
-    a.prm.gap_open = (int)ctx->params.gap_open_penalty + (int)ctx->params.gap_extend_penalty; a.prm.gap_ext = (int)ctx->params.gap_extend_penalty;
-    a.n = n; a.RL = RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u; a.use_affine_gap = ctx->params.use_affine_gap ? 1u : 0u;
-    a.bases = (const uint8_t *)d_bases; a.quals = (const uint8_t *)d_quals; a.offsets = (const uint64_t *)d_offsets;
-    a.front_clip = (const int32_t *)d_front_clip; a.data_len = (const int32_t *)d_data_len; a.results = (const snapgpu_single_result *)d_results;
-    a.scratch = (uint8_t *)dscr.p; a.scratch_stride = scratch_stride; a.work_counter = ctx->d_work;
-    a.flag = (int32_t *)d_flag; a.contig = (int32_t *)d_contig; a.pos = (int64_t *)d_pos; a.mapq = (int32_t *)d_mapq;
-    a.ops = (uint32_t *)d_ops; a.n_ops = (int32_t *)d_n_ops; a.nm = (int32_t *)d_nm; a.stale = (int32_t *)d_reference_history_dependent;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemsetAsync(d_ops, 0, (size_t)n * ops_stride * 4, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    DevBuf dpre;
-    { const int prc = launch_samf_dp8(ctx, a, dpre, s); if (prc) return prc; }
-    snapgpu_launch_sam_fields(&a, blocks, (size_t)4 * per_wave, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);           // (the scratch slab is freed on return; a caller-owned slab is the next step)
-    return sam_side_kernel_time(ctx);
-}
-
-static int launch_align(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals, const void *d_offsets,
-                        void *d_primary, void *d_first_alt, hipStream_t s, void *d_secondary, uint32_t sec_out_stride, void *d_n_secondary);
-
-// The single-end path of a SAM writer in one call, device-resident in between: ONE upload of the batch (the unclipped reads, Read::clip's
-// outcome, which reads the aligner is given), BaseAligner::AlignRead over the clipped reads, the SAM fields of every read from the results
-// where the align kernel left them, one download of the fields.  What snapgpu_align_single followed by snapgpu_sam_fields_single does with
-// two uploads of the reads and a round trip of the results (profiles/r04zy: the feeders' time was those copies and calls).
-extern "C" int snapgpu_align_sam_single(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
-                                        const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
-                                        snapgpu_single_result *results, snapgpu_single_result *first_alt,
-                                        int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
-                                        int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent)
-{
-    if (!ctx || (n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm ||
-                       !reference_history_dependent)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single: ops_stride must be at least 3");
-    if (ctx->secondary || ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single: a plain single-end context is needed (no snapgpu_enable_secondary / _paired)");
-    if (n == 0) return SNAPGPU_OK;
-    uint32_t RL = 64;
-    for (uint32_t i = 0; i < n; i++) {
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > AGC_MAX_READ_LENGTH)
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single: read length out of range");
-        const int64_t U = (int64_t)(offsets[i + 1] - offsets[i]);
-        if (front_clip[i] < 0 || data_len[i] < 0 || (int64_t)front_clip[i] + data_len[i] > U)
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single: clipping outside the read");
-        if (!skip[i] && (uint32_t)data_len[i] > ctx->params.max_read_len)
-            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (BaseAligner.cpp:354-358)");
-        if ((uint32_t)U > RL) RL = (uint32_t)U;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = ctx->stream;
-    const uint32_t per_wave = agc_lds_bytes(RL);
-    if ((size_t)4 * per_wave > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "snapgpu_align_sam_single: reads too long for the LDS rows");
-    uint32_t blocks = (uint32_t)ctx->num_cus * samf_blocks_per_cu();
-    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
-    const uint64_t scratch_stride = ((2 * (uint64_t)RL + 255) & ~(uint64_t)255) + ((lvc_scratch_bytes() + 255) & ~255u) + ((agc_scratch_bytes(RL) + 255) & ~(uint64_t)255);
-    const uint64_t total = offsets[n];
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf db, dq, doff, dfc, ddl, dsk, dres, dalt, dscr, dflag, dctg, dpos, dmq, dops, dno, dnm, dst;
-    HIPCHK(ctx, db.put(bases, total, s, 16), SNAPGPU_E_NOMEM);          // (16 bytes of slack behind the reads, as snapgpu_align_single's staging has)
-    HIPCHK(ctx, dq.put(quals, total, s, 16), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, doff.put(offsets, (size_t)(n + 1) * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dfc.put(front_clip, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, ddl.put(data_len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dsk.put(skip, (size_t)n, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dres.put(nullptr, (size_t)n * sizeof(snapgpu_single_result), s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dalt.put(nullptr, (size_t)n * sizeof(snapgpu_single_result), s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dscr.put(nullptr, (size_t)blocks * 4 * scratch_stride, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dflag.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dctg.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpos.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dmq.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dops.put(nullptr, (size_t)n * ops_stride * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dno.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dnm.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dst.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, hipMemsetAsync(dops.p, 0, (size_t)n * ops_stride * 4, s), SNAPGPU_E_LAUNCH);
-    ctx->clip_front = (const int32_t *)dfc.p; ctx->clip_len = (const int32_t *)ddl.p; ctx->clip_skip = (const uint8_t *)dsk.p;
-    int rc = launch_align(ctx, n, db.p, dq.p, doff.p, dres.p, first_alt ? dalt.p : nullptr, s, nullptr, 0, nullptr);
-    ctx->clip_front = ctx->clip_len = nullptr; ctx->clip_skip = nullptr;
-    if (rc) return rc;
-    rc = finish_timing(ctx);                // (the align launch's own hipEvent time, before the events are reused)
-    if (rc) return rc;
-    SamFieldsArgs a;
-    a.ix = ctx->ix;
-    a.prm.match = (int)ctx->params.match_reward; a.prm.sub = -(int)ctx->params.sub_penalty;
-    a.prm.gap_open = (int)ctx->params.gap_open_penalty + (int)ctx->params.gap_extend_penalty; a.prm.gap_ext = (int)ctx->params.gap_extend_penalty;
-    a.n = n; a.RL = RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u; a.use_affine_gap = ctx->params.use_affine_gap ? 1u : 0u;
-    a.bases = (const uint8_t *)db.p; a.quals = (const uint8_t *)dq.p; a.offsets = (const uint64_t *)doff.p;
-    a.front_clip = (const int32_t *)dfc.p; a.data_len = (const int32_t *)ddl.p; a.results = (const snapgpu_single_result *)dres.p;
-    a.scratch = (uint8_t *)dscr.p; a.scratch_stride = scratch_stride; a.work_counter = ctx->d_work;
-    a.flag = (int32_t *)dflag.p; a.contig = (int32_t *)dctg.p; a.pos = (int64_t *)dpos.p; a.mapq = (int32_t *)dmq.p;
-    a.ops = (uint32_t *)dops.p; a.n_ops = (int32_t *)dno.p; a.nm = (int32_t *)dnm.p; a.stale = (int32_t *)dst.p;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    DevBuf dpre;
-    { const int prc = launch_samf_dp8(ctx, a, dpre, s); if (prc) return prc; }
-    snapgpu_launch_sam_fields(&a, blocks, (size_t)4 * per_wave, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    if (results) HIPCHK(ctx, hipMemcpyAsync(results, dres.p, (size_t)n * sizeof(snapgpu_single_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (first_alt) HIPCHK(ctx, hipMemcpyAsync(first_alt, dalt.p, (size_t)n * sizeof(snapgpu_single_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(flag, dflag.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(contig, dctg.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(pos, dpos.p, (size_t)n * 8, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(mapq, dmq.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ops, dops.p, (size_t)n * ops_stride * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_ops, dno.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(nm, dnm.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(reference_history_dependent, dst.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return sam_side_kernel_time(ctx);
-}
-
-// paired-end writer: results -> the computed fields of both SAM records of each pair (sam_fields.h, cigar_k.hip)
-extern "C" int snapgpu_sam_fields_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
-                                         const int32_t *front_clip, const int32_t *data_len, const snapgpu_paired_result *results, int use_m,
-                                         int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
-                                         int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
-                                         int32_t *reference_history_dependent)
-{
-    if (!ctx || (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !results || !flag || !contig || !pos || !mapq || !ops ||
-                             !n_ops || !nm || !rnext || !pnext || !tlen || !first_written || !reference_history_dependent)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: ops_stride must be at least 3");
-    if (n_pairs == 0) return SNAPGPU_OK;
-    const uint32_t n = 2 * n_pairs;
-    uint32_t RL = 64;
-    for (uint32_t i = 0; i < n; i++) {
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > AGC_MAX_READ_LENGTH)
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: read length out of range");
-        const int64_t U = (int64_t)(offsets[i + 1] - offsets[i]);
-        if (front_clip[i] < 0 || data_len[i] < 0 || (int64_t)front_clip[i] + data_len[i] > U)
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: clipping outside the read");
-        const snapgpu_paired_result &r = results[i >> 1];
-        if (r.status[i & 1] != SNAPGPU_NotFound && (r.location[i & 1] < 0 || (uint64_t)r.location[i & 1] >= ctx->ix.n_bases))
-            return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: location outside the genome");
-        if ((uint32_t)U > RL) RL = (uint32_t)U;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = ctx->stream;
-    const uint32_t per_wave = agc_lds_bytes(RL);
-    if ((size_t)4 * per_wave > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "snapgpu_sam_fields_paired: reads too long for the LDS rows");
-    uint32_t blocks = (uint32_t)ctx->num_cus * samf_blocks_per_cu();
-    const uint32_t need = (n_pairs + 3) / 4; if (blocks > need) blocks = need;
-    const uint64_t scratch_stride = ((2 * (uint64_t)RL + 255) & ~(uint64_t)255) + ((lvc_scratch_bytes() + 255) & ~255u) + ((agc_scratch_bytes(RL) + 255) & ~(uint64_t)255);
-    const uint64_t total = offsets[n];
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf db, dq, doff, dfc, ddl, dres, dscr, dflag, dctg, dpos, dmq, dops, dno, dnm, drn, dpn, dtl, dfw, dst;
-    HIPCHK(ctx, db.put(bases, total, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dq.put(quals, total, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, doff.put(offsets, (size_t)(n + 1) * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dfc.put(front_clip, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, ddl.put(data_len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dres.put(results, (size_t)n_pairs * sizeof(snapgpu_paired_result), s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dscr.put(nullptr, (size_t)blocks * 4 * scratch_stride, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dflag.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dctg.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpos.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dmq.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dops.put(nullptr, (size_t)n * ops_stride * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dno.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dnm.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, drn.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpn.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dtl.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dfw.put(nullptr, (size_t)n_pairs * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dst.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, hipMemsetAsync(dops.p, 0, (size_t)n * ops_stride * 4, s), SNAPGPU_E_LAUNCH);
-    SamFieldsPairedArgs a;
-    a.ix = ctx->ix;
-    a.prm.match = (int)ctx->params.match_reward; a.prm.sub = -(int)ctx->params.sub_penalty;
-    a.prm.gap_open = (int)ctx->params.gap_open_penalty + (int)ctx->params.gap_extend_penalty; a.prm.gap_ext = (int)ctx->params.gap_extend_penalty;
-    a.n_pairs = n_pairs; a.RL = RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u; a.use_affine_gap = ctx->params.use_affine_gap ? 1u : 0u;
-    a.bases = (const uint8_t *)db.p; a.quals = (const uint8_t *)dq.p; a.offsets = (const uint64_t *)doff.p;
-    a.front_clip = (const int32_t *)dfc.p; a.data_len = (const int32_t *)ddl.p; a.results = (const snapgpu_paired_result *)dres.p;
-    a.scratch = (uint8_t *)dscr.p; a.scratch_stride = scratch_stride; a.work_counter = ctx->d_work;
-    a.flag = (int32_t *)dflag.p; a.contig = (int32_t *)dctg.p; a.pos = (int64_t *)dpos.p; a.mapq = (int32_t *)dmq.p;
-    a.ops = (uint32_t *)dops.p; a.n_ops = (int32_t *)dno.p; a.nm = (int32_t *)dnm.p; a.rnext = (int32_t *)drn.p; a.pnext = (int64_t *)dpn.p;
-    a.tlen = (int64_t *)dtl.p; a.first_written = (int32_t *)dfw.p; a.stale = (int32_t *)dst.p;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    snapgpu_launch_sam_fields_paired(&a, blocks, (size_t)4 * per_wave, s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    struct { void *h; void *d; size_t b; } outs[] = {
-        {flag, dflag.p, (size_t)n * 4}, {contig, dctg.p, (size_t)n * 4}, {pos, dpos.p, (size_t)n * 8}, {mapq, dmq.p, (size_t)n * 4},
-        {ops, dops.p, (size_t)n * ops_stride * 4}, {n_ops, dno.p, (size_t)n * 4}, {nm, dnm.p, (size_t)n * 4}, {rnext, drn.p, (size_t)n * 4},
-        {pnext, dpn.p, (size_t)n * 8}, {tlen, dtl.p, (size_t)n * 8}, {first_written, dfw.p, (size_t)n_pairs * 4},
-        {reference_history_dependent, dst.p, (size_t)n * 4}};
-    for (auto &o : outs) HIPCHK(ctx, hipMemcpyAsync(o.h, o.d, o.b, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return sam_side_kernel_time(ctx);
-}
-
-static int affine_gap_batch(snapgpu_ctx *ctx, int dir, uint32_t n,
-                            const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,
-                            const char *patterns, const char *quals, uint64_t patterns_bytes,
-                            const uint32_t *pat_off, const int32_t *pat_len,
-                            const int32_t *w, const int32_t *score_init, const uint8_t *is_rc,
-                            const uint8_t *banded, const uint8_t *use_clip,
-                            int32_t *ag_score, int32_t *text_offset, int32_t *pattern_offset,
-                            int32_t *n_edits, double *match_probability, bool sequence, int32_t *stale_steps)
-{
-    if (!ctx || (dir != 1 && dir != -1)) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_affine_gap: bad argument");
-    if (n == 0) return SNAPGPU_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    uint32_t RL = 16;
-    for (uint32_t i = 0; i < n; i++) {
-        if (pat_len[i] < 1 || pat_len[i] > 1000) return fail(ctx, SNAPGPU_E_INVALID, "pattern length out of range");
-        if (text_len[i] < 0 || text_len[i] > pat_len[i] + 127) return fail(ctx, SNAPGPU_E_INVALID, "text length must be in [0, pattern_len + MAX_K]");
-        if (score_init[i] < 0 || score_init[i] > 16000) return fail(ctx, SNAPGPU_E_INVALID, "score_init out of range");
-        if ((uint32_t)pat_len[i] > RL) RL = (uint32_t)pat_len[i];
-    }
-    RL = (RL + 15) & ~15u;
-    hipStream_t s = ctx->stream;
-    const uint32_t waves_per_block = 1;
-    uint32_t blocks = n; uint32_t maxb = (uint32_t)ctx->num_cus * 8; if (blocks > maxb) blocks = maxb;
-    if (sequence) blocks = 1;
-    PoolScope pool_scope(&ctx->pool);
-    DevBuf dt, dto, dtl, dp, dq, dpo, dpl, dw, dsi, drc, dbd, dcl, dscratch, o1, o2, o3, o4, o5, o6;
-    HIPCHK(ctx, dt.put(texts, texts_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dto.put(text_off, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dtl.put(text_len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dp.put(patterns, patterns_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dq.put(quals, patterns_bytes, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpo.put(pat_off, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dpl.put(pat_len, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dw.put(w, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dsi.put(score_init, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, drc.put(is_rc, (size_t)n, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dbd.put(banded, (size_t)n, s), SNAPGPU_E_NOMEM);
-    std::vector<uint8_t> zeros;
-    if (!use_clip) { zeros.assign(n, 0); use_clip = zeros.data(); }
-    HIPCHK(ctx, dcl.put(use_clip, (size_t)n, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, dscratch.put(nullptr, (size_t)(sequence ? 3 : blocks * waves_per_block) * ag_scratch_bytes(RL), s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, o1.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, o2.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, o3.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, o4.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, o5.put(nullptr, (size_t)n * 8, s), SNAPGPU_E_NOMEM);
-    if (stale_steps) HIPCHK(ctx, o6.put(nullptr, (size_t)n * 4, s), SNAPGPU_E_NOMEM);
-    if (sequence) HIPCHK(ctx, hipMemsetAsync(dscratch.p, 0, ag_scratch_bytes(RL), s), SNAPGPU_E_LAUNCH);      // a newly constructed object: the array reads as zero
-    AGBatchArgs a;
-    a.dir = dir; a.n = n; a.RL = RL;
-    a.prm = AGParams{ctx->cfg.match_reward, ctx->cfg.sub_penalty, ctx->cfg.gap_open, ctx->cfg.gap_extend, ctx->cfg.five_bonus, ctx->cfg.three_bonus};
-    a.texts = (const uint8_t *)dt.p; a.text_off = (const uint32_t *)dto.p; a.text_len = (const int32_t *)dtl.p;
-    a.patterns = (const uint8_t *)dp.p; a.quals = (const uint8_t *)dq.p; a.pat_off = (const uint32_t *)dpo.p;
-    a.pat_len = (const int32_t *)dpl.p; a.w = (const int32_t *)dw.p; a.score_init = (const int32_t *)dsi.p;
-    a.is_rc = (const uint8_t *)drc.p; a.banded = (const uint8_t *)dbd.p; a.use_clip = (const uint8_t *)dcl.p;
-    a.scratch = (uint8_t *)dscratch.p;
-    a.ag_score = (int32_t *)o1.p; a.text_offset = (int32_t *)o2.p; a.pattern_offset = (int32_t *)o3.p;
-    a.n_edits = (int32_t *)o4.p; a.prob = (double *)o5.p; a.tab = ctx->d_tab; a.stale = stale_steps ? (int32_t *)o6.p : nullptr;
-    uint32_t lds = (ag_lds_bytes(RL) + 15) & ~15u;
-    // variant by the largest striped layout in this batch (chunks of 64 positions)
-    int need = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        int nv, sl, ns; int ww = w[i] > 126 ? 126 : (w[i] < 0 ? 0 : w[i]);
-        ag_dims(banded[i] != 0, pat_len[i], ww, &nv, &sl, &ns);
-        if (ns * sl > need) need = ns * sl;
-    }
-    if (getenv("SNAPGPU_AG_LDS")) need = 1 << 20;
-    if (sequence) {
-        if (need <= 192) hipLaunchKernelGGL(k_ag_sequence<3>, dim3(1), dim3(64), lds, s, a);
-        else             hipLaunchKernelGGL(k_ag_sequence<0>, dim3(1), dim3(64), lds, s, a);          // (the exact replay has these two forms)
-    } else
-    if (need <= 192)      hipLaunchKernelGGL(k_ag_batch<3>, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * lds, s, a);
-    else if (need <= 256) hipLaunchKernelGGL(k_ag_batch<4>, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * lds, s, a);
-    else if (need <= 384) hipLaunchKernelGGL(k_ag_batch<6>, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * lds, s, a);
-    else                  hipLaunchKernelGGL(k_ag_batch<0>, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * lds, s, a);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ag_score, o1.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(text_offset, o2.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(pattern_offset, o3.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_edits, o4.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(match_probability, o5.p, (size_t)n * 8, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (stale_steps) HIPCHK(ctx, hipMemcpyAsync(stale_steps, o6.p, (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return SNAPGPU_OK;
-}
-
-extern "C" int snapgpu_affine_gap(snapgpu_ctx *ctx, int dir, uint32_t n,
-                                  const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,
-                                  const char *patterns, const char *quals, uint64_t patterns_bytes,
-                                  const uint32_t *pat_off, const int32_t *pat_len,
-                                  const int32_t *w, const int32_t *score_init, const uint8_t *is_rc,
-                                  const uint8_t *banded, const uint8_t *use_clip,
-                                  int32_t *ag_score, int32_t *text_offset, int32_t *pattern_offset,
-                                  int32_t *n_edits, double *match_probability)
-{
-    return affine_gap_batch(ctx, dir, n, texts, texts_bytes, text_off, text_len, patterns, quals, patterns_bytes, pat_off, pat_len, w, score_init, is_rc,
-                            banded, use_clip, ag_score, text_offset, pattern_offset, n_edits, match_probability, false, nullptr);
-}
-
-extern "C" int snapgpu_affine_gap_sequence(snapgpu_ctx *ctx, int dir, uint32_t n,
-                                           const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,
-                                           const char *patterns, const char *quals, uint64_t patterns_bytes,
-                                           const uint32_t *pat_off, const int32_t *pat_len,
-                                           const int32_t *w, const int32_t *score_init, const uint8_t *is_rc,
-                                           const uint8_t *banded, const uint8_t *use_clip,
-                                           int32_t *ag_score, int32_t *text_offset, int32_t *pattern_offset,
-                                           int32_t *n_edits, double *match_probability, int32_t *stale_steps)
-{
-    return affine_gap_batch(ctx, dir, n, texts, texts_bytes, text_off, text_len, patterns, quals, patterns_bytes, pat_off, pat_len, w, score_init, is_rc,
-                            banded, use_clip, ag_score, text_offset, pattern_offset, n_edits, match_probability, true, stale_steps);
-}
-
-// ctx->d_flag_list holds at least n entries: the reads / pairs a launch hands to its replay passes
-static int ensure_flag_list(snapgpu_ctx *ctx, uint32_t n)
-{
-    if (ctx->flag_list_cap >= n) return SNAPGPU_OK;
-    if (ctx->d_flag_list) (void)hipFree(ctx->d_flag_list);
-    ctx->d_flag_list = nullptr; ctx->flag_list_cap = 0;
-    const size_t cap = (size_t)n + n / 4 + 1024;
-    HIPCHK(ctx, hipMalloc((void **)&ctx->d_flag_list, cap * 4), SNAPGPU_E_NOMEM);
-    ctx->flag_list_cap = cap;
-    return SNAPGPU_OK;
-}
-
-// heavy-first dequeue order of a batch (order.h): ctx->d_order[0 .. n_units) is ready on stream s when this returns
-static int launch_unit_order(snapgpu_ctx *ctx, const void *d_bases, const void *d_offsets, uint32_t n_units, uint32_t max_hits, hipStream_t s)
-{
-    if (ctx->order_cap < n_units) {
-        if (ctx->d_order) (void)hipFree(ctx->d_order);
-        if (ctx->d_wbucket) (void)hipFree(ctx->d_wbucket);
-        ctx->d_order = ctx->d_wbucket = nullptr; ctx->order_cap = 0;
-        size_t cap = (size_t)n_units + n_units / 4 + 1024;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_order, cap * 4), SNAPGPU_E_NOMEM);
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_wbucket, cap * 4), SNAPGPU_E_NOMEM);
-        ctx->order_cap = cap;
-    }
-    if (!ctx->d_whist) HIPCHK(ctx, hipMalloc((void **)&ctx->d_whist, 64 * 4), SNAPGPU_E_NOMEM);
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_whist, 0, 34 * sizeof(uint32_t), s), SNAPGPU_E_LAUNCH);
-    hipLaunchKernelGGL(k_unit_weights<0>, dim3((unsigned)ctx->num_cus * 8), dim3(256), 0, s, ctx->ix, (const uint8_t *)d_bases, (const uint64_t *)d_offsets,
-                       n_units, max_hits, ctx->d_wbucket, ctx->d_whist);
-    hipLaunchKernelGGL(k_unit_weight_prefix<0>, dim3(1), dim3(64), 0, s, ctx->d_whist);
-    hipLaunchKernelGGL(k_unit_weight_scatter<0>, dim3((n_units + 255) / 256), dim3(256), 0, s, (const uint32_t *)ctx->d_wbucket, n_units, ctx->d_whist, ctx->d_order);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    return SNAPGPU_OK;
-}
-
-static int launch_align(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals, const void *d_offsets,
-                        void *d_primary, void *d_first_alt, hipStream_t s,
-                        void *d_secondary = nullptr, uint32_t sec_out_stride = 0, void *d_n_secondary = nullptr)
-{
-    AlignArgs a;
-    a.ix = ctx->ix; a.cfg = ctx->cfg; a.tab = ctx->d_tab; a.scratch = ctx->d_scratch;
-    a.bases = (const uint8_t *)d_bases; a.quals = (const uint8_t *)d_quals; a.offsets = (const uint64_t *)d_offsets;
-    a.n_reads = n; a.primary = (snapgpu_single_result *)d_primary; a.first_alt = (snapgpu_single_result *)d_first_alt;
-    a.cfg.stop_on_first_hit = ctx->stop_on_first_hit; a.cfg.explore_popular_seeds = ctx->explore_popular_seeds;
-    a.work_counter = ctx->d_work; a.counters = ctx->d_counters;
-    a.sec_cfg = SecCfg{-1, -1, 0, 0}; a.sec_scratch = nullptr; a.sec_stride_bytes = 0; a.secondary = nullptr; a.sec_out_stride = 0; a.n_secondary = nullptr;
-    a.flag_list = nullptr; a.flag_count = nullptr; a.remap = nullptr; a.n_remap = nullptr; a.persist = nullptr; a.persist_stride = 0;
-    a.is_replay = 0; a.order = nullptr; a.dbg = nullptr; a.dbg_slots = 0;
-    a.se_slots = nullptr; a.se_n_slots = 0; a.se_spec = nullptr; a.se_spec_cap = 0; a.se_ctl = nullptr; a.se_eager = 0; a.se_keep = 1;
-    a.front_clip = ctx->clip_front; a.data_len = ctx->clip_len; a.skip = ctx->clip_skip;
-    const bool use_help = ctx->single_help && ctx->d_se_slots && !d_n_secondary &&
-                          (ctx->single_help_forced == 1 || (ctx->feeders && ctx->feeders->load() <= 1));
-    if (use_help) {                                                       // (fresh protocol state for the launch that is about to start)
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_se_slots, 0, SE_HELP_SLOTS * sizeof(SEHelpSlot), s), SNAPGPU_E_LAUNCH);
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_se_ctl, 0, 256, s), SNAPGPU_E_LAUNCH);
-        a.se_slots = ctx->d_se_slots; a.se_n_slots = SE_HELP_SLOTS; a.se_spec = ctx->d_se_spec; a.se_spec_cap = ctx->se_spec_cap;
-        a.se_ctl = ctx->d_se_ctl; a.se_eager = ctx->single_help_eager ? 1u : 0u; a.se_keep = ctx->single_help_keep;
-    }
-    if (ctx->phase_timers) {
-        const size_t words = 64 + 3 * (size_t)ctx->n_wave_slots;
-        if (!ctx->d_dbg) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dbg, words * 8), SNAPGPU_E_NOMEM);
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_dbg, 0, words * 8, s), SNAPGPU_E_LAUNCH);
-        a.dbg = ctx->d_dbg; a.dbg_slots = ctx->n_wave_slots;
-    }
-    const bool always_exact = ctx->always_exact && ctx->d_exact_persist != nullptr && !use_help;
-    const bool exact = !always_exact && ctx->d_exact_persist != nullptr;
-    if (exact) {
-        if (const int frc = ensure_flag_list(ctx, n)) return frc;
-        a.flag_list = ctx->d_flag_list; a.flag_count = ctx->d_work + 4;
-    }
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 32, s), SNAPGPU_E_LAUNCH);
-    uint32_t blocks = ctx->n_wave_slots / 4;
-    uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    const bool heavy_first = ctx->single_heavy_first == 1 || (ctx->single_heavy_first < 0 && ctx->feeders && ctx->feeders->load() <= 1);
-    if (heavy_first && n > ctx->n_wave_slots) {                 // (inside the timed region: it is part of the pass)
-        const int orc = launch_unit_order(ctx, d_bases, d_offsets, n, ctx->cfg.max_hits, s);
-        if (orc) return orc;
-        a.order = ctx->d_order;
-    }
-    if (d_n_secondary) {
-        if (!ctx->d_sec_scratch) HIPCHK(ctx, hipMalloc((void **)&ctx->d_sec_scratch, ctx->sec_stride_bytes * ctx->n_wave_slots), SNAPGPU_E_NOMEM);
-        a.sec_cfg = ctx->sec_cfg; a.sec_scratch = ctx->d_sec_scratch; a.sec_stride_bytes = ctx->sec_stride_bytes;
-        a.secondary = (snapgpu_single_result *)d_secondary; a.sec_out_stride = sec_out_stride; a.n_secondary = (uint32_t *)d_n_secondary;
-    }
-    // (the instantiations that carry the plane Landau-Vishkin: plain launches of a context created under SNAPGPU_LV_PLANES=1)
-    const bool planes_k = ctx->ix.planes != nullptr && !d_n_secondary && !ctx->phase_timers;
-    if (always_exact) {                 // one pass, exact by construction
-        a.persist = ctx->d_exact_persist; a.persist_stride = ctx->exact_persist_stride;
-        if (ctx->phase_timers && !d_n_secondary) snapgpu_launch_single_exact_3_timed(&a, blocks, 4 * ctx->cfg.lds_per_wave, s);
-        else if (planes_k) snapgpu_launch_single_exact_planes_3(&a, blocks, 4 * ctx->cfg.lds_per_wave, s);
-        else snapgpu_launch_single_exact_3(&a, d_n_secondary ? 1 : 0, blocks, 4 * ctx->cfg.lds_per_wave, s);
-    } else if (planes_k) {
-        switch (ctx->ag_variant) {
-        case 3:  snapgpu_launch_single_planes_3(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
-        case 4:  snapgpu_launch_single_planes_4(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
-        case 6:  snapgpu_launch_single_planes_6(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
-        default: snapgpu_launch_single_planes_0(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
-        }
-    } else if (d_n_secondary) {
-        switch (ctx->ag_variant) {
-        case 3:  snapgpu_launch_single_sec_3(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
-        case 4:  snapgpu_launch_single_sec_4(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
-        case 6:  snapgpu_launch_single_sec_6(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
-        default: snapgpu_launch_single_sec_0(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
-        }
-    } else
-    switch (ctx->ag_variant) {
-    case 3:  if (ctx->phase_timers) snapgpu_launch_single_3_timed(&a, blocks, 4 * ctx->cfg.lds_per_wave, s);
-             else hipLaunchKernelGGL((k_align_single<3, false>), dim3(blocks), dim3(256), 4 * ctx->cfg.lds_per_wave, s, a);
-             break;
-    case 4:  hipLaunchKernelGGL((k_align_single<4, false>), dim3(blocks), dim3(256), 4 * ctx->cfg.lds_per_wave, s, a); break;
-    case 6:  hipLaunchKernelGGL((k_align_single<6, false>), dim3(blocks), dim3(256), 4 * ctx->cfg.lds_per_wave, s, a); break;
-    default: hipLaunchKernelGGL((k_align_single<0, false>), dim3(blocks), dim3(256), 4 * ctx->cfg.lds_per_wave, s, a); break;
-    }
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    if (exact) {        // redo the flagged reads (usually none: the launch then ends at once) as a newly constructed reference aligner would
-        AlignArgs x = a;
-        x.flag_list = nullptr; x.flag_count = nullptr; x.remap = ctx->d_flag_list; x.n_remap = ctx->d_work + 4; x.work_counter = ctx->d_work + 3;
-        x.is_replay = 1; x.order = nullptr; x.se_slots = nullptr; x.se_ctl = nullptr;
-        x.persist = ctx->d_exact_persist; x.persist_stride = ctx->exact_persist_stride;
-        if (planes_k) { if (ctx->ag_variant == 3) snapgpu_launch_single_exact_planes_3(&x, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
-                        else snapgpu_launch_single_exact_planes_0(&x, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s); }
-        else if (ctx->ag_variant == 3) snapgpu_launch_single_exact_3(&x, d_n_secondary ? 1 : 0, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
-        else if (ctx->ag_variant == 4) snapgpu_launch_single_exact_4(&x, d_n_secondary ? 1 : 0, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
-        else if (ctx->ag_variant == 6) snapgpu_launch_single_exact_6(&x, d_n_secondary ? 1 : 0, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
-        else snapgpu_launch_single_exact_0(&x, d_n_secondary ? 1 : 0, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
-        HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
-    return SNAPGPU_OK;
-}
-
-static int finish_timing(snapgpu_ctx *ctx) {
-    float ms = 0;
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev1), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1), SNAPGPU_E_LAUNCH);
-    ctx->kernel_ms += ms; ctx->kernel_launches++;
-    return SNAPGPU_OK;
-}
-
-extern "C" int snapgpu_align_single_device(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals,
-                                           const void *d_offsets, void *d_primary, void *d_first_alt, void *stream)
-{
-    if (!ctx || !d_bases || !d_quals || !d_offsets || !d_primary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_single_device: null argument");
-    if (n == 0) return SNAPGPU_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    int rc = launch_align(ctx, n, d_bases, d_quals, d_offsets, d_primary, d_first_alt, s);
-    if (rc) return rc;
-    if (!stream) return finish_timing(ctx);      // own stream: synchronous, and the launch is timed
-    return SNAPGPU_OK;
-}
-
-extern "C" int snapgpu_align_single(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals,
-                                    const uint64_t *offsets, snapgpu_single_result *primary, snapgpu_single_result *first_alt)
-{
-    if (!ctx || !bases || !quals || !offsets || !primary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_single: null argument");
-    if (n == 0) return SNAPGPU_OK;
-    for (uint32_t i = 0; i < n; i++) {
-        if (offsets[i + 1] < offsets[i]) return fail(ctx, SNAPGPU_E_INVALID, "offsets must be non-decreasing");
-        if (offsets[i + 1] - offsets[i] > ctx->params.max_read_len)
-            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (BaseAligner.cpp:354-358)");
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    size_t nb = (size_t)offsets[n];
-    int rc;
-    if ((rc = ensure_stage(ctx, 0, nb + 16)) || (rc = ensure_stage(ctx, 1, nb + 16)) || (rc = ensure_stage(ctx, 2, ((size_t)n + 1) * 8)) ||
-        (rc = ensure_stage(ctx, 3, (size_t)n * sizeof(snapgpu_single_result))) || (rc = ensure_stage(ctx, 4, (size_t)n * sizeof(snapgpu_single_result)))) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[0], bases, nb, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[1], quals, nb, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[2], offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    rc = launch_align(ctx, n, ctx->d_stage[0], ctx->d_stage[1], ctx->d_stage[2], ctx->d_stage[3], first_alt ? ctx->d_stage[4] : nullptr, s);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(primary, ctx->d_stage[3], (size_t)n * sizeof(snapgpu_single_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (first_alt) HIPCHK(ctx, hipMemcpyAsync(first_alt, ctx->d_stage[4], (size_t)n * sizeof(snapgpu_single_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    return finish_timing(ctx);
-}
-
 // =====================================================================================
-// secondary results (-om / -omax / -mpc)
-// =====================================================================================
-
-static int setup_paired_secondary(snapgpu_ctx *ctx);
-
-extern "C" int snapgpu_enable_secondary(snapgpu_ctx *ctx, const snapgpu_secondary_params *sp)
-{
-    if (!ctx || !sp) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_secondary: null argument");
-    if (sp->max_edit_distance < 0) return fail(ctx, SNAPGPU_E_INVALID, "-om must be >= 0 (AlignerOptions.cpp:604)");
-    if (sp->max_edit_distance > (int)ctx->params.extra_search_depth)
-        return fail(ctx, SNAPGPU_E_INVALID, "the max edit distance for secondary alignments (-om) cannot be bigger than the extra search depth (-D) (AlignerContext.cpp:784)");
-    if (sp->max_results <= 0) return fail(ctx, SNAPGPU_E_INVALID, "-omax must be strictly positive (AlignerOptions.cpp:621)");
-    if (sp->max_per_contig == 0 || sp->max_per_contig < -1) return fail(ctx, SNAPGPU_E_INVALID, "-mpc must be strictly positive, or -1 for no limit (AlignerOptions.cpp:650)");
-    if (sp->adjust_alignments && ctx->paired)
-        return fail(ctx, SNAPGPU_E_UNSUPPORTED, "-ae (AlignmentAdjuster before the -om filter) is implemented for BaseAligner::AlignRead (BaseAligner.cpp:2444-2463), not for the paired-end aligners (IntersectingPairedEndAligner.cpp:1298-1320)");
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    // updateBestScore appends at most one entry per ScoreSet per scored candidate, and a read scores at most one candidate per
-    // seed hit it applied: maxSeedsToUse * maxHits hits, two score sets (BaseAligner.cpp:451, 627, 1445-1468).
-    uint64_t seeds = ctx->params.num_seeds ? ctx->params.num_seeds
-                   : (uint64_t)(2 * ctx->params.seed_coverage * ctx->params.max_read_len / ctx->ix.seed_len) + 1;
-    // (the seed loop tests nSeedsApplied[F] + nSeedsApplied[RC] < maxSeedsToUse and one pass can apply both directions: seeds + 1)
-    uint64_t cap = 2 * (seeds + 1) * ctx->params.max_hits + 2;
-    if (cap > (1u << 20)) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "2 * seeds * max_hits > 2^20 secondary candidates per read is not supported");
-    uint64_t stride = cap * sizeof(snapgpu_single_result) + cap * 3 * 4;
-    stride = (stride + 255) & ~(uint64_t)255;
-    const uint64_t adj_off = stride;
-    if (sp->adjust_alignments) stride += (adjust_scratch_bytes(ctx->cfg.RL) + 255) & ~(uint64_t)255;     // adjust.h: the adjuster's Landau-Vishkin table, op list, staged read and window
-    if (ctx->d_sec_scratch) { (void)hipFree(ctx->d_sec_scratch); ctx->d_sec_scratch = nullptr; }
-    ctx->secondary = false;
-    // (the per-wave lists of the SINGLE-END launches: ~1.5 MB x 6 144 wave slots at the defaults.  A context that has the paired-end path
-    //  enabled keeps its single-end aligner's lists in the paired slab and gets these on its first single-end launch with secondary results.)
-    if (!ctx->paired) HIPCHK(ctx, hipMalloc((void **)&ctx->d_sec_scratch, stride * ctx->n_wave_slots), SNAPGPU_E_NOMEM);
-    ctx->sec_cfg = SecCfg{sp->max_edit_distance, sp->max_per_contig, sp->max_results, (uint32_t)cap, sp->adjust_alignments ? 1u : 0u, adj_off};
-    ctx->sec_stride_bytes = stride;
-    ctx->secondary = true;
-    return setup_paired_secondary(ctx);       // (if the paired-end path is enabled too)
-}
-
-extern "C" int snapgpu_align_single_secondary_device(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals,
-                                                     const void *d_offsets, void *d_primary, void *d_first_alt,
-                                                     void *d_secondary, uint32_t secondary_stride, void *d_n_secondary, void *stream)
-{
-    if (!ctx || !d_bases || !d_quals || !d_offsets || !d_primary || !d_n_secondary || (secondary_stride && !d_secondary))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_single_secondary_device: null argument");
-    if (!ctx->secondary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_secondary has not been called on this context");
-    if (n == 0) return SNAPGPU_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    int rc = launch_align(ctx, n, d_bases, d_quals, d_offsets, d_primary, d_first_alt, s, d_secondary, secondary_stride, d_n_secondary);
-    if (rc) return rc;
-    if (!stream) return finish_timing(ctx);
-    return SNAPGPU_OK;
-}
-
-static int ensure_sec_stage(snapgpu_ctx *ctx, int which, size_t bytes) {
-    if (ctx->sec_stage_cap[which] >= bytes) return 0;
-    if (ctx->d_sec_stage[which]) (void)hipFree(ctx->d_sec_stage[which]);
-    ctx->d_sec_stage[which] = nullptr; ctx->sec_stage_cap[which] = 0;
-    size_t cap = bytes + bytes / 4 + 4096;
-    HIPCHK(ctx, hipMalloc(&ctx->d_sec_stage[which], cap), SNAPGPU_E_NOMEM);
-    ctx->sec_stage_cap[which] = cap;
-    return 0;
-}
-
-extern "C" int snapgpu_align_single_secondary(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals,
-                                              const uint64_t *offsets, snapgpu_single_result *primary, snapgpu_single_result *first_alt,
-                                              snapgpu_single_result *secondary, uint32_t secondary_stride, uint32_t *n_secondary)
-{
-    if (!ctx || !bases || !quals || !offsets || !primary || !n_secondary || (secondary_stride && !secondary))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_single_secondary: null argument");
-    if (!ctx->secondary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_secondary has not been called on this context");
-    if (n == 0) return SNAPGPU_OK;
-    for (uint32_t i = 0; i < n; i++) {
-        if (offsets[i + 1] < offsets[i]) return fail(ctx, SNAPGPU_E_INVALID, "offsets must be non-decreasing");
-        if (offsets[i + 1] - offsets[i] > ctx->params.max_read_len)
-            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (BaseAligner.cpp:354-358)");
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    size_t nb = (size_t)offsets[n];
-    const size_t sec_bytes = (size_t)n * secondary_stride * sizeof(snapgpu_single_result);
-    int rc;
-    if ((rc = ensure_stage(ctx, 0, nb + 16)) || (rc = ensure_stage(ctx, 1, nb + 16)) || (rc = ensure_stage(ctx, 2, ((size_t)n + 1) * 8)) ||
-        (rc = ensure_stage(ctx, 3, (size_t)n * sizeof(snapgpu_single_result))) || (rc = ensure_stage(ctx, 4, (size_t)n * sizeof(snapgpu_single_result))) ||
-        (rc = ensure_sec_stage(ctx, 0, sec_bytes + 16)) || (rc = ensure_sec_stage(ctx, 1, (size_t)n * 4))) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[0], bases, nb, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[1], quals, nb, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[2], offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    if (sec_bytes) HIPCHK(ctx, hipMemsetAsync(ctx->d_sec_stage[0], 0, sec_bytes, s), SNAPGPU_E_LAUNCH);
-    rc = launch_align(ctx, n, ctx->d_stage[0], ctx->d_stage[1], ctx->d_stage[2], ctx->d_stage[3], first_alt ? ctx->d_stage[4] : nullptr, s,
-                      ctx->d_sec_stage[0], secondary_stride, ctx->d_sec_stage[1]);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(primary, ctx->d_stage[3], (size_t)n * sizeof(snapgpu_single_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (first_alt) HIPCHK(ctx, hipMemcpyAsync(first_alt, ctx->d_stage[4], (size_t)n * sizeof(snapgpu_single_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (sec_bytes) HIPCHK(ctx, hipMemcpyAsync(secondary, ctx->d_sec_stage[0], sec_bytes, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_secondary, ctx->d_sec_stage[1], (size_t)n * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    if ((rc = finish_timing(ctx))) return rc;
-    bool truncated = false;
-    for (uint32_t i = 0; i < n; i++) {
-        if (n_secondary[i] == 0xFFFFFFFFu) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "a read produced more secondary candidates than 2 * (seeds + 1) * max_hits");
-        if (n_secondary[i] > secondary_stride) truncated = true;
-    }
-    return truncated ? SNAPGPU_W_SECONDARY_TRUNCATED : SNAPGPU_OK;
-}
-
-// =====================================================================================
-// paired end
+// secondary results (-om / -omax / -mpc) and the paired-end path: what a context is set up with
 // =====================================================================================
 
 extern "C" void snapgpu_default_paired_params(snapgpu_paired_params *pp) {       // PairedAligner.cpp:55-57, 227-242; AlignerOptions.cpp:103-110
@@ -2398,6 +1319,39 @@ static int setup_paired_secondary(snapgpu_ctx *ctx)
     big.scratch = ctx->d_pscratch_sec_big;
     ctx->paired_sec = true;
     return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_enable_secondary(snapgpu_ctx *ctx, const snapgpu_secondary_params *sp)
+{
+    if (!ctx || !sp) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_secondary: null argument");
+    if (sp->max_edit_distance < 0) return fail(ctx, SNAPGPU_E_INVALID, "-om must be >= 0 (AlignerOptions.cpp:604)");
+    if (sp->max_edit_distance > (int)ctx->params.extra_search_depth)
+        return fail(ctx, SNAPGPU_E_INVALID, "the max edit distance for secondary alignments (-om) cannot be bigger than the extra search depth (-D) (AlignerContext.cpp:784)");
+    if (sp->max_results <= 0) return fail(ctx, SNAPGPU_E_INVALID, "-omax must be strictly positive (AlignerOptions.cpp:621)");
+    if (sp->max_per_contig == 0 || sp->max_per_contig < -1) return fail(ctx, SNAPGPU_E_INVALID, "-mpc must be strictly positive, or -1 for no limit (AlignerOptions.cpp:650)");
+    if (sp->adjust_alignments && ctx->paired)
+        return fail(ctx, SNAPGPU_E_UNSUPPORTED, "-ae (AlignmentAdjuster before the -om filter) is implemented for BaseAligner::AlignRead (BaseAligner.cpp:2444-2463), not for the paired-end aligners (IntersectingPairedEndAligner.cpp:1298-1320)");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    // updateBestScore appends at most one entry per ScoreSet per scored candidate, and a read scores at most one candidate per
+    // seed hit it applied: maxSeedsToUse * maxHits hits, two score sets (BaseAligner.cpp:451, 627, 1445-1468).
+    uint64_t seeds = ctx->params.num_seeds ? ctx->params.num_seeds
+                   : (uint64_t)(2 * ctx->params.seed_coverage * ctx->params.max_read_len / ctx->ix.seed_len) + 1;
+    // (the seed loop tests nSeedsApplied[F] + nSeedsApplied[RC] < maxSeedsToUse and one pass can apply both directions: seeds + 1)
+    uint64_t cap = 2 * (seeds + 1) * ctx->params.max_hits + 2;
+    if (cap > (1u << 20)) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "2 * seeds * max_hits > 2^20 secondary candidates per read is not supported");
+    uint64_t stride = cap * sizeof(snapgpu_single_result) + cap * 3 * 4;
+    stride = (stride + 255) & ~(uint64_t)255;
+    const uint64_t adj_off = stride;
+    if (sp->adjust_alignments) stride += (adjust_scratch_bytes(ctx->cfg.RL) + 255) & ~(uint64_t)255;     // adjust.h: the adjuster's Landau-Vishkin table, op list, staged read and window
+    if (ctx->d_sec_scratch) { (void)hipFree(ctx->d_sec_scratch); ctx->d_sec_scratch = nullptr; }
+    ctx->secondary = false;
+    // (the per-wave lists of the SINGLE-END launches: ~1.5 MB x 6 144 wave slots at the defaults.  A context that has the paired-end path
+    //  enabled keeps its single-end aligner's lists in the paired slab and gets these on its first single-end launch with secondary results.)
+    if (!ctx->paired) HIPCHK(ctx, hipMalloc((void **)&ctx->d_sec_scratch, stride * ctx->n_wave_slots), SNAPGPU_E_NOMEM);
+    ctx->sec_cfg = SecCfg{sp->max_edit_distance, sp->max_per_contig, sp->max_results, (uint32_t)cap, sp->adjust_alignments ? 1u : 0u, adj_off};
+    ctx->sec_stride_bytes = stride;
+    ctx->secondary = true;
+    return setup_paired_secondary(ctx);       // (if the paired-end path is enabled too)
 }
 
 extern "C" int snapgpu_enable_paired(snapgpu_ctx *ctx, const snapgpu_paired_params *pp)
@@ -2544,6 +1498,297 @@ extern "C" int snapgpu_enable_paired(snapgpu_ctx *ctx, const snapgpu_paired_para
     }
     ctx->paired = true;
     return setup_paired_secondary(ctx);
+}
+
+// =====================================================================================
+// staging of the host-pointer entry points
+// =====================================================================================
+
+// The device buffers of one host-pointer call, bound to the context and the stream the call runs on.  Every buffer comes from the context's
+// pool: until round 4 each call hipMalloc'ed its buffers and hipFree'd them on return -- fifteen of them in snapgpu_sam_fields_single, half
+// a gigabyte of per-wave scratch among them, and every hipFree synchronises the device: at 65 536 reads per batch snapgpu-sam spent ~200 ms
+// per batch there against ~25 ms of kernels (profiles/r04j: 0.58 M reads/s end to end).  Now a context keeps what it has allocated: a
+// buffer goes back to the pool when the Stage dies and the next call of a similar size takes it again.  (Calls on one context are serial,
+// and every entry point synchronises its stream before it returns.)
+//   in(src, bytes, slack)   acquire bytes + slack, copy bytes from the host
+//   out(dst, bytes, slack)  acquire bytes + slack, remember that download() copies bytes to dst (dst == NULL: a device-only buffer)
+//   scratch(bytes)          acquire
+//   download()              the device-to-host copy of every remembered output, in the order they were declared, then ONE stream synchronisation
+// A size is written once.  The first failure is kept in rc (the HIP error text where HIPCHK puts it: SNAPGPU_E_NOMEM for an allocation,
+// SNAPGPU_E_LAUNCH for a copy) and everything after it does nothing and answers NULL: a call site is one line per buffer and one check of rc
+// before anything is launched.
+struct Stage {
+    struct Ptr { void *p; template <class T> operator T *() const { return (T *)p; } };      // converts to whatever pointer the argument struct wants
+    snapgpu_ctx *ctx; hipStream_t s; int rc = SNAPGPU_OK;
+    Stage(snapgpu_ctx *c, hipStream_t st) : ctx(c), s(st) {}
+    ~Stage() { for (const Buf &b : bufs) ctx->pool.release(b.d); }
+    Stage(const Stage &) = delete; Stage &operator=(const Stage &) = delete;
+    // record = false: an allocation that fails is the caller's to deal with (NULL), not the call's failure
+    Ptr scratch(size_t bytes, bool record = true) {
+        if (rc) return Ptr{nullptr};
+        hipError_t e;
+        void *d = ctx->pool.acquire(bytes ? bytes : 16, &e);
+        if (!d) {
+            if (record) rc = hip_fail(ctx, "hipMalloc", e, SNAPGPU_E_NOMEM); else (void)hipGetLastError();
+            return Ptr{nullptr};
+        }
+        bufs.push_back(Buf{d, nullptr, 0});
+        return Ptr{d};
+    }
+    Ptr in(const void *src, size_t bytes, size_t slack = 0) {
+        void *d = scratch(bytes + slack);
+        if (d && src && bytes) copy(d, src, bytes, hipMemcpyHostToDevice);
+        return Ptr{rc ? nullptr : d};
+    }
+    Ptr out(void *dst, size_t bytes, size_t slack = 0) {
+        void *d = scratch(bytes + slack);
+        if (d) { bufs.back().h = dst; bufs.back().bytes = bytes; }
+        return Ptr{d};
+    }
+    Ptr opt_out(void *dst, size_t bytes) { return dst ? out(dst, bytes) : Ptr{nullptr}; }      // an output the caller may not want: no buffer then
+    Ptr inout(void *host, size_t bytes) {
+        void *d = in(host, bytes);
+        if (d) { bufs.back().h = host; bufs.back().bytes = bytes; }
+        return Ptr{d};
+    }
+    int download() {
+        for (const Buf &b : bufs) if (b.h && b.bytes) copy(b.h, b.d, b.bytes, hipMemcpyDeviceToHost);
+        if (!rc) { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) rc = hip_fail(ctx, "hipStreamSynchronize", e, SNAPGPU_E_LAUNCH); }
+        return rc;
+    }
+private:
+    struct Buf { void *d; void *h; size_t bytes; };          // h, bytes: what download() copies back (h == NULL: nothing)
+    std::vector<Buf> bufs;
+    void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+        if (rc) return;
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, s);
+        if (e != hipSuccess) rc = hip_fail(ctx, "hipMemcpyAsync", e, SNAPGPU_E_LAUNCH);
+    }
+};
+
+// the reads of a host-pointer align call into HBM (the pointers become device pointers): 16 bytes of slack behind the bases and the qualities
+static void stage_reads(Stage &st, const void *&bases, const void *&quals, const void *&offsets, size_t n_reads)
+{
+    const size_t nb = (size_t)((const uint64_t *)offsets)[n_reads];
+    bases = st.in(bases, nb, 16); quals = st.in(quals, nb, 16); offsets = st.in(offsets, (n_reads + 1) * 8);
+}
+
+// the hipEvent time of the launch(es) between ev0 and ev1, into the accumulator snapgpu_kernel_time reads
+static int finish_timing(snapgpu_ctx *ctx) {
+    float ms = 0;
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev1), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1), SNAPGPU_E_LAUNCH);
+    ctx->kernel_ms += ms; ctx->kernel_launches++;
+    return SNAPGPU_OK;
+}
+
+// offsets[0 .. n_reads] of a host-pointer align call: non-decreasing, no read longer than the context was created for (`where`: the reference's own check)
+static int check_read_offsets(snapgpu_ctx *ctx, const uint64_t *offsets, size_t n_reads, const char *where)
+{
+    for (size_t i = 0; i < n_reads; i++) {
+        if (offsets[i + 1] < offsets[i]) return fail(ctx, SNAPGPU_E_INVALID, "offsets must be non-decreasing");
+        if (offsets[i + 1] - offsets[i] > ctx->params.max_read_len)
+            return fail(ctx, SNAPGPU_E_INVALID, std::string("read longer than max_read_len given at snapgpu_create (") + where + ")");
+    }
+    return SNAPGPU_OK;
+}
+
+// What a host-pointer align call reports once its results are back: a pair (pairs != NULL) that the per-wave pools could not hold, a read whose
+// secondary candidates outgrew their list, and secondary results cut at the caller's strides.
+static int scan_results(snapgpu_ctx *ctx, uint32_t n, const snapgpu_paired_result *pairs, const uint32_t *n_secondary, uint32_t secondary_stride,
+                        const uint32_t *n_single_secondary, uint32_t single_stride)
+{
+    bool truncated = false;
+    for (uint32_t i = 0; i < n; i++) {
+        if (pairs && (pairs[i].flags & SNAPGPU_PAIR_POOL_OVERFLOW))
+            return fail(ctx, SNAPGPU_E_UNSUPPORTED, "a read pair needed more candidate entries than the per-wave pools hold (the reference would grow its buffers or ask for -mcp); its result is flagged");
+        if (!pairs && n_secondary && n_secondary[i] == 0xFFFFFFFFu) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "a read produced more secondary candidates than 2 * (seeds + 1) * max_hits");
+        if (n_secondary && n_secondary[i] > secondary_stride) truncated = true;
+        if (n_single_secondary && (uint64_t)n_single_secondary[2 * (size_t)i] + n_single_secondary[2 * (size_t)i + 1] > single_stride) truncated = true;
+    }
+    return truncated ? SNAPGPU_W_SECONDARY_TRUNCATED : SNAPGPU_OK;
+}
+
+// AffineGapVectorizedWithCigar's constructor (AffineGapVectorized.cpp:15-23): subPenalty negated, gapOpen = open + extend
+static AGCParamsPOD agc_params(const snapgpu_ctx *ctx) {
+    const snapgpu_params &p = ctx->params;
+    return AGCParamsPOD{(int)p.match_reward, -(int)p.sub_penalty, (int)p.gap_open_penalty + (int)p.gap_extend_penalty, (int)p.gap_extend_penalty};
+}
+
+// =====================================================================================
+// launchers
+// =====================================================================================
+
+// the index-probe kernel: sixteen probes per wave pass (lookup16.h) for the shape the north star uses, k_lookup_seeds for every other
+static void launch_lookup(snapgpu_ctx *ctx, uint32_t n, const void *d_seeds, void *d_n_hits, void *d_hits, uint32_t max_hits_out,
+                          unsigned long long *d_counters, hipStream_t s)
+{
+    const uint32_t maxb = (uint32_t)ctx->num_cus * 8;                                   // 32 waves per CU
+    if (ctx->ix.bucket_blob && ctx->ix.seed_len == 20 && ctx->ix.key_bytes == 4 && ((uintptr_t)d_seeds & 3) == 0 && !getenv("SNAPGPU_LOOKUP8")) {
+        uint32_t blocks = (n + 31) / 32; if (blocks > maxb) blocks = maxb;
+        // as many blocks as are resident at once (see the kernel): every wave then does an equal share of the passes from the start
+        // (per context: contexts live on different devices and are driven by different threads)
+        if (ctx->lookup_blocks_per_cu == 0) {
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_lookup_seeds20, 256, 0) != hipSuccess || nb <= 0) nb = 4;
+            if (const char *e = getenv("SNAPGPU_LOOKUP_BLOCKS_PER_CU")) { const int v = atoi(e); if (v >= 1 && v <= 8) nb = v; }
+            ctx->lookup_blocks_per_cu = nb > 8 ? 8 : nb;
+        }
+        const uint32_t fit = (uint32_t)ctx->num_cus * (uint32_t)ctx->lookup_blocks_per_cu;
+        if (blocks > fit) blocks = fit;
+        hipLaunchKernelGGL(k_lookup_seeds20, dim3(blocks), dim3(256), 0, s, ctx->ix, n, (const uint8_t *)d_seeds, (long long *)d_n_hits,
+                           (uint32_t *)d_hits, max_hits_out, d_counters);
+    } else {
+        uint32_t blocks = (n + 3) / 4; if (blocks > maxb) blocks = maxb;
+        hipLaunchKernelGGL(k_lookup_seeds, dim3(blocks), dim3(256), 0, s, ctx->ix, n, (const uint8_t *)d_seeds, (long long *)d_n_hits,
+                           (uint32_t *)d_hits, max_hits_out, d_counters);
+    }
+}
+
+// The affine-gap batch kernels (snapgpu_affine_gap / snapgpu_affine_gap_sequence), one wave per workgroup: the variant by `need`, the largest
+// striped layout in the batch (chunks of 64 positions).  sequence: the calls in order on one object (k_ag_sequence; the exact replay has these two forms).
+static void launch_ag_batch(const AGBatchArgs &a, bool sequence, int need, uint32_t blocks, uint32_t lds, hipStream_t s)
+{
+    if (sequence) {
+        if (need <= 192) hipLaunchKernelGGL(k_ag_sequence<3>, dim3(1), dim3(64), lds, s, a);
+        else             hipLaunchKernelGGL(k_ag_sequence<0>, dim3(1), dim3(64), lds, s, a);
+    } else
+    if (need <= 192)      hipLaunchKernelGGL(k_ag_batch<3>, dim3(blocks), dim3(64), lds, s, a);
+    else if (need <= 256) hipLaunchKernelGGL(k_ag_batch<4>, dim3(blocks), dim3(64), lds, s, a);
+    else if (need <= 384) hipLaunchKernelGGL(k_ag_batch<6>, dim3(blocks), dim3(64), lds, s, a);
+    else                  hipLaunchKernelGGL(k_ag_batch<0>, dim3(blocks), dim3(64), lds, s, a);
+}
+
+// ctx->d_flag_list holds at least n entries: the reads / pairs a launch hands to its replay passes
+static int ensure_flag_list(snapgpu_ctx *ctx, uint32_t n)
+{
+    if (ctx->flag_list_cap >= n) return SNAPGPU_OK;
+    if (ctx->d_flag_list) (void)hipFree(ctx->d_flag_list);
+    ctx->d_flag_list = nullptr; ctx->flag_list_cap = 0;
+    const size_t cap = (size_t)n + n / 4 + 1024;
+    HIPCHK(ctx, hipMalloc((void **)&ctx->d_flag_list, cap * 4), SNAPGPU_E_NOMEM);
+    ctx->flag_list_cap = cap;
+    return SNAPGPU_OK;
+}
+
+// heavy-first dequeue order of a batch (order.h): ctx->d_order[0 .. n_units) is ready on stream s when this returns
+static int launch_unit_order(snapgpu_ctx *ctx, const void *d_bases, const void *d_offsets, uint32_t n_units, uint32_t max_hits, hipStream_t s)
+{
+    if (ctx->order_cap < n_units) {
+        if (ctx->d_order) (void)hipFree(ctx->d_order);
+        if (ctx->d_wbucket) (void)hipFree(ctx->d_wbucket);
+        ctx->d_order = ctx->d_wbucket = nullptr; ctx->order_cap = 0;
+        size_t cap = (size_t)n_units + n_units / 4 + 1024;
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_order, cap * 4), SNAPGPU_E_NOMEM);
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_wbucket, cap * 4), SNAPGPU_E_NOMEM);
+        ctx->order_cap = cap;
+    }
+    if (!ctx->d_whist) HIPCHK(ctx, hipMalloc((void **)&ctx->d_whist, 64 * 4), SNAPGPU_E_NOMEM);
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_whist, 0, 34 * sizeof(uint32_t), s), SNAPGPU_E_LAUNCH);
+    hipLaunchKernelGGL(k_unit_weights<0>, dim3((unsigned)ctx->num_cus * 8), dim3(256), 0, s, ctx->ix, (const uint8_t *)d_bases, (const uint64_t *)d_offsets,
+                       n_units, max_hits, ctx->d_wbucket, ctx->d_whist);
+    hipLaunchKernelGGL(k_unit_weight_prefix<0>, dim3(1), dim3(64), 0, s, ctx->d_whist);
+    hipLaunchKernelGGL(k_unit_weight_scatter<0>, dim3((n_units + 255) / 256), dim3(256), 0, s, (const uint32_t *)ctx->d_wbucket, n_units, ctx->d_whist, ctx->d_order);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    return SNAPGPU_OK;
+}
+
+static int launch_align(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals, const void *d_offsets,
+                        void *d_primary, void *d_first_alt, hipStream_t s,
+                        void *d_secondary = nullptr, uint32_t sec_out_stride = 0, void *d_n_secondary = nullptr)
+{
+    AlignArgs a;
+    a.ix = ctx->ix; a.cfg = ctx->cfg; a.tab = ctx->d_tab; a.scratch = ctx->d_scratch;
+    a.bases = (const uint8_t *)d_bases; a.quals = (const uint8_t *)d_quals; a.offsets = (const uint64_t *)d_offsets;
+    a.n_reads = n; a.primary = (snapgpu_single_result *)d_primary; a.first_alt = (snapgpu_single_result *)d_first_alt;
+    a.cfg.stop_on_first_hit = ctx->stop_on_first_hit; a.cfg.explore_popular_seeds = ctx->explore_popular_seeds;
+    a.work_counter = ctx->d_work; a.counters = ctx->d_counters;
+    a.sec_cfg = SecCfg{-1, -1, 0, 0}; a.sec_scratch = nullptr; a.sec_stride_bytes = 0; a.secondary = nullptr; a.sec_out_stride = 0; a.n_secondary = nullptr;
+    a.flag_list = nullptr; a.flag_count = nullptr; a.remap = nullptr; a.n_remap = nullptr; a.persist = nullptr; a.persist_stride = 0;
+    a.is_replay = 0; a.order = nullptr; a.dbg = nullptr; a.dbg_slots = 0;
+    a.se_slots = nullptr; a.se_n_slots = 0; a.se_spec = nullptr; a.se_spec_cap = 0; a.se_ctl = nullptr; a.se_eager = 0; a.se_keep = 1;
+    a.front_clip = ctx->clip_front; a.data_len = ctx->clip_len; a.skip = ctx->clip_skip;
+    const bool use_help = ctx->single_help && ctx->d_se_slots && !d_n_secondary &&
+                          (ctx->single_help_forced == 1 || (ctx->feeders && ctx->feeders->load() <= 1));
+    if (use_help) {                                                       // (fresh protocol state for the launch that is about to start)
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_se_slots, 0, SE_HELP_SLOTS * sizeof(SEHelpSlot), s), SNAPGPU_E_LAUNCH);
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_se_ctl, 0, 256, s), SNAPGPU_E_LAUNCH);
+        a.se_slots = ctx->d_se_slots; a.se_n_slots = SE_HELP_SLOTS; a.se_spec = ctx->d_se_spec; a.se_spec_cap = ctx->se_spec_cap;
+        a.se_ctl = ctx->d_se_ctl; a.se_eager = ctx->single_help_eager ? 1u : 0u; a.se_keep = ctx->single_help_keep;
+    }
+    if (ctx->phase_timers) {
+        const size_t words = 64 + 3 * (size_t)ctx->n_wave_slots;
+        if (!ctx->d_dbg) HIPCHK(ctx, hipMalloc((void **)&ctx->d_dbg, words * 8), SNAPGPU_E_NOMEM);
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_dbg, 0, words * 8, s), SNAPGPU_E_LAUNCH);
+        a.dbg = ctx->d_dbg; a.dbg_slots = ctx->n_wave_slots;
+    }
+    const bool always_exact = ctx->always_exact && ctx->d_exact_persist != nullptr && !use_help;
+    const bool exact = !always_exact && ctx->d_exact_persist != nullptr;
+    if (exact) {
+        if (const int frc = ensure_flag_list(ctx, n)) return frc;
+        a.flag_list = ctx->d_flag_list; a.flag_count = ctx->d_work + 4;
+    }
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 32, s), SNAPGPU_E_LAUNCH);
+    uint32_t blocks = ctx->n_wave_slots / 4;
+    uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
+    const bool heavy_first = ctx->single_heavy_first == 1 || (ctx->single_heavy_first < 0 && ctx->feeders && ctx->feeders->load() <= 1);
+    if (heavy_first && n > ctx->n_wave_slots) {                 // (inside the timed region: it is part of the pass)
+        const int orc = launch_unit_order(ctx, d_bases, d_offsets, n, ctx->cfg.max_hits, s);
+        if (orc) return orc;
+        a.order = ctx->d_order;
+    }
+    if (d_n_secondary) {
+        if (!ctx->d_sec_scratch) HIPCHK(ctx, hipMalloc((void **)&ctx->d_sec_scratch, ctx->sec_stride_bytes * ctx->n_wave_slots), SNAPGPU_E_NOMEM);
+        a.sec_cfg = ctx->sec_cfg; a.sec_scratch = ctx->d_sec_scratch; a.sec_stride_bytes = ctx->sec_stride_bytes;
+        a.secondary = (snapgpu_single_result *)d_secondary; a.sec_out_stride = sec_out_stride; a.n_secondary = (uint32_t *)d_n_secondary;
+    }
+    // (the instantiations that carry the plane Landau-Vishkin: plain launches of a context created under SNAPGPU_LV_PLANES=1)
+    const bool planes_k = ctx->ix.planes != nullptr && !d_n_secondary && !ctx->phase_timers;
+    if (always_exact) {                 // one pass, exact by construction
+        a.persist = ctx->d_exact_persist; a.persist_stride = ctx->exact_persist_stride;
+        if (ctx->phase_timers && !d_n_secondary) snapgpu_launch_single_exact_3_timed(&a, blocks, 4 * ctx->cfg.lds_per_wave, s);
+        else if (planes_k) snapgpu_launch_single_exact_planes_3(&a, blocks, 4 * ctx->cfg.lds_per_wave, s);
+        else snapgpu_launch_single_exact_3(&a, d_n_secondary ? 1 : 0, blocks, 4 * ctx->cfg.lds_per_wave, s);
+    } else if (planes_k) {
+        switch (ctx->ag_variant) {
+        case 3:  snapgpu_launch_single_planes_3(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
+        case 4:  snapgpu_launch_single_planes_4(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
+        case 6:  snapgpu_launch_single_planes_6(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
+        default: snapgpu_launch_single_planes_0(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
+        }
+    } else if (d_n_secondary) {
+        switch (ctx->ag_variant) {
+        case 3:  snapgpu_launch_single_sec_3(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
+        case 4:  snapgpu_launch_single_sec_4(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
+        case 6:  snapgpu_launch_single_sec_6(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
+        default: snapgpu_launch_single_sec_0(&a, blocks, 4 * ctx->cfg.lds_per_wave, s); break;
+        }
+    } else
+    switch (ctx->ag_variant) {
+    case 3:  if (ctx->phase_timers) snapgpu_launch_single_3_timed(&a, blocks, 4 * ctx->cfg.lds_per_wave, s);
+             else hipLaunchKernelGGL((k_align_single<3, false>), dim3(blocks), dim3(256), 4 * ctx->cfg.lds_per_wave, s, a);
+             break;
+    case 4:  hipLaunchKernelGGL((k_align_single<4, false>), dim3(blocks), dim3(256), 4 * ctx->cfg.lds_per_wave, s, a); break;
+    case 6:  hipLaunchKernelGGL((k_align_single<6, false>), dim3(blocks), dim3(256), 4 * ctx->cfg.lds_per_wave, s, a); break;
+    default: hipLaunchKernelGGL((k_align_single<0, false>), dim3(blocks), dim3(256), 4 * ctx->cfg.lds_per_wave, s, a); break;
+    }
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    if (exact) {        // redo the flagged reads (usually none: the launch then ends at once) as a newly constructed reference aligner would
+        AlignArgs x = a;
+        x.flag_list = nullptr; x.flag_count = nullptr; x.remap = ctx->d_flag_list; x.n_remap = ctx->d_work + 4; x.work_counter = ctx->d_work + 3;
+        x.is_replay = 1; x.order = nullptr; x.se_slots = nullptr; x.se_ctl = nullptr;
+        x.persist = ctx->d_exact_persist; x.persist_stride = ctx->exact_persist_stride;
+        if (planes_k) { if (ctx->ag_variant == 3) snapgpu_launch_single_exact_planes_3(&x, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
+                        else snapgpu_launch_single_exact_planes_0(&x, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s); }
+        else if (ctx->ag_variant == 3) snapgpu_launch_single_exact_3(&x, d_n_secondary ? 1 : 0, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
+        else if (ctx->ag_variant == 4) snapgpu_launch_single_exact_4(&x, d_n_secondary ? 1 : 0, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
+        else if (ctx->ag_variant == 6) snapgpu_launch_single_exact_6(&x, d_n_secondary ? 1 : 0, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
+        else snapgpu_launch_single_exact_0(&x, d_n_secondary ? 1 : 0, ctx->exact_slots / 4, 4 * ctx->cfg.lds_per_wave, s);
+        HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
+    return SNAPGPU_OK;
 }
 
 struct PairedSecOut {          // device buffers of a call that wants secondary results
@@ -2695,55 +1940,632 @@ static int launch_paired(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, cons
     return SNAPGPU_OK;
 }
 
+// blocks per CU of the SAM-field kernels' persistent grids (SNAPGPU_SAMF_BLOCKS_PER_CU: measurement knob; default 8 = the kernels' launch bounds)
+static uint32_t samf_blocks_per_cu() { static int v = 0; if (!v) { const char *e = getenv("SNAPGPU_SAMF_BLOCKS_PER_CU"); v = e ? atoi(e) : 8; if (v < 1 || v > 8) v = 8; } return (uint32_t)v; }
+
+// The SAM-field kernels (sam_fields.h, cigar_k.hip) for reads of up to RL bases: dynamic LDS of a workgroup of four waves, the persistent grid
+// (n_units: reads, or pairs) and the per-wave scratch: the read and its reverse complement, the Landau-Vishkin and the affine-gap CIGAR state.
+struct SamfGeom { uint32_t RL, blocks; size_t lds; uint64_t scratch_stride; };
+static int samf_geometry(snapgpu_ctx *ctx, const char *who, uint32_t RL, uint32_t n_units, SamfGeom *g)
+{
+    g->RL = RL;
+    g->lds = (size_t)4 * agc_lds_bytes(RL);
+    if (g->lds > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, std::string(who) + ": reads too long for the LDS rows");
+    g->blocks = (uint32_t)ctx->num_cus * samf_blocks_per_cu();
+    const uint32_t need = (n_units + 3) / 4; if (g->blocks > need) g->blocks = need;
+    g->scratch_stride = ((2 * (uint64_t)RL + 255) & ~(uint64_t)255) + ((lvc_scratch_bytes() + 255) & ~255u) + ((agc_scratch_bytes(RL) + 255) & ~(uint64_t)255);
+    return SNAPGPU_OK;
+}
+
+// device pointers that SamFieldsArgs and SamFieldsPairedArgs have in common (results: snapgpu_single_result per read, or snapgpu_paired_result per pair)
+struct SamfBufs {
+    const void *bases, *quals, *offsets, *front_clip, *data_len, *results;
+    void *flag, *contig, *pos, *mapq, *ops, *n_ops, *nm, *stale;
+};
+
+// The banded row loops of a batch's records ahead of the records themselves, eight reads to a wavefront (cigar_ag.h: SamfPre, cigar_k.hip:
+// k_samf_dp8): fills a.pre / a.pre_stride / a.pre_counter and launches the kernel on the call's stream; the per-read results live in the
+// call's Stage.  SNAPGPU_SAMF_DP8=0 (measurement knob) or reads beyond 400 bp: nothing is launched and a.pre stays NULL.
+static bool samf_dp8_enabled() { static int v = -1; if (v < 0) { const char *e = getenv("SNAPGPU_SAMF_DP8"); v = e ? (atoi(e) != 0 ? 1 : 0) : 1; } return v == 1; }
+static int launch_samf_dp8(snapgpu_ctx *ctx, SamFieldsArgs &a, Stage &st)
+{
+    a.pre = nullptr; a.pre_stride = 0; a.pre_counter = ctx->d_work + 2;
+    if (!samf_dp8_enabled() || !a.use_affine_gap || a.RL > 400 || a.n == 0) return SNAPGPU_OK;
+    // Best effort (a.pre == NULL is a valid mode: k_sam_fields then runs the row loops itself): not beyond the 64 KiB of LDS per workgroup that k_sam_fields is
+    // held to, not beyond a bounded pre-buffer (5 - 13 KB per read: a fraction of what is free, 12 GiB at most), and an allocation that fails is not an error.
+    const size_t stride = samf_pre_stride(a.RL);
+    const size_t lds = 4 * snapgpu_samf_dp8_lds_per_wave(a.RL);
+    if (lds > 64 * 1024) return SNAPGPU_OK;
+    const size_t want = (size_t)a.n * stride;
+    if (want > ((size_t)12 << 30)) return SNAPGPU_OK;
+    a.pre = st.scratch(want, false);
+    if (!a.pre) return SNAPGPU_OK;
+    a.pre_stride = stride;
+    uint32_t per_cu = (uint32_t)((size_t)160 * 1024 / (lds ? lds : 1)); if (per_cu > 8) per_cu = 8; if (per_cu < 1) per_cu = 1;
+    uint32_t blocks = (uint32_t)ctx->num_cus * per_cu;
+    const uint32_t need = (a.n + 31) / 32; if (blocks > need) blocks = need;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_work + 2, 0, 4, st.s), SNAPGPU_E_LAUNCH);
+    snapgpu_launch_samf_dp8(&a, blocks, lds, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    return SNAPGPU_OK;
+}
+static int samf_kernels(snapgpu_ctx *ctx, SamFieldsArgs &a, const SamfGeom &g, Stage &st)
+{
+    if (const int rc = launch_samf_dp8(ctx, a, st)) return rc;
+    snapgpu_launch_sam_fields(&a, g.blocks, g.lds, st.s);
+    return SNAPGPU_OK;
+}
+static int samf_kernels(snapgpu_ctx *, SamFieldsPairedArgs &a, const SamfGeom &g, Stage &st)
+{
+    snapgpu_launch_sam_fields_paired(&a, g.blocks, g.lds, st.s);
+    return SNAPGPU_OK;
+}
+
+// The SAM-field launch of a call, single (A = SamFieldsArgs, a.n set) or paired (SamFieldsPairedArgs, a.n_pairs and the pair fields set), over
+// n_reads reads already in HBM: the scratch slab into the call's Stage, the fields the two argument structs share, the cleared CIGAR
+// buffer and work counter, and the kernels between ev0 and ev1.  The caller synchronises (or downloads) and calls finish_timing.
+template <class A>
+static int launch_sam_fields(snapgpu_ctx *ctx, A &a, const SamfGeom &g, const SamfBufs &b, uint32_t n_reads, uint32_t ops_stride, int use_m, Stage &st)
+{
+    a.scratch = st.scratch((size_t)g.blocks * 4 * g.scratch_stride);
+    if (st.rc) return st.rc;
+    a.ix = ctx->ix; a.prm = agc_params(ctx);
+    a.RL = g.RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u; a.use_affine_gap = ctx->params.use_affine_gap ? 1u : 0u;
+    a.bases = (const uint8_t *)b.bases; a.quals = (const uint8_t *)b.quals; a.offsets = (const uint64_t *)b.offsets;
+    a.front_clip = (const int32_t *)b.front_clip; a.data_len = (const int32_t *)b.data_len; a.results = (decltype(a.results))b.results;
+    a.scratch_stride = g.scratch_stride; a.work_counter = ctx->d_work;
+    a.flag = (int32_t *)b.flag; a.contig = (int32_t *)b.contig; a.pos = (int64_t *)b.pos; a.mapq = (int32_t *)b.mapq;
+    a.ops = (uint32_t *)b.ops; a.n_ops = (int32_t *)b.n_ops; a.nm = (int32_t *)b.nm; a.stale = (int32_t *)b.stale;
+    HIPCHK(ctx, hipMemsetAsync(b.ops, 0, (size_t)n_reads * ops_stride * 4, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
+    if (const int rc = samf_kernels(ctx, a, g, st)) return rc;
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
+    return SNAPGPU_OK;
+}
+
+// The per-read checks of the SAM-field entry points (`who`): the read's length, Read::clip's outcome inside the read, and whatever per_read(i)
+// adds (a return code other than 0 ends the call).  *RL: the longest unclipped read, 64 at least.
+template <class F>
+static int check_sam_reads(snapgpu_ctx *ctx, const char *who, uint32_t n, const uint64_t *offsets, const int32_t *front_clip, const int32_t *data_len,
+                           uint32_t *RL, F per_read)
+{
+    *RL = 64;
+    for (uint32_t i = 0; i < n; i++) {
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > AGC_MAX_READ_LENGTH)
+            return fail(ctx, SNAPGPU_E_INVALID, std::string(who) + ": read length out of range");
+        const int64_t U = (int64_t)(offsets[i + 1] - offsets[i]);
+        if (front_clip[i] < 0 || data_len[i] < 0 || (int64_t)front_clip[i] + data_len[i] > U)
+            return fail(ctx, SNAPGPU_E_INVALID, std::string(who) + ": clipping outside the read");
+        if (const int rc = per_read(i)) return rc;
+        if ((uint32_t)U > *RL) *RL = (uint32_t)U;
+    }
+    return SNAPGPU_OK;
+}
+// a result that names a location names one inside the genome
+static int check_location(snapgpu_ctx *ctx, const char *who, int32_t status, int64_t location)
+{
+    if (status != SNAPGPU_NotFound && (location < 0 || (uint64_t)location >= ctx->ix.n_bases))
+        return fail(ctx, SNAPGPU_E_INVALID, std::string(who) + ": location outside the genome");
+    return SNAPGPU_OK;
+}
+
+// =====================================================================================
+// entry points: host form = stage + what the device form launches + download
+// =====================================================================================
+
+// snapgpu_lookup_seeds (host: seeds, hit counts and hits are host arrays) and its device-pointer form.  The device form is the index-probe
+// kernel on its own, for its HBM roofline (bench.py): d_hits == NULL asks for counts only (the lists are read, not stored), the launch is
+// timed with hipEvents like the align kernels (snapgpu_kernel_time) and counted into snapgpu_counters (lookups, slots, hits, overflow lists).
+static int lookup_call(snapgpu_ctx *ctx, bool host, uint32_t n, const void *seeds, void *n_hits, void *hits, uint32_t max_hits_out, void *stream)
+{
+    if (n == 0) return SNAPGPU_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    if (host) {
+        const size_t hb = (size_t)n * 2 * max_hits_out * 4;
+        seeds = st.in(seeds, (size_t)n * ctx->ix.seed_len); n_hits = st.out(n_hits, (size_t)n * 2 * 8); hits = st.out(hits, hb);
+        if (st.rc) return st.rc;
+        HIPCHK(ctx, hipMemsetAsync(hits, 0, hb, st.s), SNAPGPU_E_LAUNCH);
+    } else HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
+    launch_lookup(ctx, n, seeds, n_hits, hits, max_hits_out, host ? nullptr : ctx->d_counters, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    if (host) return st.download();
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
+    return stream ? SNAPGPU_OK : finish_timing(ctx);
+}
+
+extern "C" int snapgpu_lookup_seeds(snapgpu_ctx *ctx, uint32_t n, const char *seeds, int64_t *n_hits,
+                                    uint32_t *hits, uint32_t max_hits_out)
+{
+    if (!ctx || !seeds || !n_hits || !hits || max_hits_out == 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_lookup_seeds: bad argument");
+    return lookup_call(ctx, true, n, seeds, n_hits, hits, max_hits_out, nullptr);
+}
+
+extern "C" int snapgpu_lookup_seeds_device(snapgpu_ctx *ctx, uint32_t n, const void *d_seeds, void *d_n_hits, void *d_hits,
+                                           uint32_t max_hits_out, void *stream)
+{
+    if (!ctx || !d_seeds || !d_n_hits || max_hits_out == 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_lookup_seeds_device: bad argument");
+    return lookup_call(ctx, false, n, d_seeds, d_n_hits, d_hits, max_hits_out, stream);
+}
+
+extern "C" int snapgpu_landau_vishkin(snapgpu_ctx *ctx, int dir, uint32_t n,
+                                      const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,
+                                      const char *patterns, const char *quals, uint64_t patterns_bytes,
+                                      const uint32_t *pat_off, const int32_t *pat_len, const int32_t *k,
+                                      int32_t *score, double *match_probability, int32_t *net_indel,
+                                      int32_t *total_indels, int32_t *text_span)
+{
+    if (!ctx || (dir != 1 && dir != -1)) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_landau_vishkin: bad argument");
+    if (n == 0) return SNAPGPU_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    uint32_t kmax = 0, pcap = 64;
+    for (uint32_t i = 0; i < n; i++) {
+        if (pat_len[i] < 0 || pat_len[i] > 1000) return fail(ctx, SNAPGPU_E_INVALID, "pattern length out of range");
+        int kk = k[i] > 126 ? 126 : k[i];
+        if (kk > (int)kmax) kmax = (uint32_t)kk;
+        if ((uint32_t)pat_len[i] > pcap) pcap = (uint32_t)pat_len[i];
+    }
+    Stage st(ctx, ctx->stream);
+    const size_t n4 = (size_t)n * 4;
+    LVBatchArgs a;
+    a.dir = dir; a.n = n; a.kmax = kmax; a.pcap = (pcap + 63) & ~63u; a.tab = ctx->d_tab;
+    a.texts = st.in(texts, texts_bytes); a.text_off = st.in(text_off, n4); a.text_len = st.in(text_len, n4);
+    a.patterns = st.in(patterns, patterns_bytes); a.quals = st.in(quals, patterns_bytes); a.pat_off = st.in(pat_off, n4);
+    a.pat_len = st.in(pat_len, n4); a.k = st.in(k, n4);
+    a.score = st.out(score, n4); a.prob = st.out(match_probability, (size_t)n * 8); a.net_indel = st.out(net_indel, n4);
+    a.total_indels = st.out(total_indels, n4); a.text_span = st.out(text_span, n4);
+    if (st.rc) return st.rc;
+    uint32_t per_wave = (lv_lds_bytes(kmax, a.pcap) + 15) & ~15u;
+    uint32_t waves_per_block = 4;
+    while (waves_per_block > 1 && (size_t)waves_per_block * per_wave > 64 * 1024) waves_per_block >>= 1;
+    if ((size_t)waves_per_block * per_wave > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "k too large for the LDS triangle");
+    uint32_t blocks = (n + waves_per_block - 1) / waves_per_block; uint32_t maxb = (uint32_t)ctx->num_cus * 8; if (blocks > maxb) blocks = maxb;
+    hipLaunchKernelGGL(k_lv_batch, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * per_wave, st.s, a);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    return st.download();
+}
+
+static int affine_gap_batch(snapgpu_ctx *ctx, int dir, uint32_t n,
+                            const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,
+                            const char *patterns, const char *quals, uint64_t patterns_bytes,
+                            const uint32_t *pat_off, const int32_t *pat_len,
+                            const int32_t *w, const int32_t *score_init, const uint8_t *is_rc,
+                            const uint8_t *banded, const uint8_t *use_clip,
+                            int32_t *ag_score, int32_t *text_offset, int32_t *pattern_offset,
+                            int32_t *n_edits, double *match_probability, bool sequence, int32_t *stale_steps)
+{
+    if (!ctx || (dir != 1 && dir != -1)) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_affine_gap: bad argument");
+    if (n == 0) return SNAPGPU_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    uint32_t RL = 16;
+    for (uint32_t i = 0; i < n; i++) {
+        if (pat_len[i] < 1 || pat_len[i] > 1000) return fail(ctx, SNAPGPU_E_INVALID, "pattern length out of range");
+        if (text_len[i] < 0 || text_len[i] > pat_len[i] + 127) return fail(ctx, SNAPGPU_E_INVALID, "text length must be in [0, pattern_len + MAX_K]");
+        if (score_init[i] < 0 || score_init[i] > 16000) return fail(ctx, SNAPGPU_E_INVALID, "score_init out of range");
+        if ((uint32_t)pat_len[i] > RL) RL = (uint32_t)pat_len[i];
+    }
+    RL = (RL + 15) & ~15u;
+    uint32_t blocks = n; uint32_t maxb = (uint32_t)ctx->num_cus * 8; if (blocks > maxb) blocks = maxb;
+    if (sequence) blocks = 1;
+    std::vector<uint8_t> zeros;
+    if (!use_clip) { zeros.assign(n, 0); use_clip = zeros.data(); }
+    Stage st(ctx, ctx->stream);
+    const size_t n4 = (size_t)n * 4;
+    AGBatchArgs a;
+    a.dir = dir; a.n = n; a.RL = RL; a.tab = ctx->d_tab;
+    a.prm = AGParams{ctx->cfg.match_reward, ctx->cfg.sub_penalty, ctx->cfg.gap_open, ctx->cfg.gap_extend, ctx->cfg.five_bonus, ctx->cfg.three_bonus};
+    a.texts = st.in(texts, texts_bytes); a.text_off = st.in(text_off, n4); a.text_len = st.in(text_len, n4);
+    a.patterns = st.in(patterns, patterns_bytes); a.quals = st.in(quals, patterns_bytes); a.pat_off = st.in(pat_off, n4);
+    a.pat_len = st.in(pat_len, n4); a.w = st.in(w, n4); a.score_init = st.in(score_init, n4);
+    a.is_rc = st.in(is_rc, n); a.banded = st.in(banded, n); a.use_clip = st.in(use_clip, n);
+    a.scratch = st.scratch((size_t)(sequence ? 3 : blocks) * ag_scratch_bytes(RL));
+    a.ag_score = st.out(ag_score, n4); a.text_offset = st.out(text_offset, n4); a.pattern_offset = st.out(pattern_offset, n4);
+    a.n_edits = st.out(n_edits, n4); a.prob = st.out(match_probability, (size_t)n * 8); a.stale = st.opt_out(stale_steps, n4);
+    if (st.rc) return st.rc;
+    if (sequence) HIPCHK(ctx, hipMemsetAsync(a.scratch, 0, ag_scratch_bytes(RL), st.s), SNAPGPU_E_LAUNCH);      // a newly constructed object: the array reads as zero
+    uint32_t lds = (ag_lds_bytes(RL) + 15) & ~15u;
+    int need = 0;                   // the largest striped layout in this batch (launch_ag_batch)
+    for (uint32_t i = 0; i < n; i++) {
+        int nv, sl, ns; int ww = w[i] > 126 ? 126 : (w[i] < 0 ? 0 : w[i]);
+        ag_dims(banded[i] != 0, pat_len[i], ww, &nv, &sl, &ns);
+        if (ns * sl > need) need = ns * sl;
+    }
+    if (getenv("SNAPGPU_AG_LDS")) need = 1 << 20;
+    launch_ag_batch(a, sequence, need, blocks, lds, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    return st.download();
+}
+
+extern "C" int snapgpu_affine_gap(snapgpu_ctx *ctx, int dir, uint32_t n,
+                                  const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,
+                                  const char *patterns, const char *quals, uint64_t patterns_bytes,
+                                  const uint32_t *pat_off, const int32_t *pat_len,
+                                  const int32_t *w, const int32_t *score_init, const uint8_t *is_rc,
+                                  const uint8_t *banded, const uint8_t *use_clip,
+                                  int32_t *ag_score, int32_t *text_offset, int32_t *pattern_offset,
+                                  int32_t *n_edits, double *match_probability)
+{
+    return affine_gap_batch(ctx, dir, n, texts, texts_bytes, text_off, text_len, patterns, quals, patterns_bytes, pat_off, pat_len, w, score_init, is_rc,
+                            banded, use_clip, ag_score, text_offset, pattern_offset, n_edits, match_probability, false, nullptr);
+}
+
+extern "C" int snapgpu_affine_gap_sequence(snapgpu_ctx *ctx, int dir, uint32_t n,
+                                           const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,
+                                           const char *patterns, const char *quals, uint64_t patterns_bytes,
+                                           const uint32_t *pat_off, const int32_t *pat_len,
+                                           const int32_t *w, const int32_t *score_init, const uint8_t *is_rc,
+                                           const uint8_t *banded, const uint8_t *use_clip,
+                                           int32_t *ag_score, int32_t *text_offset, int32_t *pattern_offset,
+                                           int32_t *n_edits, double *match_probability, int32_t *stale_steps)
+{
+    return affine_gap_batch(ctx, dir, n, texts, texts_bytes, text_off, text_len, patterns, quals, patterns_bytes, pat_off, pat_len, w, score_init, is_rc,
+                            banded, use_clip, ag_score, text_offset, pattern_offset, n_edits, match_probability, true, stale_steps);
+}
+
+// the tail of the SAM-side batch calls: the work counter cleared, the launch between ev0 and ev1, the outputs back, the kernel time
+template <class L>
+static int timed_launch_and_download(snapgpu_ctx *ctx, Stage &st, L launch)
+{
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
+    launch();
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
+    if (const int rc = st.download()) return rc;
+    return finish_timing(ctx);
+}
+
+// SAMFormat::computeCigar, Landau-Vishkin variant, for a batch of written reads (cigar_lv.h, cigar_k.hip).
+extern "C" int snapgpu_compute_cigar_lv(snapgpu_ctx *ctx, uint32_t n, const char *data, uint64_t data_bytes, const uint64_t *off,
+                                        const int32_t *len, const int64_t *loc, const int32_t *extra_before, int use_m,
+                                        uint32_t *ops, uint32_t ops_stride, int32_t *n_ops, int32_t *edit_distance,
+                                        int32_t *add_front_clipping, int64_t *extra_clipped_after)
+{
+    if (!ctx || (n && (!data || !off || !len || !loc || !extra_before || !ops || !n_ops || !edit_distance || !add_front_clipping || !extra_clipped_after)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: null argument");
+    if (ops_stride == 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: ops_stride must be positive");
+    if (n == 0) return SNAPGPU_OK;
+    uint32_t RL = 64;
+    for (uint32_t i = 0; i < n; i++) {
+        if (len[i] < 0 || len[i] > 4000) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: read length out of range");
+        if (extra_before[i] < 0 || extra_before[i] > len[i]) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: extra_before out of range");
+        if (off[i] + (uint64_t)len[i] > data_bytes) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: read outside the data buffer");
+        if (loc[i] < 0 || (uint64_t)loc[i] >= ctx->ix.n_bases) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_lv: location outside the genome");
+        if ((uint32_t)len[i] > RL) RL = (uint32_t)len[i];
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    const uint32_t per_wave = lvc_lds_bytes(RL);
+    uint32_t blocks = (uint32_t)ctx->num_cus * 4;                    // persistent grid: 16 waves per CU
+    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
+    Stage st(ctx, ctx->stream);
+    const size_t n4 = (size_t)n * 4, n8 = (size_t)n * 8, ops_bytes = (size_t)n * ops_stride * 4;
+    CigarArgs a;
+    a.ix = ctx->ix; a.n = n; a.RL = RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u; a.work_counter = ctx->d_work;
+    a.data = st.in(data, data_bytes); a.off = st.in(off, n8); a.len = st.in(len, n4); a.loc = st.in(loc, n8); a.extra_before = st.in(extra_before, n4);
+    a.scratch = st.scratch((size_t)blocks * 4 * lvc_scratch_bytes());
+    a.ops = st.out(ops, ops_bytes); a.n_ops = st.out(n_ops, n4); a.edit_distance = st.out(edit_distance, n4);
+    a.add_front_clipping = st.out(add_front_clipping, n4); a.extra_after = st.out(extra_clipped_after, n8);
+    if (st.rc) return st.rc;
+    HIPCHK(ctx, hipMemsetAsync(a.ops, 0, ops_bytes, st.s), SNAPGPU_E_LAUNCH);
+    return timed_launch_and_download(ctx, st, [&] { snapgpu_launch_cigar_lv(&a, blocks, (size_t)4 * per_wave, st.s); });
+}
+
+// AlignmentAdjuster::AdjustAlignment for a batch of results (adjust.h, cigar_k.hip)
+extern "C" int snapgpu_adjust_alignments(snapgpu_ctx *ctx, uint32_t n, const char *data, uint64_t data_bytes, const uint64_t *off, const int32_t *len,
+                                         snapgpu_single_result *results)
+{
+    if (!ctx || (n && (!data || !off || !len || !results))) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: null argument");
+    if (n == 0) return SNAPGPU_OK;
+    uint32_t RL = 64;
+    for (uint32_t i = 0; i < n; i++) {
+        if (len[i] < 1 || len[i] > 4000) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: read length out of range");
+        if (off[i] + (uint64_t)len[i] > data_bytes) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: read outside the data buffer");
+        if (const int rc = check_location(ctx, "snapgpu_adjust_alignments", results[i].status, results[i].location)) return rc;
+        if (results[i].direction != 0 && results[i].direction != 1) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_adjust_alignments: direction must be 0 (forward) or 1 (reverse complement)");
+        if ((uint32_t)len[i] > RL) RL = (uint32_t)len[i];
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    uint32_t blocks = (uint32_t)ctx->num_cus * 4;
+    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
+    Stage st(ctx, ctx->stream);
+    AdjustArgs a;
+    a.ix = ctx->ix; a.n = n; a.RL = RL; a.work_counter = ctx->d_work;
+    a.scratch_stride = 2 * (uint64_t)((RL + 255) & ~255u) + ((adjust_scratch_bytes(RL) + 255) & ~(uint64_t)255);
+    a.data = st.in(data, data_bytes); a.off = st.in(off, (size_t)n * 8); a.len = st.in(len, (size_t)n * 4);
+    a.results = st.inout(results, (size_t)n * sizeof(snapgpu_single_result));
+    a.scratch = st.scratch((size_t)blocks * 4 * a.scratch_stride);
+    if (st.rc) return st.rc;
+    return timed_launch_and_download(ctx, st, [&] { snapgpu_launch_adjust_alignments(&a, blocks, st.s); });
+}
+
+// SAMFormat::computeCigar, affine-gap variant, for a batch of written reads (cigar_ag.h, cigar_k.hip).
+extern "C" int snapgpu_compute_cigar_ag(snapgpu_ctx *ctx, uint32_t n, const char *data, const char *quals, uint64_t data_bytes,
+                                        const uint64_t *off, const int32_t *len, const int64_t *loc, const int32_t *extra_before,
+                                        const int32_t *score, int use_m, uint32_t *ops, uint32_t ops_stride, int32_t *n_ops,
+                                        int32_t *edit_distance, int32_t *add_front_clipping, int64_t *extra_clipped_after,
+                                        int32_t *back_clipping_missed, int32_t *reference_history_dependent)
+{
+    if (!ctx || (n && (!data || !quals || !off || !len || !loc || !extra_before || !score || !ops || !n_ops || !edit_distance ||
+                       !add_front_clipping || !extra_clipped_after || !back_clipping_missed || !reference_history_dependent)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: null argument");
+    if (ops_stride == 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: ops_stride must be positive");
+    if (n == 0) return SNAPGPU_OK;
+    uint32_t RL = 64;
+    for (uint32_t i = 0; i < n; i++) {
+        if (len[i] < 0 || len[i] > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: read length out of range");
+        if (extra_before[i] < 0 || extra_before[i] > len[i]) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: extra_before out of range");
+        if (off[i] + (uint64_t)len[i] > data_bytes) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: read outside the data buffer");
+        if (loc[i] < 0 || (uint64_t)loc[i] >= ctx->ix.n_bases) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: location outside the genome");
+        if (score[i] < 0) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_compute_cigar_ag: negative score");
+        if ((uint32_t)len[i] > RL) RL = (uint32_t)len[i];
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    const size_t lds = (size_t)4 * agc_lds_bytes(RL);
+    if (lds > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "snapgpu_compute_cigar_ag: reads too long for the LDS rows");
+    uint32_t blocks = (uint32_t)ctx->num_cus * 4;
+    const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
+    Stage st(ctx, ctx->stream);
+    const size_t n4 = (size_t)n * 4, n8 = (size_t)n * 8, ops_bytes = (size_t)n * ops_stride * 4;
+    CigarAGArgs a;
+    a.ix = ctx->ix; a.prm = agc_params(ctx);
+    a.n = n; a.RL = RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u; a.work_counter = ctx->d_work;
+    a.scratch_stride = (agc_scratch_bytes(RL) + 255) & ~(uint64_t)255;
+    a.data = st.in(data, data_bytes); a.quals = st.in(quals, data_bytes); a.off = st.in(off, n8); a.len = st.in(len, n4);
+    a.loc = st.in(loc, n8); a.extra_before = st.in(extra_before, n4); a.score = st.in(score, n4);
+    a.scratch = st.scratch((size_t)blocks * 4 * a.scratch_stride);
+    a.ops = st.out(ops, ops_bytes); a.n_ops = st.out(n_ops, n4); a.edit_distance = st.out(edit_distance, n4);
+    a.add_front_clipping = st.out(add_front_clipping, n4); a.extra_after = st.out(extra_clipped_after, n8);
+    a.tail_ins = st.out(back_clipping_missed, n4); a.stale = st.out(reference_history_dependent, n4);
+    if (st.rc) return st.rc;
+    HIPCHK(ctx, hipMemsetAsync(a.ops, 0, ops_bytes, st.s), SNAPGPU_E_LAUNCH);
+    return timed_launch_and_download(ctx, st, [&] { snapgpu_launch_cigar_ag(&a, blocks, lds, st.s); });
+}
+
+// result -> FLAG / RNAME index / POS / MAPQ / CIGAR / NM of the SAM record (sam_fields.h, cigar_k.hip)
+extern "C" int snapgpu_sam_fields_single(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                         const int32_t *front_clip, const int32_t *data_len, const snapgpu_single_result *results, int use_m,
+                                         int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                                         int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent)
+{
+    const char *who = "snapgpu_sam_fields_single";
+    if (!ctx || (n && (!bases || !quals || !offsets || !front_clip || !data_len || !results || !flag || !contig || !pos || !mapq || !ops || !n_ops ||
+                       !nm || !reference_history_dependent)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: null argument");
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: ops_stride must be at least 3");
+    if (n == 0) return SNAPGPU_OK;
+    SamfGeom g; uint32_t RL;
+    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL,
+                             [&](uint32_t i) { return check_location(ctx, who, results[i].status, results[i].location); });
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    if ((rc = samf_geometry(ctx, who, RL, n, &g))) return rc;
+    Stage st(ctx, ctx->stream);
+    const size_t total = offsets[n], n4 = (size_t)n * 4;
+    const SamfBufs b{st.in(bases, total), st.in(quals, total), st.in(offsets, (size_t)(n + 1) * 8), st.in(front_clip, n4), st.in(data_len, n4),
+                     st.in(results, (size_t)n * sizeof(snapgpu_single_result)),
+                     st.out(flag, n4), st.out(contig, n4), st.out(pos, (size_t)n * 8), st.out(mapq, n4), st.out(ops, n4 * ops_stride), st.out(n_ops, n4),
+                     st.out(nm, n4), st.out(reference_history_dependent, n4)};
+    if (st.rc) return st.rc;
+    SamFieldsArgs a; a.n = n;
+    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
+    return finish_timing(ctx);
+}
+
+// device-pointer form of snapgpu_sam_fields_single: reads, clipping and results already in HBM (e.g. right after
+// snapgpu_align_single_device), outputs left in HBM.  max_read_len sizes the per-wave LDS rows and the scratch slab.
+extern "C" int snapgpu_sam_fields_single_device(snapgpu_ctx *ctx, uint32_t n, uint32_t max_read_len, const void *d_bases, const void *d_quals,
+                                                const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_results, int use_m,
+                                                void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
+                                                void *d_n_ops, void *d_nm, void *d_reference_history_dependent, void *stream)
+{
+    if (!ctx || (n && (!d_bases || !d_quals || !d_offsets || !d_front_clip || !d_data_len || !d_results || !d_flag || !d_contig || !d_pos || !d_mapq ||
+                       !d_ops || !d_n_ops || !d_nm || !d_reference_history_dependent)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: null argument");
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: ops_stride must be at least 3");
+    if (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: max_read_len out of range");
+    if (n == 0) return SNAPGPU_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    SamfGeom g;
+    int rc = samf_geometry(ctx, "snapgpu_sam_fields_single_device", max_read_len < 64 ? 64 : max_read_len, n, &g);
+    if (rc) return rc;
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    const SamfBufs b{d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_results, d_flag, d_contig, d_pos, d_mapq, d_ops, d_n_ops, d_nm,
+                     d_reference_history_dependent};
+    SamFieldsArgs a; a.n = n;
+    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);           // (the scratch slab goes back to the pool on return; a caller-owned slab is the next step)
+    return finish_timing(ctx);
+}
+
+// The single-end path of a SAM writer in one call, device-resident in between: ONE upload of the batch (the unclipped reads, Read::clip's
+// outcome, which reads the aligner is given), BaseAligner::AlignRead over the clipped reads, the SAM fields of every read from the results
+// where the align kernel left them, one download of the fields.  What snapgpu_align_single followed by snapgpu_sam_fields_single does with
+// two uploads of the reads and a round trip of the results (profiles/r04zy: the feeders' time was those copies and calls).
+extern "C" int snapgpu_align_sam_single(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                        const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                        snapgpu_single_result *results, snapgpu_single_result *first_alt,
+                                        int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                                        int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent)
+{
+    const char *who = "snapgpu_align_sam_single";
+    if (!ctx || (n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm ||
+                       !reference_history_dependent)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single: null argument");
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single: ops_stride must be at least 3");
+    if (ctx->secondary || ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single: a plain single-end context is needed (no snapgpu_enable_secondary / _paired)");
+    if (n == 0) return SNAPGPU_OK;
+    SamfGeom g; uint32_t RL;
+    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
+        if (!skip[i] && (uint32_t)data_len[i] > ctx->params.max_read_len)
+            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (BaseAligner.cpp:354-358)");
+        return (int)SNAPGPU_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    if ((rc = samf_geometry(ctx, who, RL, n, &g))) return rc;
+    Stage st(ctx, ctx->stream);
+    const size_t n4 = (size_t)n * 4, rb = (size_t)n * sizeof(snapgpu_single_result);
+    const void *d_bases = bases, *d_quals = quals, *d_offsets = offsets;
+    stage_reads(st, d_bases, d_quals, d_offsets, n);
+    const void *d_front_clip = st.in(front_clip, n4), *d_data_len = st.in(data_len, n4), *d_skip = st.in(skip, n);
+    void *d_results = st.out(results, rb), *d_first_alt = st.opt_out(first_alt, rb);
+    const SamfBufs b{d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_results,
+                     st.out(flag, n4), st.out(contig, n4), st.out(pos, (size_t)n * 8), st.out(mapq, n4), st.out(ops, n4 * ops_stride), st.out(n_ops, n4),
+                     st.out(nm, n4), st.out(reference_history_dependent, n4)};
+    if (st.rc) return st.rc;
+    ctx->clip_front = (const int32_t *)d_front_clip; ctx->clip_len = (const int32_t *)d_data_len; ctx->clip_skip = (const uint8_t *)d_skip;
+    rc = launch_align(ctx, n, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s);
+    ctx->clip_front = ctx->clip_len = nullptr; ctx->clip_skip = nullptr;
+    if (rc || (rc = finish_timing(ctx))) return rc;                // (the align launch's own hipEvent time, before the events are reused)
+    SamFieldsArgs a; a.n = n;
+    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
+    return finish_timing(ctx);
+}
+
+// paired-end writer: results -> the computed fields of both SAM records of each pair (sam_fields.h, cigar_k.hip)
+extern "C" int snapgpu_sam_fields_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                         const int32_t *front_clip, const int32_t *data_len, const snapgpu_paired_result *results, int use_m,
+                                         int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                                         int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
+                                         int32_t *reference_history_dependent)
+{
+    const char *who = "snapgpu_sam_fields_paired";
+    if (!ctx || (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !results || !flag || !contig || !pos || !mapq || !ops ||
+                             !n_ops || !nm || !rnext || !pnext || !tlen || !first_written || !reference_history_dependent)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: null argument");
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: ops_stride must be at least 3");
+    if (n_pairs == 0) return SNAPGPU_OK;
+    const uint32_t n = 2 * n_pairs;
+    SamfGeom g; uint32_t RL;
+    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL,
+                             [&](uint32_t i) { return check_location(ctx, who, results[i >> 1].status[i & 1], results[i >> 1].location[i & 1]); });
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    if ((rc = samf_geometry(ctx, who, RL, n_pairs, &g))) return rc;
+    Stage st(ctx, ctx->stream);
+    const size_t total = offsets[n], n4 = (size_t)n * 4, n8 = (size_t)n * 8;
+    SamfBufs b{st.in(bases, total), st.in(quals, total), st.in(offsets, (size_t)(n + 1) * 8), st.in(front_clip, n4), st.in(data_len, n4),
+               st.in(results, (size_t)n_pairs * sizeof(snapgpu_paired_result)),
+               st.out(flag, n4), st.out(contig, n4), st.out(pos, n8), st.out(mapq, n4), st.out(ops, n4 * ops_stride), st.out(n_ops, n4), st.out(nm, n4), nullptr};
+    SamFieldsPairedArgs a;
+    a.n_pairs = n_pairs;
+    a.rnext = st.out(rnext, n4); a.pnext = st.out(pnext, n8); a.tlen = st.out(tlen, n8); a.first_written = st.out(first_written, (size_t)n_pairs * 4);
+    b.stale = st.out(reference_history_dependent, n4);          // (declared last: the outputs come back in the order of the argument list)
+    if (st.rc) return st.rc;
+    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
+    return finish_timing(ctx);
+}
+
+// BaseAligner::AlignRead for a batch, with (n_secondary != NULL: snapgpu_enable_secondary) or without secondary results.  host: every pointer
+// is a host array and the call stages, launches, downloads and reports on what came back; otherwise device pointers, and only a call on the
+// context's own stream (stream == NULL) is synchronous and timed.
+static int align_single_call(snapgpu_ctx *ctx, bool host, uint32_t n, const void *bases, const void *quals, const void *offsets, void *primary,
+                             void *first_alt, void *secondary, uint32_t secondary_stride, void *n_secondary, void *stream)
+{
+    if (n_secondary && !ctx->secondary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_secondary has not been called on this context");
+    if (n == 0) return SNAPGPU_OK;
+    int rc;
+    if (host && (rc = check_read_offsets(ctx, (const uint64_t *)offsets, n, "BaseAligner.cpp:354-358"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    const uint32_t *h_n_secondary = (const uint32_t *)n_secondary;
+    if (host) {
+        const size_t rb = (size_t)n * sizeof(snapgpu_single_result), sec_bytes = (size_t)n * secondary_stride * sizeof(snapgpu_single_result);
+        stage_reads(st, bases, quals, offsets, n);
+        primary = st.out(primary, rb); first_alt = st.opt_out(first_alt, rb);
+        if (n_secondary) { secondary = st.out(secondary, sec_bytes, 16); n_secondary = st.out(n_secondary, (size_t)n * 4); }
+        if (st.rc) return st.rc;
+        if (n_secondary && sec_bytes) HIPCHK(ctx, hipMemsetAsync(secondary, 0, sec_bytes, st.s), SNAPGPU_E_LAUNCH);
+    }
+    if ((rc = launch_align(ctx, n, bases, quals, offsets, primary, first_alt, st.s, secondary, secondary_stride, n_secondary))) return rc;
+    if (host && (rc = st.download())) return rc;
+    if (!stream && (rc = finish_timing(ctx))) return rc;
+    return host && h_n_secondary ? scan_results(ctx, n, nullptr, h_n_secondary, secondary_stride, nullptr, 0) : SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_align_single_device(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals,
+                                           const void *d_offsets, void *d_primary, void *d_first_alt, void *stream)
+{
+    if (!ctx || !d_bases || !d_quals || !d_offsets || !d_primary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_single_device: null argument");
+    return align_single_call(ctx, false, n, d_bases, d_quals, d_offsets, d_primary, d_first_alt, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int snapgpu_align_single(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals,
+                                    const uint64_t *offsets, snapgpu_single_result *primary, snapgpu_single_result *first_alt)
+{
+    if (!ctx || !bases || !quals || !offsets || !primary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_single: null argument");
+    return align_single_call(ctx, true, n, bases, quals, offsets, primary, first_alt, nullptr, 0, nullptr, nullptr);
+}
+
+extern "C" int snapgpu_align_single_secondary_device(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals,
+                                                     const void *d_offsets, void *d_primary, void *d_first_alt,
+                                                     void *d_secondary, uint32_t secondary_stride, void *d_n_secondary, void *stream)
+{
+    if (!ctx || !d_bases || !d_quals || !d_offsets || !d_primary || !d_n_secondary || (secondary_stride && !d_secondary))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_single_secondary_device: null argument");
+    return align_single_call(ctx, false, n, d_bases, d_quals, d_offsets, d_primary, d_first_alt, d_secondary, secondary_stride, d_n_secondary, stream);
+}
+
+extern "C" int snapgpu_align_single_secondary(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals,
+                                              const uint64_t *offsets, snapgpu_single_result *primary, snapgpu_single_result *first_alt,
+                                              snapgpu_single_result *secondary, uint32_t secondary_stride, uint32_t *n_secondary)
+{
+    if (!ctx || !bases || !quals || !offsets || !primary || !n_secondary || (secondary_stride && !secondary))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_single_secondary: null argument");
+    return align_single_call(ctx, true, n, bases, quals, offsets, primary, first_alt, secondary, secondary_stride, n_secondary, nullptr);
+}
+
+// ChimericPairedEndAligner::align for a batch of pairs, with (so != NULL: its pointers are host or device as the rest; both
+// snapgpu_enable_paired and snapgpu_enable_secondary) or without secondary results.  host / stream: as align_single_call.
+static int align_paired_call(snapgpu_ctx *ctx, bool host, uint32_t n_pairs, const void *bases, const void *quals, const void *offsets, void *primary,
+                             void *first_alt, const PairedSecOut *so, void *stream)
+{
+    if (so && !ctx->paired_sec) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_paired and snapgpu_enable_secondary must both have been called on this context");
+    if (!so && !ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_paired has not been called on this context");
+    if (n_pairs == 0) return SNAPGPU_OK;
+    const size_t nr = (size_t)2 * n_pairs;
+    int rc;
+    if (host && (rc = check_read_offsets(ctx, (const uint64_t *)offsets, nr, "IntersectingPairedEndAligner.cpp:361-365"))) return rc;
+    const PairedInFlight in_flight(ctx); ctx->paired_share = in_flight.share;      // (paired_grid_share: this call's launches ask for their share of the chip)
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    const snapgpu_paired_result *h_primary = (const snapgpu_paired_result *)primary;
+    PairedSecOut d_so = so ? *so : PairedSecOut{};
+    if (host) {
+        const size_t rb = (size_t)n_pairs * sizeof(snapgpu_paired_result);
+        const size_t sec_bytes = (size_t)n_pairs * d_so.stride * sizeof(snapgpu_paired_result), ssec_bytes = (size_t)n_pairs * d_so.single_stride * sizeof(snapgpu_single_result);
+        stage_reads(st, bases, quals, offsets, nr);
+        primary = st.out(primary, rb); first_alt = st.opt_out(first_alt, rb);
+        if (so) {
+            d_so.secondary = st.out(so->secondary, sec_bytes, 16); d_so.n_secondary = st.out(so->n_secondary, (size_t)n_pairs * 4);
+            d_so.single_secondary = st.out(so->single_secondary, ssec_bytes, 16); d_so.n_single_secondary = st.out(so->n_single_secondary, nr * 4);
+        }
+        if (st.rc) return st.rc;
+        if (sec_bytes) HIPCHK(ctx, hipMemsetAsync(d_so.secondary, 0, sec_bytes, st.s), SNAPGPU_E_LAUNCH);
+        if (ssec_bytes) HIPCHK(ctx, hipMemsetAsync(d_so.single_secondary, 0, ssec_bytes, st.s), SNAPGPU_E_LAUNCH);
+    }
+    if ((rc = launch_paired(ctx, n_pairs, bases, quals, offsets, primary, first_alt, st.s, so ? &d_so : nullptr))) return rc;
+    if (host && (rc = st.download())) return rc;
+    if (!stream && (rc = finish_timing(ctx))) return rc;
+    if (!host) return SNAPGPU_OK;
+    return scan_results(ctx, n_pairs, h_primary, so ? (const uint32_t *)so->n_secondary : nullptr, d_so.stride,
+                        so ? (const uint32_t *)so->n_single_secondary : nullptr, d_so.single_stride);
+}
+
 extern "C" int snapgpu_align_paired_device(snapgpu_ctx *ctx, uint32_t n_pairs, const void *d_bases, const void *d_quals,
                                            const void *d_offsets, void *d_primary, void *d_first_alt, void *stream)
 {
     if (!ctx || !d_bases || !d_quals || !d_offsets || !d_primary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_paired_device: null argument");
-    if (!ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_paired has not been called on this context");
-    if (n_pairs == 0) return SNAPGPU_OK;
-    const PairedInFlight in_flight(ctx); ctx->paired_share = in_flight.share;      // (paired_grid_share: this call's launches ask for their share of the chip)
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    int rc = launch_paired(ctx, n_pairs, d_bases, d_quals, d_offsets, d_primary, d_first_alt, s);
-    if (rc) return rc;
-    if (!stream) return finish_timing(ctx);
-    return SNAPGPU_OK;
+    return align_paired_call(ctx, false, n_pairs, d_bases, d_quals, d_offsets, d_primary, d_first_alt, nullptr, stream);
 }
 
 extern "C" int snapgpu_align_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals,
                                     const uint64_t *offsets, snapgpu_paired_result *primary, snapgpu_paired_result *first_alt)
 {
     if (!ctx || !bases || !quals || !offsets || !primary) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_paired: null argument");
-    if (!ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_paired has not been called on this context");
-    if (n_pairs == 0) return SNAPGPU_OK;
-    const size_t nr = (size_t)2 * n_pairs;
-    for (size_t i = 0; i < nr; i++) {
-        if (offsets[i + 1] < offsets[i]) return fail(ctx, SNAPGPU_E_INVALID, "offsets must be non-decreasing");
-        if (offsets[i + 1] - offsets[i] > ctx->params.max_read_len)
-            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (IntersectingPairedEndAligner.cpp:361-365)");
-    }
-    const PairedInFlight in_flight(ctx); ctx->paired_share = in_flight.share;      // (paired_grid_share: this call's launches ask for their share of the chip)
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    size_t nb = (size_t)offsets[nr];
-    int rc;
-    if ((rc = ensure_stage(ctx, 0, nb + 16)) || (rc = ensure_stage(ctx, 1, nb + 16)) || (rc = ensure_stage(ctx, 2, (nr + 1) * 8)) ||
-        (rc = ensure_stage(ctx, 3, (size_t)n_pairs * sizeof(snapgpu_paired_result))) ||
-        (rc = ensure_stage(ctx, 4, (size_t)n_pairs * sizeof(snapgpu_paired_result)))) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[0], bases, nb, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[1], quals, nb, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[2], offsets, (nr + 1) * 8, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    rc = launch_paired(ctx, n_pairs, ctx->d_stage[0], ctx->d_stage[1], ctx->d_stage[2], ctx->d_stage[3], first_alt ? ctx->d_stage[4] : nullptr, s);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(primary, ctx->d_stage[3], (size_t)n_pairs * sizeof(snapgpu_paired_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (first_alt) HIPCHK(ctx, hipMemcpyAsync(first_alt, ctx->d_stage[4], (size_t)n_pairs * sizeof(snapgpu_paired_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    rc = finish_timing(ctx);
-    if (rc) return rc;
-    for (uint32_t i = 0; i < n_pairs; i++)
-        if (primary[i].flags & SNAPGPU_PAIR_POOL_OVERFLOW)
-            return fail(ctx, SNAPGPU_E_UNSUPPORTED, "a read pair needed more candidate entries than the per-wave pools hold (the reference would grow its buffers or ask for -mcp); its result is flagged");
-    return SNAPGPU_OK;
+    return align_paired_call(ctx, true, n_pairs, bases, quals, offsets, primary, first_alt, nullptr, nullptr);
 }
 
 extern "C" int snapgpu_align_paired_secondary_device(snapgpu_ctx *ctx, uint32_t n_pairs, const void *d_bases, const void *d_quals,
@@ -2754,26 +2576,8 @@ extern "C" int snapgpu_align_paired_secondary_device(snapgpu_ctx *ctx, uint32_t 
     if (!ctx || !d_bases || !d_quals || !d_offsets || !d_primary || !d_n_secondary || !d_n_single_secondary ||
         (secondary_stride && !d_secondary) || (single_stride && !d_single_secondary))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_paired_secondary_device: null argument");
-    if (!ctx->paired_sec) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_paired and snapgpu_enable_secondary must both have been called on this context");
-    if (n_pairs == 0) return SNAPGPU_OK;
-    const PairedInFlight in_flight(ctx); ctx->paired_share = in_flight.share;      // (paired_grid_share: this call's launches ask for their share of the chip)
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    PairedSecOut so{d_secondary, secondary_stride, d_n_secondary, d_single_secondary, single_stride, d_n_single_secondary};
-    int rc = launch_paired(ctx, n_pairs, d_bases, d_quals, d_offsets, d_primary, d_first_alt, s, &so);
-    if (rc) return rc;
-    if (!stream) return finish_timing(ctx);
-    return SNAPGPU_OK;
-}
-
-static int ensure_psec_stage(snapgpu_ctx *ctx, int which, size_t bytes) {
-    if (ctx->psec_stage_cap[which] >= bytes) return 0;
-    if (ctx->d_psec_stage[which]) (void)hipFree(ctx->d_psec_stage[which]);
-    ctx->d_psec_stage[which] = nullptr; ctx->psec_stage_cap[which] = 0;
-    size_t cap = bytes + bytes / 4 + 4096;
-    HIPCHK(ctx, hipMalloc(&ctx->d_psec_stage[which], cap), SNAPGPU_E_NOMEM);
-    ctx->psec_stage_cap[which] = cap;
-    return 0;
+    const PairedSecOut so{d_secondary, secondary_stride, d_n_secondary, d_single_secondary, single_stride, d_n_single_secondary};
+    return align_paired_call(ctx, false, n_pairs, d_bases, d_quals, d_offsets, d_primary, d_first_alt, &so, stream);
 }
 
 extern "C" int snapgpu_align_paired_secondary(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
@@ -2784,50 +2588,8 @@ extern "C" int snapgpu_align_paired_secondary(snapgpu_ctx *ctx, uint32_t n_pairs
     if (!ctx || !bases || !quals || !offsets || !primary || !n_secondary || !n_single_secondary ||
         (secondary_stride && !secondary) || (single_stride && !single_secondary))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_paired_secondary: null argument");
-    if (!ctx->paired_sec) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_enable_paired and snapgpu_enable_secondary must both have been called on this context");
-    if (n_pairs == 0) return SNAPGPU_OK;
-    const size_t nr = (size_t)2 * n_pairs;
-    for (size_t i = 0; i < nr; i++) {
-        if (offsets[i + 1] < offsets[i]) return fail(ctx, SNAPGPU_E_INVALID, "offsets must be non-decreasing");
-        if (offsets[i + 1] - offsets[i] > ctx->params.max_read_len)
-            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (IntersectingPairedEndAligner.cpp:361-365)");
-    }
-    const PairedInFlight in_flight(ctx); ctx->paired_share = in_flight.share;      // (paired_grid_share: this call's launches ask for their share of the chip)
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    size_t nb = (size_t)offsets[nr];
-    const size_t sec_bytes = (size_t)n_pairs * secondary_stride * sizeof(snapgpu_paired_result);
-    const size_t ssec_bytes = (size_t)n_pairs * single_stride * sizeof(snapgpu_single_result);
-    int rc;
-    if ((rc = ensure_stage(ctx, 0, nb + 16)) || (rc = ensure_stage(ctx, 1, nb + 16)) || (rc = ensure_stage(ctx, 2, (nr + 1) * 8)) ||
-        (rc = ensure_stage(ctx, 3, (size_t)n_pairs * sizeof(snapgpu_paired_result))) ||
-        (rc = ensure_stage(ctx, 4, (size_t)n_pairs * sizeof(snapgpu_paired_result))) ||
-        (rc = ensure_psec_stage(ctx, 0, sec_bytes + 16)) || (rc = ensure_psec_stage(ctx, 1, (size_t)n_pairs * 4)) ||
-        (rc = ensure_psec_stage(ctx, 2, ssec_bytes + 16)) || (rc = ensure_psec_stage(ctx, 3, nr * 4))) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[0], bases, nb, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[1], quals, nb, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage[2], offsets, (nr + 1) * 8, hipMemcpyHostToDevice, s), SNAPGPU_E_LAUNCH);
-    if (sec_bytes) HIPCHK(ctx, hipMemsetAsync(ctx->d_psec_stage[0], 0, sec_bytes, s), SNAPGPU_E_LAUNCH);
-    if (ssec_bytes) HIPCHK(ctx, hipMemsetAsync(ctx->d_psec_stage[2], 0, ssec_bytes, s), SNAPGPU_E_LAUNCH);
-    PairedSecOut so{ctx->d_psec_stage[0], secondary_stride, ctx->d_psec_stage[1], ctx->d_psec_stage[2], single_stride, ctx->d_psec_stage[3]};
-    rc = launch_paired(ctx, n_pairs, ctx->d_stage[0], ctx->d_stage[1], ctx->d_stage[2], ctx->d_stage[3], first_alt ? ctx->d_stage[4] : nullptr, s, &so);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(primary, ctx->d_stage[3], (size_t)n_pairs * sizeof(snapgpu_paired_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (first_alt) HIPCHK(ctx, hipMemcpyAsync(first_alt, ctx->d_stage[4], (size_t)n_pairs * sizeof(snapgpu_paired_result), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (sec_bytes) HIPCHK(ctx, hipMemcpyAsync(secondary, ctx->d_psec_stage[0], sec_bytes, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_secondary, ctx->d_psec_stage[1], (size_t)n_pairs * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    if (ssec_bytes) HIPCHK(ctx, hipMemcpyAsync(single_secondary, ctx->d_psec_stage[2], ssec_bytes, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(n_single_secondary, ctx->d_psec_stage[3], nr * 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
-    rc = finish_timing(ctx);
-    if (rc) return rc;
-    bool truncated = false;
-    for (uint32_t i = 0; i < n_pairs; i++) {
-        if (primary[i].flags & SNAPGPU_PAIR_POOL_OVERFLOW)
-            return fail(ctx, SNAPGPU_E_UNSUPPORTED, "a read pair needed more candidate entries than the per-wave pools hold (the reference would grow its buffers or ask for -mcp); its result is flagged");
-        if (n_secondary[i] > secondary_stride || (uint64_t)n_single_secondary[2 * (size_t)i] + n_single_secondary[2 * (size_t)i + 1] > single_stride) truncated = true;
-    }
-    return truncated ? SNAPGPU_W_SECONDARY_TRUNCATED : SNAPGPU_OK;
+    const PairedSecOut so{secondary, secondary_stride, n_secondary, single_secondary, single_stride, n_single_secondary};
+    return align_paired_call(ctx, true, n_pairs, bases, quals, offsets, primary, first_alt, &so, nullptr);
 }
 
 extern "C" int snapgpu_get_counters(snapgpu_ctx *ctx, snapgpu_counters *out, int reset) {
