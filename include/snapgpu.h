@@ -24,6 +24,11 @@
  *       AlignmentAdjuster::AdjustAlignment      SNAPLib/AlignmentAdjuster.cpp:33-190 (the `-ae` step, BaseAligner.cpp:2444-2463)
  *   snapgpu_sam_fields_paired
  *       SAMFormat::writePairs / fillMateInfo    SNAPLib/SAM.cpp:1575-1895 / 1308-1421; SimpleReadWriter::writePairs SNAPLib/ReadWriter.cpp:345-520
+ *   snapgpu_sam_fields_paired_device
+ *       the same, for arrays already in HBM (the results where snapgpu_align_paired_device left them)
+ *   snapgpu_align_sam_paired
+ *       ChimericPairedEndAligner::align as PairedAlignerContext::runIterationThread calls it  SNAPLib/PairedAligner.cpp:640-790 (the
+ *       useful-read test :680-682), followed by SimpleReadWriter::writePairs  SNAPLib/ReadWriter.cpp:345-520
  *   snapgpu_sam_fields_single
  *       SimpleReadWriter::writeReads            SNAPLib/ReadWriter.cpp:170-330
  *       SAMFormat::writeRead / createSAMLine / computeCigarString  SNAPLib/SAM.cpp:1898-2352 / 1424-1572 / 2595-2766
@@ -476,6 +481,38 @@ int  snapgpu_sam_fields_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *b
                                int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
                                int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
                                int32_t *reference_history_dependent);
+
+/* Device-pointer form of snapgpu_sam_fields_paired (SAMFormat::writePairs / fillMateInfo, SNAPLib/SAM.cpp:1575-1895 / 1308-1421): every
+ * array already in HBM (the 2 * n_pairs unclipped mates, Read::clip's outcome, the PairedAlignmentResults snapgpu_align_paired_device left
+ * there), outputs left in HBM.  max_read_len >= the longest mate of the batch (it sizes the LDS rows and the per-wave scratch, which this call
+ * still allocates and frees itself).  Synchronous on `stream` (NULL: the context's). */
+int  snapgpu_sam_fields_paired_device(snapgpu_ctx *ctx, uint32_t n_pairs, uint32_t max_read_len, const void *d_bases, const void *d_quals,
+                                      const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_results, int use_m,
+                                      void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
+                                      void *d_n_ops, void *d_nm, void *d_rnext, void *d_pnext, void *d_tlen, void *d_first_written,
+                                      void *d_reference_history_dependent, void *stream);
+
+/*
+ * The paired-end path of a SAM writer in ONE call: ChimericPairedEndAligner::align as PairedAlignerContext::runIterationThread calls it
+ * (SNAPLib/PairedAligner.cpp:640-790) over the clipped mates, then what SimpleReadWriter::writePairs (SNAPLib/ReadWriter.cpp:345-520)
+ * computes for each pair's result (snapgpu_sam_fields_paired) -- with the batch uploaded once and the results handed from the align
+ * kernels (the main pass, the pool-overflow pass and the exact replay) to the SAM-field kernels in HBM.  Host pointers.
+ *   bases / quals / offsets   the 2 * n_pairs UNCLIPPED mates (offsets[2 * n_pairs + 1]); front_clip / data_len [2 * n_pairs]: Read::clip's
+ *                             outcome (the aligner sees bases[offsets[i] + front_clip[i] .. + data_len[i]), the SAM-field kernel the whole mate)
+ *   skip[i] != 0   [n_pairs]  neither mate is useful (too short, too many Ns: PairedAligner.cpp:680-682): the pair is not given to the aligner and
+ *                             both mates are written unaligned (status NotFound, location InvalidGenomeLocation32, score -1, the rest 0)
+ *   results / first_alt       [n_pairs] out, each may be NULL: the PairedAlignmentResults, for a caller that wants them
+ *   flag .. reference_history_dependent   as snapgpu_sam_fields_paired (a cigar that does not fit ops_stride: n_ops -1, nm -2)
+ * The context must have snapgpu_enable_paired and no snapgpu_enable_secondary; a mate the aligner is given that is longer than max_read_len
+ * is SNAPGPU_E_INVALID (IntersectingPairedEndAligner.cpp:361-365); a pair that outgrew the candidate pools is reported as by
+ * snapgpu_align_paired (SNAPGPU_E_UNSUPPORTED, outputs written).  With secondary results or ALT records to write, use the two calls it replaces.
+ */
+int  snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                              const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                              snapgpu_paired_result *results, snapgpu_paired_result *first_alt,
+                              int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                              int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
+                              int32_t *reference_history_dependent);
 
 /*
  * Batched AffineGapVectorized<dir>::computeScore (banded[i] == 0) / computeScoreBanded

@@ -51,7 +51,7 @@ EXPORTED_SYMBOLS = [
     "snapgpu_align_single_device", "snapgpu_get_counters", "snapgpu_kernel_time",
     "snapgpu_enable_secondary", "snapgpu_align_single_secondary", "snapgpu_align_single_secondary_device",
     "snapgpu_align_paired_secondary", "snapgpu_align_paired_secondary_device",
-    "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_align_sam_single", "snapgpu_create_replica_with_params",
+    "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_paired", "snapgpu_create_replica_with_params",
     "snapgpu_default_index_build_params", "snapgpu_index_build", "snapgpu_index_build_from_fasta", "snapgpu_index_build_shaped",
     "snapgpu_index_build_from_fasta_shaped", "snapgpu_built_index_view",
     "snapgpu_built_index_save", "snapgpu_built_index_stats", "snapgpu_built_index_destroy",
@@ -372,6 +372,26 @@ class BaseAligner:
         return dict(flag=flag, contig=contig, pos=pos, mapq=mapq, ops=ops, n_ops=n_ops, nm=nm, rnext=rnext, pnext=pnext, tlen=tlen,
                     first_written=first, stale=stale)
 
+    def samFieldsPaired_device(self, n_pairs: int, max_read_len: int, d_bases: int, d_quals: int, d_offsets: int, d_front_clip: int, d_data_len: int,
+                               d_results: int, d_flag: int, d_contig: int, d_pos: int, d_mapq: int, d_ops: int, ops_stride: int, d_n_ops: int, d_nm: int,
+                               d_rnext: int, d_pnext: int, d_tlen: int, d_first_written: int, d_stale: int, use_m: bool = False, stream: int = 0):
+        """Device-pointer form of samFieldsPaired (snapgpu_sam_fields_paired_device): every array already in HBM -- e.g. the results where
+        ChimericPairedEndAligner.align_device left them -- and the outputs left there.  Synchronous on `stream` (0: the context's)."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.lib.snapgpu_sam_fields_paired_device.argtypes = ([C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 5 +
+                                                              [C.c_uint32] + [C.c_void_p] * 8)
+        self._check(self.lib.snapgpu_sam_fields_paired_device(
+            self.handle, C.c_uint32(n_pairs), C.c_uint32(max_read_len), vp(d_bases), vp(d_quals), vp(d_offsets), vp(d_front_clip), vp(d_data_len),
+            vp(d_results), C.c_int(1 if use_m else 0), vp(d_flag), vp(d_contig), vp(d_pos), vp(d_mapq), vp(d_ops), C.c_uint32(ops_stride), vp(d_n_ops),
+            vp(d_nm), vp(d_rnext), vp(d_pnext), vp(d_tlen), vp(d_first_written), vp(d_stale), vp(stream)), "snapgpu_sam_fields_paired_device")
+
+    def samf_pre_valid(self) -> int:
+        """Diagnostics: SamfPre records the row-loop pre-pass of this context's last SAM-field launch left valid (0: no pre-pass ran)."""
+        v = C.c_uint64(0)
+        self.lib.snapgpu_debug_samf_pre_valid.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        self._check(self.lib.snapgpu_debug_samf_pre_valid(self.handle, C.byref(v)), "snapgpu_debug_samf_pre_valid")
+        return int(v.value)
+
     # ---- BaseAligner::AlignRead over a batch -------------------------------------------
     def AlignRead(self, bases: np.ndarray, quals: np.ndarray, offsets: np.ndarray):
         """Returns (primaryResult[n], firstALTResult[n]) as RESULT_DTYPE arrays."""
@@ -522,6 +542,33 @@ class ChimericPairedEndAligner(BaseAligner):
         self._check(self.lib.snapgpu_align_paired(self.handle, C.c_uint32(n), ptr(bases), ptr(quals), ptr(offsets),
                                                   ptr(primary), ptr(first_alt)), "snapgpu_align_paired")
         return primary, first_alt
+
+    def alignSamPaired(self, bases, quals, offsets, front_clip, data_len, skip, use_m: bool = False, ops_stride: int = 64, want_results: bool = True):
+        """The paired-end path of a SAM writer in one call (snapgpu_align_sam_paired): ChimericPairedEndAligner::align over Read::clip's
+        windows (PairedAligner.cpp:700) and SAMFormat::writePairs' computed fields for each pair's result, the batch uploaded once.
+        bases / quals / offsets (2 n + 1 entries): the unclipped mates; front_clip / data_len [2 n]: Read::clip's outcome; skip[i] != 0:
+        pair i is not given to the aligner (neither mate useful, PairedAligner.cpp:680-682).  Returns (results, first_alt, dict(flag,
+        contig, pos, mapq, ops, n_ops, nm, rnext, pnext, tlen, first_written, stale)); want_results = False: (None, None, dict)."""
+        from .abi import PAIRED_RESULT_DTYPE
+        bases = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1); quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        front_clip = np.ascontiguousarray(front_clip, dtype=np.int32); data_len = np.ascontiguousarray(data_len, dtype=np.int32)
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        if (offsets.size - 1) % 2:
+            raise ValueError("offsets must have 2*n_pairs + 1 entries")
+        n = offsets.size - 1; npairs = n // 2
+        results = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
+        first_alt = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
+        flag = np.zeros(n, np.int32); contig = np.zeros(n, np.int32); pos = np.zeros(n, np.int64); mapq = np.zeros(n, np.int32)
+        ops = np.zeros((n, ops_stride), dtype=np.uint32); n_ops = np.zeros(n, np.int32); nm = np.zeros(n, np.int32); stale = np.zeros(n, np.int32)
+        rnext = np.zeros(n, np.int32); pnext = np.zeros(n, np.int64); tlen = np.zeros(n, np.int64); first = np.zeros(npairs, np.int32)
+        self._check(self.lib.snapgpu_align_sam_paired(
+            self.handle, C.c_uint32(npairs), ptr(bases), ptr(quals), ptr(offsets), ptr(front_clip), ptr(data_len), ptr(skip),
+            C.c_int(1 if use_m else 0), ptr(results) if want_results else None, ptr(first_alt) if want_results else None,
+            ptr(flag), ptr(contig), ptr(pos), ptr(mapq), ptr(ops), C.c_uint32(ops_stride), ptr(n_ops), ptr(nm),
+            ptr(rnext), ptr(pnext), ptr(tlen), ptr(first), ptr(stale)), "snapgpu_align_sam_paired")
+        return results, first_alt, dict(flag=flag, contig=contig, pos=pos, mapq=mapq, ops=ops, n_ops=n_ops, nm=nm, rnext=rnext, pnext=pnext,
+                                        tlen=tlen, first_written=first, stale=stale)
 
     def align_secondary(self, bases: np.ndarray, quals: np.ndarray, offsets: np.ndarray, stride: int = 8, single_stride: int = 16):
         """ChimericPairedEndAligner::align with secondary results (after enable_secondary(...)): returns

@@ -37,6 +37,7 @@ struct SamFieldsArgs {
     int32_t *flag; int32_t *contig; int64_t *pos; int32_t *mapq; uint32_t *ops; int32_t *n_ops; int32_t *nm; int32_t *stale;
     // the banded row loops run ahead of the records, eight reads to a wavefront (cigar_ag.h: SamfPre; k_samf_dp8): n * pre_stride bytes, or NULL
     uint8_t *pre; uint64_t pre_stride; uint32_t *pre_counter;
+    uint32_t *pre_valid;                                                         // SamfPre records the pre-pass left valid (snapgpu_debug_samf_pre_valid)
 };
 
 struct SamFieldsPairedArgs {
@@ -51,11 +52,15 @@ struct SamFieldsPairedArgs {
     // per read [2 * n_pairs]
     int32_t *flag; int32_t *contig; int64_t *pos; int32_t *mapq; uint32_t *ops; int32_t *n_ops; int32_t *nm; int32_t *rnext; int64_t *pnext; int64_t *tlen; int32_t *stale;
     int32_t *first_written;                                                      // [n_pairs]: which read's record comes first in the file
+    // the banded row loops of the 2 * n_pairs mates run ahead of the records (k_samf_dp8_paired): one SamfPre per mate, or NULL
+    uint8_t *pre; uint64_t pre_stride; uint32_t *pre_counter;
+    uint32_t *pre_valid;
 };
 
 extern "C" void snapgpu_launch_sam_fields_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 extern "C" void snapgpu_launch_sam_fields(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 extern "C" void snapgpu_launch_samf_dp8(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+extern "C" void snapgpu_launch_samf_dp8_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 extern "C" size_t snapgpu_samf_dp8_lds_per_wave(uint32_t RL);
 extern "C" void snapgpu_launch_cigar_ag(const CigarAGArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 // snapgpu_adjust_alignments: AlignmentAdjuster::AdjustAlignment for a batch of results (adjust.h), one wavefront per result

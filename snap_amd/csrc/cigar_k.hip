@@ -143,9 +143,28 @@ static __host__ __device__ __forceinline__ uint32_t samf_dp8_group_bytes(uint32_
 }
 extern "C" size_t snapgpu_samf_dp8_lds_per_wave(uint32_t RL) { return (size_t)8 * samf_dp8_group_bytes(RL); }
 
-__global__ __launch_bounds__(256) void k_samf_dp8(SamFieldsArgs a)
+// Where a read's result fields come from: the batch's snapgpu_single_result records, or mate r & 1 of pair r >> 1's snapgpu_paired_result.
+struct SamfDp8Res { int status, score, dir, add_front, used_ag, clipped_before, clipped_after; long long loc; };
+static __device__ __forceinline__ uint32_t samf_dp8_n(const SamFieldsArgs &a) { return a.n; }
+static __device__ __forceinline__ uint32_t samf_dp8_n(const SamFieldsPairedArgs &a) { return 2u * a.n_pairs; }
+static __device__ __forceinline__ SamfDp8Res samf_dp8_res(const SamFieldsArgs &a, uint32_t r) {
+    const snapgpu_single_result *rp = &a.results[r];
+    return SamfDp8Res{rp->status, rp->score, rp->direction, rp->clipping_for_read_adjustment, rp->used_affine_gap_scoring, rp->bases_clipped_before,
+                      rp->bases_clipped_after, (long long)rp->location};
+}
+static __device__ __forceinline__ SamfDp8Res samf_dp8_res(const SamFieldsPairedArgs &a, uint32_t r) {
+    const snapgpu_paired_result *pr = &a.results[r >> 1]; const uint32_t w = r & 1u;
+    return SamfDp8Res{pr->status[w], pr->score[w], pr->direction[w], pr->clipping_for_read_adjustment[w], pr->used_affine_gap_scoring[w],
+                      pr->bases_clipped_before[w], pr->bases_clipped_after[w], (long long)pr->location[w]};
+}
+
+// A = SamFieldsArgs (k_samf_dp8: one SamfPre per read) or SamFieldsPairedArgs (k_samf_dp8_paired: one per mate, 2 * n_pairs of them).  A mate's
+// record goes through sam_fields_single_item's `paired` branch, whose attempt 0 differs from the single-end one in two places only: the aligner's
+// soft clipping is applied whether or not the affine-gap writer runs (the test below wants the affine-gap writer anyway), and a read that hangs
+// over the end of its contig is formatted at `extra` instead of being moved (the test below wants extra == 0).  So the same test holds for both.
+template <class A>
+static __device__ __forceinline__ void samf_dp8_run(const A &a, uint8_t *lds)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = lane_id(), el = lane & 7, g = lane >> 3;
     const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t RL = a.RL, HN = samf_dp8_hn(RL), GB = samf_dp8_group_bytes(RL);
@@ -156,28 +175,30 @@ __global__ __launch_bounds__(256) void k_samf_dp8(SamFieldsArgs a)
     const int open = a.prm.gap_open, ext = a.prm.gap_ext, score_init = AGC_MAX_READ_LENGTH;
     const unsigned long long gmask = 0xffull << (8 * g);
     const long long nb = (long long)a.ix.n_bases;
+    const uint32_t n = samf_dp8_n(a);
+    uint32_t n_valid = 0;
     while (true) {
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(a.pre_counter, 8u);
         base = first_u32(base);
-        if (base >= a.n) break;
+        if (base >= n) break;
         const uint32_t r = base + (uint32_t)g;
         // ---- is this read's first cigar call the case this kernel runs?  (sam_fields_single_item attempt 0, cigar_ag_item pass 0)
-        bool elig = r < a.n;
+        bool elig = r < n;
         int plen = 0, w = 0, dir = 0, bcb = 0, U = 0;
         long long loc = 0;
         uint64_t rb = 0;
         SamfPre *pre = (SamfPre *)(a.pre + (size_t)(elig ? r : base) * a.pre_stride);
         if (elig) {
-            const snapgpu_single_result *rp = &a.results[r];
+            const SamfDp8Res rp = samf_dp8_res(a, r);
             rb = a.offsets[r]; U = (int)(a.offsets[r + 1] - rb);
-            const int status = rp->status, score = rp->score, F0 = a.front_clip[r], D0 = a.data_len[r], addF = rp->clipping_for_read_adjustment;
-            loc = rp->location; dir = rp->direction;
-            const bool ag_branch = a.use_affine_gap != 0 && (rp->used_affine_gap_scoring != 0 || score > 0);
+            const int status = rp.status, score = rp.score, F0 = a.front_clip[r], D0 = a.data_len[r], addF = rp.add_front;
+            loc = rp.loc; dir = rp.dir;
+            const bool ag_branch = a.use_affine_gap != 0 && (rp.used_ag != 0 || score > 0);
             const int front = F0 + addF, dlen = D0 - addF;
             int clipped = dlen, bca;
             if (dir == 1) { bcb = U - clipped - front; bca = front; } else { bcb = front; bca = U - clipped - bcb; }
-            bcb += rp->bases_clipped_before; bca += rp->bases_clipped_after; clipped -= rp->bases_clipped_before + rp->bases_clipped_after;
+            bcb += rp.clipped_before; bca += rp.clipped_after; clipped -= rp.clipped_before + rp.clipped_after;
             elig = status != SNAPGPU_NotFound && ag_branch && loc >= 0 && loc < nb && score >= 0 && score <= SAMF_PRE_MAX_W && U <= (int)RL &&
                    clipped >= 3 * (2 * score + 1) && bcb >= 0 && bcb + clipped <= U && dlen >= 0;
             if (elig) {
@@ -190,7 +211,7 @@ __global__ __launch_bounds__(256) void k_samf_dp8(SamFieldsArgs a)
             plen = clipped; w = score;
         }
         const int rows_cap = (int)samf_pre_rows(RL);
-        if (el == 0 && r < a.n) pre->valid = 0;
+        if (el == 0 && r < n) pre->valid = 0;
         if (!BALLOT(elig)) continue;
         // the group's shape: vectors per segment (1 or 2), segment length, segments
         const int bw = 2 * w + 1 < plen ? 2 * w + 1 : plen;
@@ -328,13 +349,33 @@ __global__ __launch_bounds__(256) void k_samf_dp8(SamFieldsArgs a)
             pre->plen = plen; pre->w = w; pre->bcb = bcb; pre->loc = loc; pre->score = score; pre->text_used = text_used; pre->dir = dir; pre->rows = rows_cap;
             pre->valid = 1;
         }
+        n_valid += (uint32_t)__builtin_popcountll(BALLOT(elig && el == 0));
         WAVE_SYNC();
     }
+    if (lane == 0 && n_valid != 0u) atomicAdd(a.pre_valid, n_valid);
 }
+
+__global__ __launch_bounds__(256) void k_samf_dp8(SamFieldsArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    samf_dp8_run(a, lds);
+}
+
+// the 2 * n_pairs mates of a paired batch (k_sam_fields_paired hands mate 2 * i + w its record)
+__global__ __launch_bounds__(256) void k_samf_dp8_paired(SamFieldsPairedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    samf_dp8_run(a, lds);
+}
+
 
 extern "C" void snapgpu_launch_samf_dp8(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
 {
     hipLaunchKernelGGL(k_samf_dp8, dim3(blocks), dim3(256), lds_bytes, s, *a);
+}
+extern "C" void snapgpu_launch_samf_dp8_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_samf_dp8_paired, dim3(blocks), dim3(256), lds_bytes, s, *a);
 }
 
 // paired-end writer: both reads of a pair by one wavefront, then SAMFormat::fillMateInfo for each (sam_fields.h)
@@ -373,8 +414,9 @@ __global__ __launch_bounds__(256, SAMF_WAVES) void k_sam_fields_paired(SamFields
             r.ag_score = 0; r.supplementary = (int32_t)first_u32((uint32_t)pr->supplementary[w]); r.seed_offset = 0; r.match_probability = 0.0;
             r.probability_all_candidates = 0.0; r.popular_seeds_skipped = 0; r.reserved = 0;
             const int F0 = (int)first_u32((uint32_t)a.front_clip[ri]), D0 = (int)first_u32((uint32_t)a.data_len[ri]);
+            const SamfPre *pre = a.pre ? (const SamfPre *)(a.pre + (size_t)ri * a.pre_stride) : nullptr;
             o[w] = sam_fields_single_item(a.ix, prm, a.use_affine_gap != 0, a.use_m != 0, a.bases + b, a.quals + b, (int)(e - b), F0, D0, r,
-                                          my, a.RL, oriented, lv_cells, ag_scratch, a.ops + (size_t)ri * a.ops_stride, (int)a.ops_stride, true);
+                                          my, a.RL, oriented, lv_cells, ag_scratch, a.ops + (size_t)ri * a.ops_stride, (int)a.ops_stride, true, pre);
             WAVE_SYNC();
         }
         for (int w = 0; w < 2; w++) {

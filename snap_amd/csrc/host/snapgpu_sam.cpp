@@ -2,7 +2,7 @@
 //     snapgpu-sam single <index-dir> <reads.fq> -o <out.sam> [-d maxDist] [-G-] [-=] [-M] [-Cxx] [-ea] [-D n] [-om n [-omax n] [-mpc n]] [-mrl minReadLength]
 //                        [-b readsPerBatch] [-gpus n] [-q contextsPerGpu] [-t formatterThreads]
 //     snapgpu-sam paired <index-dir> <reads1.fq> <reads2.fq> -o <out.sam> [same options]
-// Streams FASTQ records in batches across include/snapgpu.h -- snapgpu_align_single / snapgpu_align_paired (BaseAligner::AlignRead,
+// Streams FASTQ records in batches across include/snapgpu.h -- snapgpu_align_sam_single / snapgpu_align_sam_paired (BaseAligner::AlignRead,
 // ChimericPairedEndAligner::align) and snapgpu_sam_fields_single / _paired (what SimpleReadWriter::writeReads / writePairs compute before
 // they print) -- and prints the records the way the reference does.
 //
@@ -822,6 +822,35 @@ static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
     std::vector<int32_t> front_clip(n, 0), data_len(n, 0);
     std::vector<char> useful(n, 0);
     for (size_t i = 0; i < n; i++) useful[i] = clip_read(o, b, i, front_clip[i], data_len[i]);
+    // ---- the common case in ONE call (snapgpu_align_sam_paired): no secondary results, one record pair per pair unless -ea has a first-ALT result to
+    // write.  The batch goes up as it was parsed -- no clipped copy for the aligner, no results coming back to be scattered and sent up again.
+    // (SNAPGPU_SAM_PAIRED_FUSED=0: measurement knob, the calls it replaces)
+    static const bool fused_on = !(getenv("SNAPGPU_SAM_PAIRED_FUSED") && atoi(getenv("SNAPGPU_SAM_PAIRED_FUSED")) == 0);
+    if (o.om < 0 && np > 0 && fused_on) {
+        const bool want_alt = o.p.emit_alt_alignments != 0;
+        std::vector<uint8_t> skip(np);
+        for (size_t k = 0; k < np; k++) skip[k] = !useful[2 * k] && !useful[2 * k + 1];      // neither mate useful (PairedAligner.cpp:680-682)
+        std::vector<snapgpu_paired_result> fres, falt;
+        if (want_alt) { fres.resize(np); falt.resize(np); }
+        const size_t nrec = 2 * np;
+        w.emit.clear(); w.pu_pair.resize(np); w.pu_secondary.assign(np, 0); w.su_read.clear();
+        for (size_t k = 0; k < np; k++) { w.emit.push_back(Work::Emit{(uint32_t)k, 0}); w.pu_pair[k] = (uint32_t)k; }
+        w.flag.assign(nrec, 0); w.contig.assign(nrec, 0); w.mapq.assign(nrec, 0); w.n_ops.assign(nrec, 0); w.nm.assign(nrec, 0); w.rnext.assign(nrec, 0);
+        w.first_written.assign(np, 0); w.pos.assign(nrec, 0); w.pnext.assign(nrec, 0); w.tlen.assign(nrec, 0);
+        w.s_flag.clear(); w.s_contig.clear(); w.s_mapq.clear(); w.s_n_ops.clear(); w.s_nm.clear(); w.s_pos.clear();
+        w.ops_stride = w.s_ops_stride = o.ops_stride;
+        std::vector<int32_t> stale(nrec);
+        with_growing_stride(w, nrec, [&] {
+            int rc = snapgpu_align_sam_paired(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(), skip.data(),
+                                              o.use_m ? 1 : 0, want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL,
+                                              w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(), w.ops.data(), w.ops_stride, w.n_ops.data(),
+                                              w.nm.data(), w.rnext.data(), w.pnext.data(), w.tlen.data(), w.first_written.data(), stale.data());
+            if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_paired", rc);
+        });
+        bool any_alt = false;
+        if (want_alt) for (size_t k = 0; k < np && !any_alt; k++) any_alt = !skip[k] && (falt[k].status[0] != SNAPGPU_NotFound || falt[k].status[1] != SNAPGPU_NotFound);
+        if (!any_alt) return;                                           // (rare: a first-ALT pair to write -- the batch goes through the calls below)
+    }
     std::vector<uint32_t> to_align;                                     // pairs with at least one useful mate (PairedAligner.cpp:680-682)
     std::vector<char> ab, aq; std::vector<uint64_t> ao(1, 0);
     for (size_t k = 0; k < np; k++) {

@@ -66,6 +66,10 @@ struct PairedArgs {
     uint32_t single_agc_cap;
     const uint8_t *bases, *quals;
     const uint64_t *offsets;           // [2n+1]
+    // Read::clip's window over an UNCLIPPED batch (snapgpu_align_sam_paired: the k_align_paired<.., CLIP = true> launches; no other launch looks at them): mate 2i + w is
+    // bases[offsets[2i+w] + front_clip[2i+w] .. + data_len[2i+w]); skip[i] != 0: pair i is not given to the aligner (neither mate useful,
+    // PairedAligner.cpp:680-682) and gets the not-found result
+    const int32_t *front_clip, *data_len; const uint8_t *skip;
     uint32_t n_pairs;
     int32_t max_k_paired, max_k_single;
     snapgpu_paired_result *primary, *first_alt;
@@ -105,4 +109,13 @@ void snapgpu_launch_paired_exact_4(const PairedArgs *a, uint32_t blocks, size_t 
 void snapgpu_launch_paired_exact_6(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 void snapgpu_launch_paired_sec_exact_3(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 void snapgpu_launch_paired_sec_exact_0(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+// k_align_paired<.., CLIP = true> (paired_k.hip, the units without -DPAIRED_SEC): PairedArgs::front_clip / data_len / skip are given
+void snapgpu_launch_paired_clip_3(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_paired_clip_4(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_paired_clip_6(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_paired_clip_0(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_paired_clip_exact_3(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_paired_clip_exact_4(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_paired_clip_exact_6(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_paired_clip_exact_0(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 }

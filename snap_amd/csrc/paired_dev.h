@@ -562,7 +562,10 @@ struct DevPL {
 // Scalar-heavy control flow; 3 waves per SIMD for the 192-position variant, 2 for the others: what its LDS footprint (under 10 KB per
 // wave since round 3: Landau-Vishkin triangle for limits <= 22 only, the register affine-gap forms' tables instead of the LDS form's rows)
 // allows and what was measured: paired_args.h, SNAPGPU_PAIRED_WAVES_PER_SIMD.
-template <int AGC, bool SEC, bool EXACT = false>
+// CLIP: the batch is unclipped and PairedArgs::front_clip / data_len / skip say what the aligner is given (snapgpu_align_sam_paired).  A template
+// parameter, not a test of the pointers: the kernel has no registers to spare (168 VGPRs with spills, every SGPR in use), and three more
+// wave-uniform pointers live across the pair loop cost the plain launches 21 more spilled VGPRs and 450 more spilled SGPRs when it was one.
+template <int AGC, bool SEC, bool EXACT = false, bool CLIP = false>
 __global__ __launch_bounds__(256, SNAPGPU_PAIRED_WAVES_PER_SIMD(AGC)) void k_align_paired(PairedArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -657,7 +660,8 @@ __global__ __launch_bounds__(256, SNAPGPU_PAIRED_WAVES_PER_SIMD(AGC)) void k_ali
     // both reads of pair i, both orientations, into this wave's LDS
     auto load_pair = [&](uint32_t i) {
         for (int r = 0; r < 2; r++) {
-            const uint64_t b = first_u64(a.offsets[2 * (size_t)i + r]), e = first_u64(a.offsets[2 * (size_t)i + r + 1]);
+            uint64_t b = first_u64(a.offsets[2 * (size_t)i + r]), e = first_u64(a.offsets[2 * (size_t)i + r + 1]);
+            if constexpr (CLIP) { b += (uint64_t)first_u32((uint32_t)a.front_clip[2 * (size_t)i + r]); e = b + (uint64_t)first_u32((uint32_t)a.data_len[2 * (size_t)i + r]); }
             int len = (int)(e - b);
             if (len < 0 || len > (int)RL) len = 0;          // (the host rejects such batches; never write past the LDS buffers)
             uint8_t *f = prd + (2 * r) * RL, *rc = prd + (2 * r + 1) * RL, *qf = pql + (2 * r) * RL, *qr = pql + (2 * r + 1) * RL;
@@ -681,6 +685,17 @@ __global__ __launch_bounds__(256, SNAPGPU_PAIRED_WAVES_PER_SIMD(AGC)) void k_ali
         i = first_u32(i);
         if (i >= n_total) break;
         if (a.remap) i = first_u32(a.remap[i]);
+        if (CLIP && first_u32((uint32_t)a.skip[i]) != 0u) {       // not given to the aligner: NotFound, no location, score -1 for both mates; no flags, so no later pass takes it
+            const int nd = (int)(sizeof(snapgpu_paired_result) / 4);
+            if (lane < nd) { ((uint32_t *)&a.primary[i])[lane] = 0u; if (a.first_alt) ((uint32_t *)&a.first_alt[i])[lane] = 0u; }
+            WAVE_SYNC();                                          // (one wave's stores reach memory in issue order: the fields below land on the zeros)
+            if (lane < 2) {
+                a.primary[i].status[lane] = SNAPGPU_NotFound; a.primary[i].location[lane] = SNAPGPU_InvalidGenomeLocation32; a.primary[i].score[lane] = -1;
+                if (a.first_alt) { a.first_alt[i].status[lane] = SNAPGPU_NotFound; a.first_alt[i].location[lane] = SNAPGPU_InvalidGenomeLocation32; a.first_alt[i].score[lane] = -1; }
+            }
+            if (!EXACT && a.help_done != nullptr && lane == 0) atomicAdd(a.help_done, 1u);
+            continue;
+        }
         if constexpr (EXACT) {          // newly constructed reference aligners: all four traceback arrays read as zero -- cleared once per
             if (++pl.ag_epoch == 16u) { // fifteen pairs; in between, cells that do not carry this pair's tag read as zero (dev_common.h: bt_cell)
                 if (pl.ag_hw0) wave_zero16(pl.ag_persist0, ((size_t)pl.ag_hw0 + 15) & ~(size_t)15);

@@ -15,6 +15,16 @@
 #define PE_CAT2(a, b) a##b
 #define PE_CAT(a, b) PE_CAT2(a, b)
 
+#ifndef PAIRED_SEC      // the variant (and its exact twin) that reads each mate through Read::clip's window over an unclipped batch (snapgpu_align_sam_paired)
+extern "C" void PE_CAT(snapgpu_launch_paired_clip_, PAIRED_AGC)(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_align_paired<PAIRED_AGC, false, false, true>), dim3(blocks), dim3(256), lds_bytes, s, *a);
+}
+extern "C" void PE_CAT(snapgpu_launch_paired_clip_exact_, PAIRED_AGC)(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_align_paired<PAIRED_AGC, false, true, true>), dim3(blocks), dim3(256), lds_bytes, s, *a);
+}
+#endif
 #ifdef PAIRED_SEC       // the variant that also produces secondary results (-om)
 extern "C" void PE_CAT(snapgpu_launch_paired_sec_, PAIRED_AGC)(const PairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
 {

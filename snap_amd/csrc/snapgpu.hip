@@ -834,6 +834,7 @@ extern "C" int snapgpu_create(const snapgpu_index_view *idx, const snapgpu_param
         CRCHK(hipMalloc((void **)&ctx->d_se_ctl, 256), SNAPGPU_E_NOMEM);
     }
     CRCHK(hipMalloc((void **)&ctx->d_work, 256), SNAPGPU_E_NOMEM);
+    CRCHK(hipMemsetAsync(ctx->d_work, 0, 256, ctx->stream), SNAPGPU_E_NODEVICE);
     CRCHK(hipMalloc((void **)&ctx->d_counters, sizeof(snapgpu_counters)), SNAPGPU_E_NOMEM);
     CRCHK(hipMemsetAsync(ctx->d_counters, 0, sizeof(snapgpu_counters), ctx->stream), SNAPGPU_E_NODEVICE);
     CRCHK(hipStreamSynchronize(ctx->stream), SNAPGPU_E_NODEVICE);
@@ -1595,13 +1596,14 @@ static int check_read_offsets(snapgpu_ctx *ctx, const uint64_t *offsets, size_t 
 
 // What a host-pointer align call reports once its results are back: a pair (pairs != NULL) that the per-wave pools could not hold, a read whose
 // secondary candidates outgrew their list, and secondary results cut at the caller's strides.
+static const char *const POOL_OVERFLOW_MSG = "a read pair needed more candidate entries than the per-wave pools hold (the reference would grow its buffers or ask for -mcp); its result is flagged";
 static int scan_results(snapgpu_ctx *ctx, uint32_t n, const snapgpu_paired_result *pairs, const uint32_t *n_secondary, uint32_t secondary_stride,
                         const uint32_t *n_single_secondary, uint32_t single_stride)
 {
     bool truncated = false;
     for (uint32_t i = 0; i < n; i++) {
         if (pairs && (pairs[i].flags & SNAPGPU_PAIR_POOL_OVERFLOW))
-            return fail(ctx, SNAPGPU_E_UNSUPPORTED, "a read pair needed more candidate entries than the per-wave pools hold (the reference would grow its buffers or ask for -mcp); its result is flagged");
+            return fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG);
         if (!pairs && n_secondary && n_secondary[i] == 0xFFFFFFFFu) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "a read produced more secondary candidates than 2 * (seeds + 1) * max_hits");
         if (n_secondary && n_secondary[i] > secondary_stride) truncated = true;
         if (n_single_secondary && (uint64_t)n_single_secondary[2 * (size_t)i] + n_single_secondary[2 * (size_t)i + 1] > single_stride) truncated = true;
@@ -1869,6 +1871,7 @@ static int launch_paired(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, cons
     a.bases = (const uint8_t *)d_bases; a.quals = (const uint8_t *)d_quals; a.offsets = (const uint64_t *)d_offsets;
     a.n_pairs = n; a.primary = (snapgpu_paired_result *)d_primary; a.first_alt = (snapgpu_paired_result *)d_first_alt;
     a.work_counter = ctx->d_work; a.counters = ctx->d_counters;
+    a.front_clip = so ? nullptr : ctx->clip_front; a.data_len = so ? nullptr : ctx->clip_len; a.skip = so ? nullptr : ctx->clip_skip;      // (snapgpu_align_sam_paired: the batch is unclipped)
     HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
     if (const int frc = ensure_flag_list(ctx, n)) return frc;
     uint32_t blocks = paired_grid_share(ctx, (so ? ctx->p_sec_slots : ctx->p_wave_slots) / 4);
@@ -1879,6 +1882,15 @@ static int launch_paired(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, cons
         if (so) {                              // secondary results: the 192-position register variant, or the LDS form for everything longer
             if (ctx->p_ag_variant == 3) snapgpu_launch_paired_sec_3(&x, nblocks, lds, s);
             else snapgpu_launch_paired_sec_0(&x, nblocks, lds, s);
+            return;
+        }
+        if (x.front_clip) {                    // an unclipped batch with its clip windows (snapgpu_align_sam_paired)
+            switch (ctx->p_ag_variant) {
+            case 3:  snapgpu_launch_paired_clip_3(&x, nblocks, lds, s); break;
+            case 4:  snapgpu_launch_paired_clip_4(&x, nblocks, lds, s); break;
+            case 6:  snapgpu_launch_paired_clip_6(&x, nblocks, lds, s); break;
+            default: snapgpu_launch_paired_clip_0(&x, nblocks, lds, s); break;
+            }
             return;
         }
         switch (ctx->p_ag_variant) {           // one translation unit per affine-gap variant (paired_k.hip), compiled in parallel
@@ -1901,6 +1913,7 @@ static int launch_paired(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, cons
     b.secondary = a.secondary; b.sec_out_stride = a.sec_out_stride; b.n_secondary = a.n_secondary;
     b.single_secondary = a.single_secondary; b.ssec_out_stride = a.ssec_out_stride; b.n_single_secondary = a.n_single_secondary;
     b.bases = a.bases; b.quals = a.quals; b.offsets = a.offsets; b.n_pairs = n; b.primary = a.primary; b.first_alt = a.first_alt;
+    b.front_clip = a.front_clip; b.data_len = a.data_len; b.skip = a.skip;
     b.counters = a.counters; b.is_replay = 1;
     a.is_replay = 0;
     a.dbg_flag_every = b.dbg_flag_every = 0;
@@ -1931,7 +1944,14 @@ static int launch_paired(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, cons
         uint32_t slots = so ? ctx->p_sec_big_slots : ctx->p_big_slots;
         if (slots > PEXACT_SLOTS) slots = PEXACT_SLOTS;
         if (so) { if (ctx->p_ag_variant == 3) snapgpu_launch_paired_sec_exact_3(&x, slots / 4, lds, s); else snapgpu_launch_paired_sec_exact_0(&x, slots / 4, lds, s); }
-        else launch_paired_exact(ctx->p_ag_variant, &x, slots / 4, lds, s);
+        else if (x.front_clip) {
+            switch (ctx->p_ag_variant) {
+            case 3:  snapgpu_launch_paired_clip_exact_3(&x, slots / 4, lds, s); break;
+            case 4:  snapgpu_launch_paired_clip_exact_4(&x, slots / 4, lds, s); break;
+            case 6:  snapgpu_launch_paired_clip_exact_6(&x, slots / 4, lds, s); break;
+            default: snapgpu_launch_paired_clip_exact_0(&x, slots / 4, lds, s); break;
+            }
+        } else launch_paired_exact(ctx->p_ag_variant, &x, slots / 4, lds, s);
         HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
     }
 
@@ -1964,28 +1984,35 @@ struct SamfBufs {
 };
 
 // The banded row loops of a batch's records ahead of the records themselves, eight reads to a wavefront (cigar_ag.h: SamfPre, cigar_k.hip:
-// k_samf_dp8): fills a.pre / a.pre_stride / a.pre_counter and launches the kernel on the call's stream; the per-read results live in the
+// k_samf_dp8, k_samf_dp8_paired for the mates of a paired batch): fills a.pre / a.pre_stride / a.pre_counter and launches the kernel on the call's stream; the per-read results live in the
 // call's Stage.  SNAPGPU_SAMF_DP8=0 (measurement knob) or reads beyond 400 bp: nothing is launched and a.pre stays NULL.
 static bool samf_dp8_enabled() { static int v = -1; if (v < 0) { const char *e = getenv("SNAPGPU_SAMF_DP8"); v = e ? (atoi(e) != 0 ? 1 : 0) : 1; } return v == 1; }
-static int launch_samf_dp8(snapgpu_ctx *ctx, SamFieldsArgs &a, Stage &st)
+static uint32_t samf_n_reads(const SamFieldsArgs &a) { return a.n; }
+static uint32_t samf_n_reads(const SamFieldsPairedArgs &a) { return 2 * a.n_pairs; }                 // (one SamfPre per mate)
+static void samf_dp8_kernel(const SamFieldsArgs &a, uint32_t blocks, size_t lds, hipStream_t s) { snapgpu_launch_samf_dp8(&a, blocks, lds, s); }
+static void samf_dp8_kernel(const SamFieldsPairedArgs &a, uint32_t blocks, size_t lds, hipStream_t s) { snapgpu_launch_samf_dp8_paired(&a, blocks, lds, s); }
+template <class A>
+static int launch_samf_dp8(snapgpu_ctx *ctx, A &a, Stage &st)
 {
-    a.pre = nullptr; a.pre_stride = 0; a.pre_counter = ctx->d_work + 2;
-    if (!samf_dp8_enabled() || !a.use_affine_gap || a.RL > 400 || a.n == 0) return SNAPGPU_OK;
-    // Best effort (a.pre == NULL is a valid mode: k_sam_fields then runs the row loops itself): not beyond the 64 KiB of LDS per workgroup that k_sam_fields is
+    const uint32_t n = samf_n_reads(a);
+    a.pre = nullptr; a.pre_stride = 0; a.pre_counter = ctx->d_work + 2; a.pre_valid = ctx->d_work + 8;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_work + 8, 0, 4, st.s), SNAPGPU_E_LAUNCH);          // (snapgpu_debug_samf_pre_valid: 0 when nothing is launched)
+    if (!samf_dp8_enabled() || !a.use_affine_gap || a.RL > 400 || n == 0) return SNAPGPU_OK;
+    // Best effort (a.pre == NULL is a valid mode: the field kernel then runs the row loops itself): not beyond the 64 KiB of LDS per workgroup that k_sam_fields is
     // held to, not beyond a bounded pre-buffer (5 - 13 KB per read: a fraction of what is free, 12 GiB at most), and an allocation that fails is not an error.
     const size_t stride = samf_pre_stride(a.RL);
     const size_t lds = 4 * snapgpu_samf_dp8_lds_per_wave(a.RL);
     if (lds > 64 * 1024) return SNAPGPU_OK;
-    const size_t want = (size_t)a.n * stride;
+    const size_t want = (size_t)n * stride;
     if (want > ((size_t)12 << 30)) return SNAPGPU_OK;
     a.pre = st.scratch(want, false);
     if (!a.pre) return SNAPGPU_OK;
     a.pre_stride = stride;
     uint32_t per_cu = (uint32_t)((size_t)160 * 1024 / (lds ? lds : 1)); if (per_cu > 8) per_cu = 8; if (per_cu < 1) per_cu = 1;
     uint32_t blocks = (uint32_t)ctx->num_cus * per_cu;
-    const uint32_t need = (a.n + 31) / 32; if (blocks > need) blocks = need;
+    const uint32_t need = (n + 31) / 32; if (blocks > need) blocks = need;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_work + 2, 0, 4, st.s), SNAPGPU_E_LAUNCH);
-    snapgpu_launch_samf_dp8(&a, blocks, lds, st.s);
+    samf_dp8_kernel(a, blocks, lds, st.s);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
     return SNAPGPU_OK;
 }
@@ -1995,8 +2022,9 @@ static int samf_kernels(snapgpu_ctx *ctx, SamFieldsArgs &a, const SamfGeom &g, S
     snapgpu_launch_sam_fields(&a, g.blocks, g.lds, st.s);
     return SNAPGPU_OK;
 }
-static int samf_kernels(snapgpu_ctx *, SamFieldsPairedArgs &a, const SamfGeom &g, Stage &st)
+static int samf_kernels(snapgpu_ctx *ctx, SamFieldsPairedArgs &a, const SamfGeom &g, Stage &st)
 {
+    if (const int rc = launch_samf_dp8(ctx, a, st)) return rc;
     snapgpu_launch_sam_fields_paired(&a, g.blocks, g.lds, st.s);
     return SNAPGPU_OK;
 }
@@ -2456,6 +2484,106 @@ extern "C" int snapgpu_sam_fields_paired(snapgpu_ctx *ctx, uint32_t n_pairs, con
     if (st.rc) return st.rc;
     if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
     return finish_timing(ctx);
+}
+
+// device-pointer form of snapgpu_sam_fields_paired: reads, clipping and results already in HBM (e.g. right after
+// snapgpu_align_paired_device), outputs left in HBM.  max_read_len sizes the per-wave LDS rows and the scratch slab.
+extern "C" int snapgpu_sam_fields_paired_device(snapgpu_ctx *ctx, uint32_t n_pairs, uint32_t max_read_len, const void *d_bases, const void *d_quals,
+                                                const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_results, int use_m,
+                                                void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
+                                                void *d_n_ops, void *d_nm, void *d_rnext, void *d_pnext, void *d_tlen, void *d_first_written,
+                                                void *d_reference_history_dependent, void *stream)
+{
+    const char *who = "snapgpu_sam_fields_paired_device";
+    if (!ctx || (n_pairs && (!d_bases || !d_quals || !d_offsets || !d_front_clip || !d_data_len || !d_results || !d_flag || !d_contig || !d_pos || !d_mapq ||
+                             !d_ops || !d_n_ops || !d_nm || !d_rnext || !d_pnext || !d_tlen || !d_first_written || !d_reference_history_dependent)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired_device: null argument");
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired_device: ops_stride must be at least 3");
+    if (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired_device: max_read_len out of range");
+    if (n_pairs == 0) return SNAPGPU_OK;
+    if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired_device: too many pairs");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    SamfGeom g;
+    int rc = samf_geometry(ctx, who, max_read_len < 64 ? 64 : max_read_len, n_pairs, &g);
+    if (rc) return rc;
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    const SamfBufs b{d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_results, d_flag, d_contig, d_pos, d_mapq, d_ops, d_n_ops, d_nm,
+                     d_reference_history_dependent};
+    SamFieldsPairedArgs a; a.n_pairs = n_pairs;
+    a.rnext = (int32_t *)d_rnext; a.pnext = (int64_t *)d_pnext; a.tlen = (int64_t *)d_tlen; a.first_written = (int32_t *)d_first_written;
+    if ((rc = launch_sam_fields(ctx, a, g, b, 2 * n_pairs, ops_stride, use_m, st))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);           // (the scratch slab and the pre-pass records go back to the pool on return)
+    return finish_timing(ctx);
+}
+
+// The paired-end path of a SAM writer in one call, device-resident in between: ONE upload of the batch (the unclipped mates, Read::clip's
+// outcome, which pairs the aligner is given), ChimericPairedEndAligner::align over the clip windows with its second-pass and exact-replay
+// launches, the SAM fields of both mates of every pair from the results where the align kernels left them, one download.  What
+// snapgpu_align_paired on a clipped copy of the reads, a host scatter and snapgpu_sam_fields_paired do with two uploads of the reads and a
+// round trip of the results.
+extern "C" int snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                        const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                        snapgpu_paired_result *results, snapgpu_paired_result *first_alt,
+                                        int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                                        int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
+                                        int32_t *reference_history_dependent)
+{
+    const char *who = "snapgpu_align_sam_paired";
+    if (!ctx || (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !flag || !contig || !pos || !mapq || !ops || !n_ops ||
+                             !nm || !rnext || !pnext || !tlen || !first_written || !reference_history_dependent)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: null argument");
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: ops_stride must be at least 3");
+    if (!ctx->paired || ctx->secondary)
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: a paired-end context without secondary results is needed (snapgpu_enable_paired, no snapgpu_enable_secondary)");
+    if (n_pairs == 0) return SNAPGPU_OK;
+    if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: too many pairs");
+    const uint32_t n = 2 * n_pairs;
+    SamfGeom g; uint32_t RL;
+    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
+        if (!skip[i >> 1] && (uint32_t)data_len[i] > ctx->params.max_read_len)
+            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (IntersectingPairedEndAligner.cpp:361-365)");
+        return (int)SNAPGPU_OK;
+    });
+    if (rc) return rc;
+    const PairedInFlight in_flight(ctx); ctx->paired_share = in_flight.share;      // (paired_grid_share: this call's launches ask for their share of the chip)
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    if ((rc = samf_geometry(ctx, who, RL, n_pairs, &g))) return rc;
+    Stage st(ctx, ctx->stream);
+    const size_t n4 = (size_t)n * 4, n8 = (size_t)n * 8, rb = (size_t)n_pairs * sizeof(snapgpu_paired_result);
+    const void *d_bases = bases, *d_quals = quals, *d_offsets = offsets;
+    stage_reads(st, d_bases, d_quals, d_offsets, n);
+    const void *d_front_clip = st.in(front_clip, n4), *d_data_len = st.in(data_len, n4), *d_skip = st.in(skip, n_pairs);
+    void *d_results = st.out(results, rb), *d_first_alt = st.opt_out(first_alt, rb);      // (results == NULL: a device-only buffer)
+    uint32_t h_overflowed = 0;
+    uint32_t *d_overflowed = st.out(&h_overflowed, 4);
+    SamfBufs b{d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_results,
+               st.out(flag, n4), st.out(contig, n4), st.out(pos, n8), st.out(mapq, n4), st.out(ops, n4 * ops_stride), st.out(n_ops, n4), st.out(nm, n4), nullptr};
+    SamFieldsPairedArgs a; a.n_pairs = n_pairs;
+    a.rnext = st.out(rnext, n4); a.pnext = st.out(pnext, n8); a.tlen = st.out(tlen, n8); a.first_written = st.out(first_written, (size_t)n_pairs * 4);
+    b.stale = st.out(reference_history_dependent, n4);
+    if (st.rc) return st.rc;
+    ctx->clip_front = (const int32_t *)d_front_clip; ctx->clip_len = (const int32_t *)d_data_len; ctx->clip_skip = (const uint8_t *)d_skip;
+    rc = launch_paired(ctx, n_pairs, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s);
+    ctx->clip_front = ctx->clip_len = nullptr; ctx->clip_skip = nullptr;
+    if (rc || (rc = finish_timing(ctx))) return rc;                // (the align launches' own hipEvent time, before the events are reused)
+    // what snapgpu_align_paired reports for a pool overflow, without the results on the host: the pairs still flagged after the second pass, counted
+    HIPCHK(ctx, hipMemsetAsync(d_overflowed, 0, 4, st.s), SNAPGPU_E_LAUNCH);
+    snapgpu_launch_collect_flagged((snapgpu_paired_result *)d_results, n_pairs, ctx->d_flag_list, d_overflowed, 0, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
+    if ((rc = finish_timing(ctx))) return rc;
+    return h_overflowed ? fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG) : SNAPGPU_OK;
+}
+
+// Diagnostics (not part of the drop-in surface): how many SamfPre records the row-loop pre-pass (k_samf_dp8 / k_samf_dp8_paired) of the context's
+// LAST SAM-field launch left valid -- 0 when that launch ran without a pre-pass (SNAPGPU_SAMF_DP8=0, reads beyond 400 bp, no affine gap).
+extern "C" int snapgpu_debug_samf_pre_valid(snapgpu_ctx *ctx, uint64_t *n_valid) {
+    if (!ctx || !n_valid) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_debug_samf_pre_valid: null argument");
+    uint32_t v = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    HIPCHK(ctx, hipMemcpy(&v, ctx->d_work + 8, 4, hipMemcpyDeviceToHost), SNAPGPU_E_LAUNCH);
+    *n_valid = v;
+    return SNAPGPU_OK;
 }
 
 // BaseAligner::AlignRead for a batch, with (n_secondary != NULL: snapgpu_enable_secondary) or without secondary results.  host: every pointer
