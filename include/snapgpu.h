@@ -29,6 +29,8 @@
  *   snapgpu_align_sam_paired
  *       ChimericPairedEndAligner::align as PairedAlignerContext::runIterationThread calls it  SNAPLib/PairedAligner.cpp:640-790 (the
  *       useful-read test :680-682), followed by SimpleReadWriter::writePairs  SNAPLib/ReadWriter.cpp:345-520
+ *   snapgpu_align_sam_single_records
+ *       AlignRead with secondary results, finalizeSecondaryResults, writeReads per result  SNAPLib/SingleAligner.cpp:250-325, BaseAligner.cpp:2423-2553
  *   snapgpu_sam_fields_single
  *       SimpleReadWriter::writeReads            SNAPLib/ReadWriter.cpp:170-330
  *       SAMFormat::writeRead / createSAMLine / computeCigarString  SNAPLib/SAM.cpp:1898-2352 / 1424-1572 / 2595-2766
@@ -67,6 +69,7 @@ extern "C" {
 #define SNAPGPU_E_NOMEM        -4
 #define SNAPGPU_E_LAUNCH       -5   /* kernel launch or execution failed                 */
 #define SNAPGPU_W_SECONDARY_TRUNCATED 1 /* some read has more secondary results than the caller's stride: see snapgpu_align_single_secondary */
+#define SNAPGPU_W_RECORDS_TRUNCATED 2   /* the batch has more SAM records than the caller's record capacity: see snapgpu_align_sam_single_records */
 
 /* mirrors enum AlignmentResult, SNAPLib/AlignmentResult.h:33 */
 enum { SNAPGPU_NotFound = 0, SNAPGPU_SingleHit = 1, SNAPGPU_MultipleHits = 2 };
@@ -459,13 +462,63 @@ int  snapgpu_sam_fields_single_device(snapgpu_ctx *ctx, uint32_t n, uint32_t max
  *                             means the first-ALT result is not computed into a caller-visible buffer)
  *   flag .. reference_history_dependent   as snapgpu_sam_fields_single (a cigar that does not fit ops_stride: n_ops -1, nm -2)
  * The context must be a plain single-end one (no snapgpu_enable_secondary / _paired).  With secondary results, -ae or ALT records to
- * write, use the two calls it replaces.
+ * write, use snapgpu_align_sam_single_records below: the same one upload and one download, for every record of every read.
  */
 int  snapgpu_align_sam_single(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
                               const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
                               snapgpu_single_result *results, snapgpu_single_result *first_alt,
                               int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
                               int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent);
+
+/*
+ * Single-end reads to ALL their SAM records in ONE call: what `snap-aligner single` writes with -om / -omax / -mpc (secondary results), -ea
+ * (first-ALT records) and -ae (alignment adjustment) -- AlignRead with secondary results and finalizeSecondaryResults (BaseAligner.cpp:2423-2553),
+ * then SimpleReadWriter::writeReads for every result of the read (SingleAligner.cpp:250-325).  One upload of the batch, one download of the
+ * records; results, the record list and the SAM-field kernels stay in HBM in between, and no per-record copy of a read is made anywhere.
+ *   ctx                 a single-end context, with or without snapgpu_enable_secondary (not snapgpu_enable_paired).  With secondary results
+ *                       the context's adjust_alignments (-ae) is honoured; without them adjust_primary != 0 asks for -ae's adjustment of the
+ *                       primary, all that finalizeSecondaryResults has to adjust then (BaseAligner.cpp:2444-2452).  adjust_primary != 0 on a
+ *                       context whose secondary results were enabled without adjust_alignments is SNAPGPU_E_INVALID.
+ *   bases .. use_m      exactly as snapgpu_align_sam_single: the UNCLIPPED reads, Read::clip's outcome, skip[i] != 0 = not given to the aligner
+ *   results / first_alt / secondary (secondary_stride entries per read) / n_secondary
+ *                       optional outputs (NULL: not wanted), as snapgpu_align_single_secondary fills them; read i's secondary results beyond
+ *                       secondary_stride are not in `secondary`, but all of them are in the record list.  A context without secondary
+ *                       results leaves `secondary` alone and zeroes n_secondary.
+ * The records, in the order the reference writes them: for read i its primary, then its secondary results in the order
+ * finalizeSecondaryResults leaves them, then its first-ALT result when the aligner produced one (SingleAligner.cpp:312: altAwareness and
+ * status != NotFound, which params.emit_alt_alignments, -ea, governs).  Read i's records are rec_begin[i] .. rec_begin[i + 1].
+ *   record_capacity     records the per-record arrays have room for
+ *   n_records           out: records the batch HAS (= rec_begin[n])
+ *   rec_begin           [n + 1] out
+ *   rec_read, rec_kind  [record_capacity] out: the read a record belongs to; 0 primary, 1 secondary, 2 first-ALT
+ *   flag .. reference_history_dependent   [record_capacity] out (ops: ops_stride per record), as snapgpu_sam_fields_single, with 0x100 set in
+ *                       the flag of every record that is not its read's primary (createSAMLine, SAM.cpp:1477-1479).  A cigar that does not fit
+ *                       ops_stride: n_ops -1, nm -2.
+ * Returns SNAPGPU_OK, or SNAPGPU_W_RECORDS_TRUNCATED (> 0) when *n_records > record_capacity: the first record_capacity records are then
+ * exactly what a call with enough room writes there (rec_begin and the optional result arrays are complete), and the caller calls again.
+ * How many secondary results a read has never concerns the caller: the library's first launch has room for 8 per read (or secondary_stride)
+ * and the reads that have more -- they are known from n_secondary -- are run again on their own, inside the call.
+ * Under -ae a read the reader clipped whose alignment reaches the end of its contig is refused (SNAPGPU_E_UNSUPPORTED for the call), not
+ * answered differently: see the LIMITATION of snapgpu_adjust_alignments.
+ */
+int  snapgpu_align_sam_single_records(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                      const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                      snapgpu_single_result *results, snapgpu_single_result *first_alt,
+                                      snapgpu_single_result *secondary, uint32_t secondary_stride, uint32_t *n_secondary,
+                                      uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, uint32_t *rec_read, uint8_t *rec_kind,
+                                      int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                                      int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent);
+
+/* Device-pointer form of snapgpu_align_sam_single_records: the reads, Read::clip's outcome, skip and every output array in HBM (d_results,
+ * d_first_alt, d_secondary, d_n_secondary may be NULL); n_records stays a host word.  max_read_len >= the longest unclipped read of the batch,
+ * as in snapgpu_sam_fields_single_device.  Synchronous on `stream` (NULL: the context's): the record count is read back inside the call.
+ * n == 0 writes d_rec_begin[0] = 0 (when d_rec_begin is given), like the host form. */
+int  snapgpu_align_sam_single_records_device(snapgpu_ctx *ctx, uint32_t n, uint32_t max_read_len, const void *d_bases, const void *d_quals,
+                                             const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_skip, int use_m,
+                                             int adjust_primary, void *d_results, void *d_first_alt, void *d_secondary, uint32_t secondary_stride,
+                                             void *d_n_secondary, uint64_t record_capacity, uint64_t *n_records, void *d_rec_begin, void *d_rec_read,
+                                             void *d_rec_kind, void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
+                                             void *d_n_ops, void *d_nm, void *d_reference_history_dependent, void *stream);
 
 /*
  * The paired-end writer: for the primary PairedAlignmentResult of each pair, the computed fields of BOTH SAM records -- what

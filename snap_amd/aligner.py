@@ -43,6 +43,8 @@ def load_library():
     return _lib
 
 
+W_RECORDS_TRUNCATED = 2          # SNAPGPU_W_RECORDS_TRUNCATED (include/snapgpu.h)
+
 EXPORTED_SYMBOLS = [
     "snapgpu_abi_version", "snapgpu_last_error", "snapgpu_default_params", "snapgpu_create",
     "snapgpu_destroy", "snapgpu_create_from_directory", "snapgpu_device_count", "snapgpu_create_replica", "snapgpu_broadcast_index", "snapgpu_default_paired_params", "snapgpu_enable_paired",
@@ -51,7 +53,7 @@ EXPORTED_SYMBOLS = [
     "snapgpu_align_single_device", "snapgpu_get_counters", "snapgpu_kernel_time",
     "snapgpu_enable_secondary", "snapgpu_align_single_secondary", "snapgpu_align_single_secondary_device",
     "snapgpu_align_paired_secondary", "snapgpu_align_paired_secondary_device",
-    "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_paired", "snapgpu_create_replica_with_params",
+    "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_single_records", "snapgpu_align_sam_single_records_device", "snapgpu_align_sam_paired", "snapgpu_create_replica_with_params",
     "snapgpu_default_index_build_params", "snapgpu_index_build", "snapgpu_index_build_from_fasta", "snapgpu_index_build_shaped",
     "snapgpu_index_build_from_fasta_shaped", "snapgpu_built_index_view",
     "snapgpu_built_index_save", "snapgpu_built_index_stats", "snapgpu_built_index_destroy",
@@ -352,6 +354,70 @@ class BaseAligner:
             C.c_int(1 if use_m else 0), ptr(results), ptr(first_alt), ptr(flag), ptr(contig), ptr(pos), ptr(mapq), ptr(ops),
             C.c_uint32(ops_stride), ptr(n_ops), ptr(nm), ptr(stale)), "snapgpu_align_sam_single")
         return results, first_alt, dict(flag=flag, contig=contig, pos=pos, mapq=mapq, ops=ops, n_ops=n_ops, nm=nm, stale=stale)
+
+    def alignSamRecords(self, bases, quals, offsets, front_clip, data_len, skip, use_m: bool = False, ops_stride: int = 64,
+                        adjust_primary: bool = False, capacity: int | None = None, secondary_stride: int = 0, grow: bool = True):
+        """Single-end reads to ALL their SAM records in one call (snapgpu_align_sam_single_records): -om / -omax / -mpc through
+        enable_secondary on this context, -ae through its adjust argument (or adjust_primary on a context without secondary results), -ea
+        through params.emit_alt_alignments.  Inputs as alignSam.  capacity: records the per-record arrays have room for (default: one
+        and a half per read); grow: call again with the count the library asks for when that was too few -- otherwise the truncated
+        answer is returned with truncated=True.  secondary_stride > 0: also return the strided secondary results.
+        Returns dict(n_records, truncated, rec_begin, rec_read, rec_kind, flag, contig, pos, mapq, ops, n_ops, nm, stale, results,
+        first_alt, n_secondary[, secondary]); the per-record arrays are cut to the records that were written."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1); quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        front_clip = np.ascontiguousarray(front_clip, dtype=np.int32); data_len = np.ascontiguousarray(data_len, dtype=np.int32)
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        n = offsets.size - 1
+        cap = int(capacity) if capacity is not None else n + n // 2 + 16
+        results = np.zeros(n, dtype=RESULT_DTYPE); first_alt = np.zeros(n, dtype=RESULT_DTYPE); n_secondary = np.zeros(n, np.uint32)
+        secondary = np.zeros((n, secondary_stride), dtype=RESULT_DTYPE) if secondary_stride else None
+        rec_begin = np.zeros(n + 1, np.uint64)
+        f = self.lib.snapgpu_align_sam_single_records
+        f.argtypes = ([C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint64] +
+                      [C.c_void_p] * 9 + [C.c_uint32] + [C.c_void_p] * 3)
+        while True:
+            rec_read = np.zeros(cap, np.uint32); rec_kind = np.zeros(cap, np.uint8)
+            flag = np.zeros(cap, np.int32); contig = np.zeros(cap, np.int32); pos = np.zeros(cap, np.int64); mapq = np.zeros(cap, np.int32)
+            ops = np.zeros((cap, ops_stride), dtype=np.uint32); n_ops = np.zeros(cap, np.int32); nm = np.zeros(cap, np.int32); stale = np.zeros(cap, np.int32)
+            n_rec = C.c_uint64(0)
+            rc = f(self.handle, n, ptr(bases), ptr(quals), ptr(offsets), ptr(front_clip), ptr(data_len), ptr(skip), 1 if use_m else 0,
+                   1 if adjust_primary else 0, ptr(results), ptr(first_alt), ptr(secondary) if secondary is not None else None, secondary_stride,
+                   ptr(n_secondary), cap, C.addressof(n_rec), ptr(rec_begin), ptr(rec_read), ptr(rec_kind), ptr(flag), ptr(contig), ptr(pos),
+                   ptr(mapq), ptr(ops), ops_stride, ptr(n_ops), ptr(nm), ptr(stale))
+            if rc == W_RECORDS_TRUNCATED and grow:
+                cap = int(n_rec.value)
+                continue
+            if rc != W_RECORDS_TRUNCATED:
+                self._check(rc, "snapgpu_align_sam_single_records")
+            break
+        m = min(int(n_rec.value), cap)
+        out = dict(n_records=int(n_rec.value), truncated=rc == W_RECORDS_TRUNCATED, rec_begin=rec_begin, rec_read=rec_read[:m], rec_kind=rec_kind[:m],
+                   flag=flag[:m], contig=contig[:m], pos=pos[:m], mapq=mapq[:m], ops=ops[:m], n_ops=n_ops[:m], nm=nm[:m], stale=stale[:m],
+                   results=results, first_alt=first_alt, n_secondary=n_secondary)
+        if secondary is not None:
+            out["secondary"] = secondary
+        return out
+
+    def alignSamRecords_device(self, n: int, max_read_len: int, d_bases: int, d_quals: int, d_offsets: int, d_front_clip: int, d_data_len: int, d_skip: int,
+                               capacity: int, d_rec_begin: int, d_rec_read: int, d_rec_kind: int, d_flag: int, d_contig: int, d_pos: int, d_mapq: int,
+                               d_ops: int, ops_stride: int, d_n_ops: int, d_nm: int, d_stale: int, use_m: bool = False, adjust_primary: bool = False,
+                               d_results: int = 0, d_first_alt: int = 0, d_secondary: int = 0, secondary_stride: int = 0, d_n_secondary: int = 0, stream: int = 0):
+        """Device-pointer form of alignSamRecords (snapgpu_align_sam_single_records_device): the reads, Read::clip's outcome, skip and every
+        output array already in HBM (the result arrays are optional: 0).  Synchronous on `stream` (0: the context's).
+        Returns (n_records, truncated)."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        f = self.lib.snapgpu_align_sam_single_records_device
+        f.argtypes = ([C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p, C.c_uint64] +
+                      [C.c_void_p] * 9 + [C.c_uint32] + [C.c_void_p] * 4)
+        n_rec = C.c_uint64(0)
+        rc = f(self.handle, n, max_read_len, vp(d_bases), vp(d_quals), vp(d_offsets), vp(d_front_clip), vp(d_data_len), vp(d_skip), 1 if use_m else 0,
+               1 if adjust_primary else 0, vp(d_results), vp(d_first_alt), vp(d_secondary), secondary_stride, vp(d_n_secondary), capacity, C.addressof(n_rec),
+               vp(d_rec_begin), vp(d_rec_read), vp(d_rec_kind), vp(d_flag), vp(d_contig), vp(d_pos), vp(d_mapq), vp(d_ops), ops_stride, vp(d_n_ops), vp(d_nm),
+               vp(d_stale), vp(stream))
+        if rc != W_RECORDS_TRUNCATED:
+            self._check(rc, "snapgpu_align_sam_single_records_device")
+        return int(n_rec.value), rc == W_RECORDS_TRUNCATED
 
     def samFieldsPaired(self, bases, quals, offsets, front_clip, data_len, results, use_m: bool = False, ops_stride: int = 64):
         """SAMFormat::writePairs + fillMateInfo up to the point of printing (see snapgpu_sam_fields_paired).  offsets has 2 n + 1

@@ -57,6 +57,71 @@ struct SamFieldsPairedArgs {
     uint32_t *pre_valid;
 };
 
+// snapgpu_align_sam_single_records: the records of a batch are a list over its reads (sam_records.h).  Record r belongs to read rec_read[r];
+// it is the read's primary (kind 0), its k-th secondary result (kind 1, k = r - rec_begin[read] - 1) or its first-ALT result (kind 2), read
+// where the align kernels left them: no per-record copy of a read or of a result exists.
+#define SAMREC_CHUNK 1024u          // reads per wavefront tile of the list's scan (sam_records.h)
+#define SAMREC_PRIMARY 0
+#define SAMREC_SECONDARY 1
+#define SAMREC_FIRST_ALT 2
+struct SamRecSrc {
+    const snapgpu_single_result *primary; const snapgpu_single_result *first_alt;      // [n reads]
+    const snapgpu_single_result *secondary; uint32_t sec_stride;                        // [n reads * sec_stride]: the align launch's strided output
+    const snapgpu_single_result *sec_ovf; uint32_t ovf_stride;                          // [n_overflow * ovf_stride]: the rerun of the reads that outgrew sec_stride
+    const uint32_t *sec_slot;                                                           // [n reads] row of sec_ovf, or 0xFFFFFFFF: the read's row of `secondary`
+    const uint64_t *rec_begin; const uint32_t *rec_read; const uint8_t *rec_kind;       // [n reads + 1], [records], [records]
+};
+
+// the SAM-field kernels over a record list: SamFieldsArgs with n = records to format, the per-read arrays indexed through src.rec_read and the
+// outputs (and the SamfPre rows) per record
+struct SamFieldsRecArgs {
+    DevIndex ix;
+    AGCParamsPOD prm;
+    uint32_t n, RL, ops_stride, use_m, use_affine_gap;
+    const uint8_t *bases; const uint8_t *quals; const uint64_t *offsets;
+    const int32_t *front_clip; const int32_t *data_len;
+    const snapgpu_single_result *results;                                        // (= src.primary)
+    uint8_t *scratch; uint64_t scratch_stride;
+    uint32_t *work_counter;
+    int32_t *flag; int32_t *contig; int64_t *pos; int32_t *mapq; uint32_t *ops; int32_t *n_ops; int32_t *nm; int32_t *stale;
+    uint8_t *pre; uint64_t pre_stride; uint32_t *pre_counter;
+    uint32_t *pre_valid;
+    SamRecSrc src;
+};
+
+// what the host reads back once the record list is counted
+struct SamRecSummary {
+    unsigned long long total;         // records the batch has
+    uint32_t n_overflow;              // reads with more secondary results than sec_stride
+    uint32_t max_secondary;           // the most any of those has
+    uint32_t cand_overflow;           // a read outgrew its per-wave candidate list (n_secondary 0xFFFFFFFF)
+    uint32_t refused;                 // SAMREC_AE_CLIPPED | SAMREC_RERUN_MISMATCH
+};
+#define SAMREC_AE_CLIPPED 1u        // -ae: a reader-clipped read reaches the end of its contig (adjust.h's limitation)
+#define SAMREC_RERUN_MISMATCH 2u    // the rerun of an overflowed read counted other secondary results than its first pass (cannot happen: the kernels are deterministic)
+
+struct SamRecArgs {
+    DevIndex ix;
+    uint32_t n, n_chunks, alt_aware, check_clipped, max_k;
+    uint64_t cap;                                                                // records the caller has room for
+    const uint64_t *offsets; const int32_t *front_clip; const int32_t *data_len;
+    const uint32_t *n_secondary;                                                 // [n] or NULL (a context without secondary results)
+    uint32_t *count; uint64_t *partial;                                          // [n], [n_chunks]
+    uint32_t *sec_slot; uint32_t *ovf_list;                                      // [n] each (ovf_list: the reads to rerun)
+    SamRecSummary *summary;
+    uint64_t *rec_begin; uint32_t *rec_read; uint8_t *rec_kind;                  // [n + 1], [cap], [cap]: what src's pointers of the same name read
+    SamRecSrc src;
+    // the rerun's batch: the overflowed reads as a batch of their own (offsets / Read::clip's outcome gathered, the bases stay where they are)
+    uint64_t *ovf_offsets; int32_t *ovf_front_clip; int32_t *ovf_data_len;
+    const uint32_t *ovf_n_secondary;                                             // [n_overflow] what the rerun counted
+    uint64_t *clip_off;                                                          // [n] offsets[i] + front_clip[i]: where the adjuster's read starts
+};
+extern "C" void snapgpu_launch_samrec_count(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
+extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hipStream_t s);
+extern "C" void snapgpu_launch_samrec_list(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
+extern "C" void snapgpu_launch_samrec_clip_off(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
+extern "C" void snapgpu_launch_sam_fields_rec(const SamFieldsRecArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+extern "C" void snapgpu_launch_samf_dp8_rec(const SamFieldsRecArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 extern "C" void snapgpu_launch_sam_fields_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 extern "C" void snapgpu_launch_sam_fields(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 extern "C" void snapgpu_launch_samf_dp8(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);

@@ -7,6 +7,7 @@
 #include "sam_fields.h"
 #include "adjust.h"
 #include "cigar_args.h"
+#include "sam_records.h"
 
 __global__ __launch_bounds__(256) void k_cigar_lv(CigarArgs a)
 {
@@ -82,6 +83,7 @@ extern "C" void snapgpu_launch_cigar_ag(const CigarAGArgs *a, uint32_t blocks, s
 #define SAMF_WAVES 8            // waves per SIMD the SAM-field kernels are built for (blocks of four waves: as many blocks per CU).  The kernels are
                                 // latency-bound (8 of 64 lanes in the affine-gap CIGAR): 4.32 M reads/s at 4 (131 VGPRs, rounds 2-3), 5.31 M at 6, 5.73 M at 8 (profiles/r04n)
 #endif
+// (k_sam_fields_rec below is this body over a record list: a change here belongs there too)
 __global__ __launch_bounds__(256, SAMF_WAVES) void k_sam_fields(SamFieldsArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -126,9 +128,61 @@ __global__ __launch_bounds__(256, SAMF_WAVES) void k_sam_fields(SamFieldsArgs a)
     }
 }
 
+// The records of snapgpu_align_sam_single_records: k_sam_fields with record i reaching its read through the record list and its result where the
+// align kernels left it (sam_records.h), and SAM_SECONDARY in the flag of a record that is not its read's primary (createSAMLine's argument,
+// SAM.cpp:1477-1479: writeReads passes i != 0 || !firstIsPrimary).  A kernel of its own, so that k_sam_fields stays the code it was.
+__global__ __launch_bounds__(256, SAMF_WAVES) void k_sam_fields_rec(SamFieldsRecArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int lane = lane_id();
+    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t wave_slot = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_in_block;
+    uint8_t *my = lds + (size_t)wave_in_block * agc_lds_bytes(a.RL);
+    uint8_t *scratch = a.scratch + (size_t)wave_slot * a.scratch_stride;
+    uint8_t *oriented = scratch;                                                      // 2 * RL bytes
+    uint32_t *lv_cells = (uint32_t *)(scratch + ((2 * a.RL + 255) & ~255u));
+    uint8_t *ag_scratch = (uint8_t *)lv_cells + ((lvc_scratch_bytes() + 255) & ~255u);
+    AGCParams prm; prm.match = a.prm.match; prm.sub = a.prm.sub; prm.gap_open = a.prm.gap_open; prm.gap_ext = a.prm.gap_ext;
+    while (true) {
+        uint32_t i = 0;
+        if (lane == 0) i = atomicAdd(a.work_counter, 1u);
+        i = first_u32(i);
+        if (i >= a.n) break;
+        const uint32_t rd = first_u32(a.src.rec_read[i]), kind = first_u32((uint32_t)a.src.rec_kind[i]);
+        const uint64_t b = first_u64(a.offsets[rd]), e = first_u64(a.offsets[rd + 1]);
+        snapgpu_single_result r;                                                  // the fields the writer looks at, as wave-uniform values
+        {
+            const snapgpu_single_result *rp = samrec_result(a.src, rd, kind, (uint32_t)((uint64_t)i - first_u64(a.src.rec_begin[rd])));
+            r.status = (int32_t)first_u32((uint32_t)rp->status); r.direction = (int32_t)first_u32((uint32_t)rp->direction);
+            r.location = (int64_t)first_u64((uint64_t)rp->location); r.orig_location = 0;
+            r.score = (int32_t)first_u32((uint32_t)rp->score); r.score_prior_to_clipping = 0;
+            r.mapq = (int32_t)first_u32((uint32_t)rp->mapq);
+            r.clipping_for_read_adjustment = (int32_t)first_u32((uint32_t)rp->clipping_for_read_adjustment);
+            r.used_affine_gap_scoring = (int32_t)first_u32((uint32_t)rp->used_affine_gap_scoring);
+            r.bases_clipped_before = (int32_t)first_u32((uint32_t)rp->bases_clipped_before);
+            r.bases_clipped_after = (int32_t)first_u32((uint32_t)rp->bases_clipped_after);
+            r.ag_score = 0; r.supplementary = (int32_t)first_u32((uint32_t)rp->supplementary); r.seed_offset = 0; r.match_probability = 0.0;
+            r.probability_all_candidates = 0.0; r.popular_seeds_skipped = 0; r.reserved = 0;
+        }
+        uint32_t *ops = a.ops + (size_t)i * a.ops_stride;
+        const int F0 = (int)first_u32((uint32_t)a.front_clip[rd]), D0 = (int)first_u32((uint32_t)a.data_len[rd]);
+        const SamfPre *pre = a.pre ? (const SamfPre *)(a.pre + (size_t)i * a.pre_stride) : nullptr;
+        const SamFieldsOut o = sam_fields_single_item(a.ix, prm, a.use_affine_gap != 0, a.use_m != 0, a.bases + b, a.quals + b, (int)(e - b), F0, D0, r,
+                                                      my, a.RL, oriented, lv_cells, ag_scratch, ops, (int)a.ops_stride, false, pre);
+        if (lane == 0) {
+            a.flag[i] = o.flag | (kind != SAMREC_PRIMARY ? 0x100 : 0); a.contig[i] = o.contig; a.pos[i] = o.pos; a.mapq[i] = o.mapq; a.n_ops[i] = o.n_ops; a.nm[i] = o.nm; a.stale[i] = o.stale;
+        }
+        WAVE_SYNC();
+    }
+}
+
 extern "C" void snapgpu_launch_sam_fields(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
 {
     hipLaunchKernelGGL(k_sam_fields, dim3(blocks), dim3(256), lds_bytes, s, *a);
+}
+extern "C" void snapgpu_launch_sam_fields_rec(const SamFieldsRecArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sam_fields_rec, dim3(blocks), dim3(256), lds_bytes, s, *a);
 }
 
 // ---- the banded row loops of a batch's records, eight reads to a wavefront (cigar_ag.h: SamfPre) -------------------------------------------
@@ -149,6 +203,17 @@ static __device__ __forceinline__ uint32_t samf_dp8_n(const SamFieldsArgs &a) { 
 static __device__ __forceinline__ uint32_t samf_dp8_n(const SamFieldsPairedArgs &a) { return 2u * a.n_pairs; }
 static __device__ __forceinline__ SamfDp8Res samf_dp8_res(const SamFieldsArgs &a, uint32_t r) {
     const snapgpu_single_result *rp = &a.results[r];
+    return SamfDp8Res{rp->status, rp->score, rp->direction, rp->clipping_for_read_adjustment, rp->used_affine_gap_scoring, rp->bases_clipped_before,
+                      rp->bases_clipped_after, (long long)rp->location};
+}
+static __device__ __forceinline__ uint32_t samf_dp8_n(const SamFieldsRecArgs &a) { return a.n; }
+// the read whose bases / clipping item r is formatted from (r itself unless the launch goes through a record list)
+static __device__ __forceinline__ uint32_t samf_dp8_read(const SamFieldsArgs &, uint32_t r) { return r; }
+static __device__ __forceinline__ uint32_t samf_dp8_read(const SamFieldsPairedArgs &, uint32_t r) { return r; }
+static __device__ __forceinline__ uint32_t samf_dp8_read(const SamFieldsRecArgs &a, uint32_t r) { return a.src.rec_read[r]; }
+static __device__ __forceinline__ SamfDp8Res samf_dp8_res(const SamFieldsRecArgs &a, uint32_t r) {
+    const uint32_t i = a.src.rec_read[r];
+    const snapgpu_single_result *rp = samrec_result(a.src, i, (uint32_t)a.src.rec_kind[r], (uint32_t)((uint64_t)r - a.src.rec_begin[i]));
     return SamfDp8Res{rp->status, rp->score, rp->direction, rp->clipping_for_read_adjustment, rp->used_affine_gap_scoring, rp->bases_clipped_before,
                       rp->bases_clipped_after, (long long)rp->location};
 }
@@ -191,8 +256,9 @@ static __device__ __forceinline__ void samf_dp8_run(const A &a, uint8_t *lds)
         SamfPre *pre = (SamfPre *)(a.pre + (size_t)(elig ? r : base) * a.pre_stride);
         if (elig) {
             const SamfDp8Res rp = samf_dp8_res(a, r);
-            rb = a.offsets[r]; U = (int)(a.offsets[r + 1] - rb);
-            const int status = rp.status, score = rp.score, F0 = a.front_clip[r], D0 = a.data_len[r], addF = rp.add_front;
+            const uint32_t rd = samf_dp8_read(a, r);
+            rb = a.offsets[rd]; U = (int)(a.offsets[rd + 1] - rb);
+            const int status = rp.status, score = rp.score, F0 = a.front_clip[rd], D0 = a.data_len[rd], addF = rp.add_front;
             loc = rp.loc; dir = rp.dir;
             const bool ag_branch = a.use_affine_gap != 0 && (rp.used_ag != 0 || score > 0);
             const int front = F0 + addF, dlen = D0 - addF;
@@ -361,6 +427,13 @@ __global__ __launch_bounds__(256) void k_samf_dp8(SamFieldsArgs a)
     samf_dp8_run(a, lds);
 }
 
+// the records of a record list (k_sam_fields_rec hands record r its SamfPre)
+__global__ __launch_bounds__(256) void k_samf_dp8_rec(SamFieldsRecArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    samf_dp8_run(a, lds);
+}
+
 // the 2 * n_pairs mates of a paired batch (k_sam_fields_paired hands mate 2 * i + w its record)
 __global__ __launch_bounds__(256) void k_samf_dp8_paired(SamFieldsPairedArgs a)
 {
@@ -372,6 +445,10 @@ __global__ __launch_bounds__(256) void k_samf_dp8_paired(SamFieldsPairedArgs a)
 extern "C" void snapgpu_launch_samf_dp8(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
 {
     hipLaunchKernelGGL(k_samf_dp8, dim3(blocks), dim3(256), lds_bytes, s, *a);
+}
+extern "C" void snapgpu_launch_samf_dp8_rec(const SamFieldsRecArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_samf_dp8_rec, dim3(blocks), dim3(256), lds_bytes, s, *a);
 }
 extern "C" void snapgpu_launch_samf_dp8_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
 {
@@ -471,4 +548,24 @@ __global__ __launch_bounds__(256) void k_adjust_alignments(AdjustArgs a)
 extern "C" void snapgpu_launch_adjust_alignments(const AdjustArgs *a, uint32_t blocks, hipStream_t s)
 {
     hipLaunchKernelGGL(k_adjust_alignments, dim3(blocks), dim3(256), 0, s, *a);
+}
+
+// ---- the record list of snapgpu_align_sam_single_records (sam_records.h) ---------------------------------------------------------------------
+extern "C" void snapgpu_launch_samrec_count(const SamRecArgs *a, uint32_t blocks, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_samrec_count, dim3(blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samrec_partials, dim3(1), dim3(64), 0, s, *a);
+}
+extern "C" void snapgpu_launch_samrec_list(const SamRecArgs *a, uint32_t blocks, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_samrec_begins, dim3(blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samrec_list, dim3(blocks), dim3(256), 0, s, *a);
+}
+extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_samrec_gather, dim3((m + 256) / 256), dim3(256), 0, s, *a, m);
+}
+extern "C" void snapgpu_launch_samrec_clip_off(const SamRecArgs *a, uint32_t blocks, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_samrec_clip_off, dim3(blocks), dim3(256), 0, s, *a);
 }

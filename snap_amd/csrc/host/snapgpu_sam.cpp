@@ -554,6 +554,18 @@ template <class F> static void with_growing_stride(Work &w, size_t n_rec, F call
     }
 }
 
+// `single` with -om / -omax / -mpc / -ea / -ae: every record of every read from ONE call (snapgpu_align_sam_single_records) -- the batch goes up
+// as it was parsed and the records come down ready to print; no clipped copy, no second call for -ae, no results coming back to be expanded
+// into a record batch and sent up again.  The files are the same bytes either way (tests/test_zz_gpu_sam_single_records.py).
+// SNAPGPU_SAM_SINGLE_FUSED=1 turns it on, =0 (and, for now, unset) keeps the calls it replaces: the one-call path has not been timed against
+// them on the hardware yet (DESIGN.md section 13 says what to measure), and an untimed path does not become the tool's default.
+static bool single_records_path(const Options &o)
+{
+    static const bool fused_on = getenv("SNAPGPU_SAM_SINGLE_FUSED") && atoi(getenv("SNAPGPU_SAM_SINGLE_FUSED")) != 0;
+    return fused_on && !o.paired && (o.om >= 0 || o.ae || o.p.emit_alt_alignments != 0);
+}
+static std::atomic<uint32_t> g_records_per_read_x16(24);        // record capacity of the next call, in sixteenths of a record per read: grows to what batches have needed
+
 // Read::clip and the useless-read filter for a batch, and the reads to align gathered into one buffer: host work that does not need the GPU,
 // done by the parser threads where there are several (the feeder threads' time belongs to the device)
 static void prepare_single(const Options &o, Work &w)
@@ -561,7 +573,7 @@ static void prepare_single(const Options &o, Work &w)
     const Batch &b = w.b;
     const size_t n = b.n();
     w.front_clip.assign(n, 0); w.data_len.assign(n, 0); w.skip.assign(n, 1); w.to_align.clear(); w.ab.clear(); w.aq.clear(); w.ao.assign(1, 0);
-    const bool fused = o.om < 0 && !o.ae;               // gpu_single's one-call path works on the batch itself: nothing to gather
+    const bool fused = (o.om < 0 && !o.ae) || single_records_path(o);      // gpu_single's one-call paths work on the batch itself: nothing to gather
     if (!fused) { w.ab.reserve(b.bases.size()); w.aq.reserve(b.quals.size()); w.ao.reserve(n + 1); }
     w.to_align.reserve(n);
     w.max_len = 0;
@@ -587,6 +599,41 @@ static void gpu_single(const Options &o, FeederCtx &fc, Work &w)
     const size_t n = b.n();
     if (!w.prepared) prepare_single(o, w);            // (the parser threads of the mapped reader have done it already)
     snapgpu_ctx *ctx = ctx_for(o, fc, w.max_len);
+    // ---- secondary results, -ae, -ea: all records in ONE call (snapgpu_align_sam_single_records)
+    if (single_records_path(o) && n > 0) {
+        w.ops_stride = o.ops_stride;
+        std::vector<uint64_t> rec_begin(n + 1);
+        std::vector<uint8_t> kind;
+        std::vector<int32_t> stale;
+        uint64_t n_rec = 0;
+        size_t cap = (n * (size_t)g_records_per_read_x16.load() + 15) / 16 + 16;
+        lap(g_ns_prep);
+        for (;;) {
+            w.rec_read.resize(cap); kind.resize(cap); stale.resize(cap);
+            w.flag.resize(cap); w.contig.resize(cap); w.mapq.resize(cap); w.n_ops.resize(cap); w.nm.resize(cap); w.pos.resize(cap);
+            w.ops.assign(cap * (size_t)w.ops_stride, 0);
+            const int rc2 = snapgpu_align_sam_single_records(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
+                                                             w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, NULL, NULL, NULL, 0, NULL, (uint64_t)cap, &n_rec,
+                                                             rec_begin.data(), w.rec_read.data(), kind.data(), w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(),
+                                                             w.ops.data(), w.ops_stride, w.n_ops.data(), w.nm.data(), stale.data());
+            if (rc2 == SNAPGPU_E_UNSUPPORTED && o.ae && !strncmp(snapgpu_last_error(ctx), "-ae:", 4))
+                die("-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)");
+            if (rc2 == SNAPGPU_W_RECORDS_TRUNCATED) { cap = (size_t)n_rec + (size_t)n_rec / 16; continue; }       // (rare: the capacity follows what batches need)
+            if (rc2 != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_single_records", rc2);
+            bool too_small = false;
+            for (size_t i = 0; i < (size_t)n_rec && !too_small; i++) too_small = w.nm[i] == -2;
+            if (!too_small) break;
+            if (w.ops_stride >= 4096) die("a cigar needs more than 4096 operations");
+            w.ops_stride *= 4;
+        }
+        const size_t nr = (size_t)n_rec;
+        { const uint32_t need = (uint32_t)((nr * 16 + n - 1) / n) + 2; uint32_t cur = g_records_per_read_x16.load(); while (need > cur && !g_records_per_read_x16.compare_exchange_weak(cur, need)) {} }
+        w.rec_read.resize(nr); w.flag.resize(nr); w.contig.resize(nr); w.mapq.resize(nr); w.n_ops.resize(nr); w.nm.resize(nr); w.pos.resize(nr);
+        w.ops.resize(nr * (size_t)w.ops_stride);
+        w.rec_secondary.resize(nr); for (size_t r = 0; r < nr; r++) w.rec_secondary[r] = kind[r] != 0;      // (0x100 is in the flags already)
+        lap(g_ns_align);
+        return;
+    }
     // ---- the common case in ONE call (snapgpu_align_sam_single): no secondary results, no -ae; one record per read unless a first-ALT result turns up
     std::vector<snapgpu_single_result> fused_res, fused_alt;
     bool fused_done = false;
@@ -758,7 +805,7 @@ struct GroupBuf {
 };
 static void gpu_single_group(const Options &o, FeederCtx &fc, std::vector<Work *> &ws, GroupBuf &g)
 {
-    const bool fusable = o.om < 0 && !o.ae;
+    const bool fusable = o.om < 0 && !o.ae && !single_records_path(o);
     if (ws.size() == 1 || !fusable) { for (Work *w : ws) gpu_single(o, fc, *w); return; }
     auto t_stage = std::chrono::steady_clock::now();
     auto lap = [&](std::atomic<unsigned long long> &acc) { const auto t = std::chrono::steady_clock::now(); acc += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(t - t_stage).count(); t_stage = t; };

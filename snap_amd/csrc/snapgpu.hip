@@ -35,6 +35,7 @@
 #include "cigar_lv.h"
 #include "cigar_ag.h"
 #include "cigar_args.h"
+#include "adjust.h"
 
 // =====================================================================================
 // kernels
@@ -1552,6 +1553,7 @@ struct Stage {
         if (d) { bufs.back().h = host; bufs.back().bytes = bytes; }
         return Ptr{d};
     }
+    void limit(const void *d, size_t bytes) { for (Buf &b : bufs) if (b.d == d && b.bytes > bytes) b.bytes = bytes; }      // download() copies no more than this of an output
     int download() {
         for (const Buf &b : bufs) if (b.h && b.bytes) copy(b.h, b.d, b.bytes, hipMemcpyDeviceToHost);
         if (!rc) { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) rc = hip_fail(ctx, "hipStreamSynchronize", e, SNAPGPU_E_LAUNCH); }
@@ -1991,6 +1993,8 @@ static uint32_t samf_n_reads(const SamFieldsArgs &a) { return a.n; }
 static uint32_t samf_n_reads(const SamFieldsPairedArgs &a) { return 2 * a.n_pairs; }                 // (one SamfPre per mate)
 static void samf_dp8_kernel(const SamFieldsArgs &a, uint32_t blocks, size_t lds, hipStream_t s) { snapgpu_launch_samf_dp8(&a, blocks, lds, s); }
 static void samf_dp8_kernel(const SamFieldsPairedArgs &a, uint32_t blocks, size_t lds, hipStream_t s) { snapgpu_launch_samf_dp8_paired(&a, blocks, lds, s); }
+static uint32_t samf_n_reads(const SamFieldsRecArgs &a) { return a.n; }                             // (one SamfPre per record)
+static void samf_dp8_kernel(const SamFieldsRecArgs &a, uint32_t blocks, size_t lds, hipStream_t s) { snapgpu_launch_samf_dp8_rec(&a, blocks, lds, s); }
 template <class A>
 static int launch_samf_dp8(snapgpu_ctx *ctx, A &a, Stage &st)
 {
@@ -2020,6 +2024,12 @@ static int samf_kernels(snapgpu_ctx *ctx, SamFieldsArgs &a, const SamfGeom &g, S
 {
     if (const int rc = launch_samf_dp8(ctx, a, st)) return rc;
     snapgpu_launch_sam_fields(&a, g.blocks, g.lds, st.s);
+    return SNAPGPU_OK;
+}
+static int samf_kernels(snapgpu_ctx *ctx, SamFieldsRecArgs &a, const SamfGeom &g, Stage &st)
+{
+    if (const int rc = launch_samf_dp8(ctx, a, st)) return rc;
+    snapgpu_launch_sam_fields_rec(&a, g.blocks, g.lds, st.s);
     return SNAPGPU_OK;
 }
 static int samf_kernels(snapgpu_ctx *ctx, SamFieldsPairedArgs &a, const SamfGeom &g, Stage &st)
@@ -2450,6 +2460,229 @@ extern "C" int snapgpu_align_sam_single(snapgpu_ctx *ctx, uint32_t n, const char
     SamFieldsArgs a; a.n = n;
     if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
     return finish_timing(ctx);
+}
+
+// ---- single-end reads to ALL their SAM records in one call (-om, -ea, -ae) --------------------------------------------------------------------
+// The device side of snapgpu_align_sam_single_records, every pointer a device pointer: the align launch (with the context's secondary
+// results when it has them), -ae's adjuster for a context that has none, the record list (sam_records.h), a rerun of the reads whose
+// secondary results outgrew the first launch's stride, and the SAM-field kernels over the list.  Internal buffers live in the call's Stage.
+struct SamRecIO {
+    const void *bases, *quals, *offsets, *front_clip, *data_len, *skip;
+    void *primary, *first_alt;                                 // [n] each, always there
+    void *secondary; uint32_t sec_stride; void *n_secondary;   // the context's secondary results: [n * sec_stride], [n] (NULL without snapgpu_enable_secondary)
+    void *rec_begin, *rec_read, *rec_kind;                     // [n + 1], [cap], [cap]
+    void *flag, *contig, *pos, *mapq, *ops, *n_ops, *nm, *stale;      // [cap] each (ops: [cap * ops_stride])
+};
+// *sum is filled by copies on the call's stream: total is final when this returns, `refused` once the stream has been synchronised.
+static int sam_records_core(snapgpu_ctx *ctx, const char *who, Stage &st, uint32_t n, uint32_t RL, const SamRecIO &io, uint64_t cap, uint32_t ops_stride,
+                            int use_m, bool adjust_primary, SamRecSummary *sum)
+{
+    int rc;
+    hipStream_t s = st.s;
+    const bool sec = ctx->secondary;
+    const uint32_t n_chunks = (n + SAMREC_CHUNK - 1) / SAMREC_CHUNK;
+    SamRecArgs ra; memset(&ra, 0, sizeof(ra));
+    ra.ix = ctx->ix; ra.n = n; ra.n_chunks = n_chunks; ra.alt_aware = ctx->params.alt_awareness ? 1u : 0u; ra.max_k = ctx->params.max_k; ra.cap = cap;
+    ra.check_clipped = (sec ? ctx->sec_cfg.adjust != 0 : adjust_primary) ? 1u : 0u;
+    ra.offsets = (const uint64_t *)io.offsets; ra.front_clip = (const int32_t *)io.front_clip; ra.data_len = (const int32_t *)io.data_len;
+    ra.n_secondary = sec ? (const uint32_t *)io.n_secondary : nullptr;
+    ra.count = st.scratch((size_t)n * 4); ra.partial = st.scratch((size_t)n_chunks * 8); ra.sec_slot = st.scratch((size_t)n * 4);
+    ra.ovf_list = st.scratch((size_t)n * 4); ra.summary = st.scratch(sizeof(SamRecSummary));
+    ra.rec_begin = (uint64_t *)io.rec_begin; ra.rec_read = (uint32_t *)io.rec_read; ra.rec_kind = (uint8_t *)io.rec_kind;
+    if (adjust_primary && !sec) ra.clip_off = st.scratch((size_t)n * 8);
+    if (st.rc) return st.rc;
+    ra.src.primary = (const snapgpu_single_result *)io.primary; ra.src.first_alt = (const snapgpu_single_result *)io.first_alt;
+    ra.src.secondary = (const snapgpu_single_result *)io.secondary; ra.src.sec_stride = sec ? io.sec_stride : 0;
+    ra.src.sec_slot = ra.sec_slot; ra.src.rec_begin = ra.rec_begin; ra.src.rec_read = ra.rec_read; ra.src.rec_kind = ra.rec_kind;
+    uint32_t lb = (uint32_t)ctx->num_cus * 8; { const uint32_t need = (n + 255) / 256; if (lb > need) lb = need; }      // grid of the per-read kernels
+
+    // ---- BaseAligner::AlignRead over the clipped reads (a read that is skipped gets no secondary count from the kernel: it has none)
+    if (sec) HIPCHK(ctx, hipMemsetAsync(io.n_secondary, 0, (size_t)n * 4, s), SNAPGPU_E_LAUNCH);
+    ctx->clip_front = ra.front_clip; ctx->clip_len = ra.data_len; ctx->clip_skip = (const uint8_t *)io.skip;
+    rc = launch_align(ctx, n, io.bases, io.quals, io.offsets, io.primary, io.first_alt, s, sec ? io.secondary : nullptr, sec ? io.sec_stride : 0,
+                      sec ? io.n_secondary : nullptr);
+    ctx->clip_front = ctx->clip_len = nullptr; ctx->clip_skip = nullptr;
+    if (rc || (rc = finish_timing(ctx))) return rc;
+    // ---- -ae without -om: finalizeSecondaryResults has only the primary to adjust (BaseAligner.cpp:2444-2452; a context with secondary results
+    // adjusted inside the align kernel)
+    if (adjust_primary && !sec) {
+        snapgpu_launch_samrec_clip_off(&ra, lb, s);
+        uint32_t blocks = (uint32_t)ctx->num_cus * 4; { const uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need; }
+        AdjustArgs a;
+        a.ix = ctx->ix; a.n = n; a.RL = RL; a.work_counter = ctx->d_work;
+        a.scratch_stride = 2 * (uint64_t)((RL + 255) & ~255u) + ((adjust_scratch_bytes(RL) + 255) & ~(uint64_t)255);
+        a.data = (const uint8_t *)io.bases; a.off = ra.clip_off; a.len = ra.data_len; a.results = (snapgpu_single_result *)io.primary;
+        a.scratch = st.scratch((size_t)blocks * 4 * a.scratch_stride);
+        if (st.rc) return st.rc;
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
+        HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
+        snapgpu_launch_adjust_alignments(&a, blocks, s);
+        HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+        HIPCHK(ctx, hipEventRecord(ctx->ev1, s), SNAPGPU_E_LAUNCH);
+        if ((rc = finish_timing(ctx))) return rc;
+    }
+    // ---- how many records, and which reads have more secondary results than the first launch had room for
+    HIPCHK(ctx, hipMemsetAsync(ra.summary, 0, sizeof(SamRecSummary), s), SNAPGPU_E_LAUNCH);
+    snapgpu_launch_samrec_count(&ra, lb, s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemcpyAsync(sum, ra.summary, sizeof(SamRecSummary), hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
+    if (sum->cand_overflow) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "a read produced more secondary candidates than 2 * (seeds + 1) * max_hits");
+    if (sum->n_overflow) {         // those reads again, as a batch of their own, with room for the most any of them has
+        const uint32_t m = sum->n_overflow, stride = sum->max_secondary;
+        const size_t mb = (size_t)m * sizeof(snapgpu_single_result);
+        ra.ovf_offsets = st.scratch((size_t)(m + 1) * 8); ra.ovf_front_clip = st.scratch((size_t)m * 4); ra.ovf_data_len = st.scratch((size_t)m * 4);
+        void *p2 = st.scratch(mb), *a2 = st.scratch(mb), *ns2 = st.scratch((size_t)m * 4), *ovf = st.scratch(mb * stride, true);
+        if (st.rc) return st.rc;
+        ra.src.sec_ovf = (const snapgpu_single_result *)ovf; ra.src.ovf_stride = stride; ra.ovf_n_secondary = (const uint32_t *)ns2;
+        HIPCHK(ctx, hipMemsetAsync(ovf, 0, mb * stride, s), SNAPGPU_E_LAUNCH);          // (a row the rerun did not fill would read as NotFound, and k_samrec_list checks its counts)
+        snapgpu_launch_samrec_gather(&ra, m, s);
+        HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+        const int heavy = ctx->single_heavy_first; ctx->single_heavy_first = 0;          // (the gathered offsets do not delimit the reads: no weights from them)
+        ctx->clip_front = ra.ovf_front_clip; ctx->clip_len = ra.ovf_data_len; ctx->clip_skip = nullptr;
+        rc = launch_align(ctx, m, io.bases, io.quals, ra.ovf_offsets, p2, a2, s, ovf, stride, ns2);
+        ctx->clip_front = ctx->clip_len = nullptr; ctx->single_heavy_first = heavy;
+        if (rc || (rc = finish_timing(ctx))) return rc;
+    }
+    // ---- the record list, then the fields of the records the caller has room for
+    snapgpu_launch_samrec_list(&ra, lb, s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    // (the copy of `refused` into the caller's summary is issued last, below: no return between it and the caller's synchronisation)
+    auto copy_refused = [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(&sum->refused, &ra.summary->refused, 4, hipMemcpyDeviceToHost, s), SNAPGPU_E_LAUNCH);
+        return SNAPGPU_OK;
+    };
+    const uint64_t n_fmt = sum->total < cap ? sum->total : cap;
+    if (n_fmt == 0) return copy_refused();
+    if (n_fmt > 0xFFFFFFFFull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 records in one call");
+    SamfGeom g;
+    if ((rc = samf_geometry(ctx, who, RL, (uint32_t)n_fmt, &g))) return rc;
+    const SamfBufs b{io.bases, io.quals, io.offsets, io.front_clip, io.data_len, io.primary, io.flag, io.contig, io.pos, io.mapq, io.ops, io.n_ops, io.nm, io.stale};
+    SamFieldsRecArgs a; a.n = (uint32_t)n_fmt; a.src = ra.src;
+    if ((rc = launch_sam_fields(ctx, a, g, b, (uint32_t)n_fmt, ops_stride, use_m, st))) return rc;
+    return copy_refused();
+}
+
+// the first launch's room per read when the caller does not ask for the secondary results: 8 (what most reads need; the rest are rerun) within -omax
+static uint32_t samrec_first_stride(const snapgpu_ctx *ctx) { const int64_t m = ctx->sec_cfg.omax; return (uint32_t)(m < 1 ? 1 : (m < 8 ? m : 8)); }
+static const char *const RERUN_MISMATCH_MSG = "snapgpu_align_sam_single_records: the rerun of a read found a different number of secondary results than its first pass";
+static const char *const AE_CLIPPED_MSG = "-ae: a read the reader clipped reaches the end of its contig, which the adjuster does not reproduce (see snapgpu_adjust_alignments)";
+
+extern "C" int snapgpu_align_sam_single_records(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                                const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                                snapgpu_single_result *results, snapgpu_single_result *first_alt,
+                                                snapgpu_single_result *secondary, uint32_t secondary_stride, uint32_t *n_secondary,
+                                                uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, uint32_t *rec_read, uint8_t *rec_kind,
+                                                int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                                                int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent)
+{
+    const char *who = "snapgpu_align_sam_single_records";
+    if (!ctx || !n_records || !rec_begin || (n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip)) ||
+        (n && record_capacity && (!rec_read || !rec_kind || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm || !reference_history_dependent)) ||
+        (secondary && secondary_stride == 0))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records: null argument");
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records: ops_stride must be at least 3");
+    if (ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records: a single-end context is needed (no snapgpu_enable_paired)");
+    if (adjust_primary && ctx->secondary && !ctx->sec_cfg.adjust)
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records: a context with secondary results takes -ae from snapgpu_enable_secondary (adjust_alignments)");
+    *n_records = 0; rec_begin[0] = 0;
+    if (n == 0) return SNAPGPU_OK;
+    uint32_t RL;
+    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
+        if (!skip[i] && (uint32_t)data_len[i] > ctx->params.max_read_len)
+            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (BaseAligner.cpp:354-358)");
+        return (int)SNAPGPU_OK;
+    });
+    if (rc) return rc;
+    if ((size_t)4 * agc_lds_bytes(RL) > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, std::string(who) + ": reads too long for the LDS rows");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, ctx->stream);
+    const bool sec = ctx->secondary;
+    const uint64_t cap = record_capacity;
+    const size_t n4 = (size_t)n * 4, rb = (size_t)n * sizeof(snapgpu_single_result), c4 = (size_t)cap * 4;
+    SamRecIO io;
+    io.bases = bases; io.quals = quals; io.offsets = offsets;
+    stage_reads(st, io.bases, io.quals, io.offsets, n);
+    io.front_clip = st.in(front_clip, n4); io.data_len = st.in(data_len, n4); io.skip = st.in(skip, n);
+    io.primary = st.out(results, rb); io.first_alt = st.out(first_alt, rb);                          // (a NULL host pointer: a device-only buffer)
+    io.sec_stride = secondary ? secondary_stride : samrec_first_stride(ctx);
+    io.secondary = nullptr; io.n_secondary = nullptr;
+    const size_t sec_bytes = (size_t)n * io.sec_stride * sizeof(snapgpu_single_result);
+    if (sec) { io.secondary = st.out(secondary, sec_bytes, 16); io.n_secondary = st.out(n_secondary, n4); }
+    io.rec_begin = st.out(rec_begin, (size_t)(n + 1) * 8); io.rec_read = st.out(rec_read, c4); io.rec_kind = st.out(rec_kind, (size_t)cap);
+    io.flag = st.out(flag, c4); io.contig = st.out(contig, c4); io.pos = st.out(pos, (size_t)cap * 8); io.mapq = st.out(mapq, c4);
+    io.ops = st.out(ops, c4 * ops_stride); io.n_ops = st.out(n_ops, c4); io.nm = st.out(nm, c4); io.stale = st.out(reference_history_dependent, c4);
+    if (st.rc) return st.rc;
+    if (sec && secondary) HIPCHK(ctx, hipMemsetAsync(io.secondary, 0, sec_bytes, st.s), SNAPGPU_E_LAUNCH);
+    if (!sec && n_secondary) memset(n_secondary, 0, n4);
+    SamRecSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = sam_records_core(ctx, who, st, n, RL, io, cap, ops_stride, use_m, adjust_primary != 0, &sum))) return rc;
+    const size_t f = (size_t)(sum.total < cap ? sum.total : cap);                                    // the records that were formatted: only they come down
+    st.limit(io.rec_read, f * 4); st.limit(io.rec_kind, f); st.limit(io.flag, f * 4); st.limit(io.contig, f * 4); st.limit(io.pos, f * 8); st.limit(io.mapq, f * 4);
+    st.limit(io.ops, f * 4 * ops_stride); st.limit(io.n_ops, f * 4); st.limit(io.nm, f * 4); st.limit(io.stale, f * 4);
+    if ((rc = st.download())) return rc;
+    if (f && (rc = finish_timing(ctx))) return rc;
+    *n_records = sum.total;
+    if (sum.refused & SAMREC_RERUN_MISMATCH) return fail(ctx, SNAPGPU_E_LAUNCH, RERUN_MISMATCH_MSG);
+    if (sum.refused & SAMREC_AE_CLIPPED) return fail(ctx, SNAPGPU_E_UNSUPPORTED, AE_CLIPPED_MSG);
+    return sum.total > cap ? SNAPGPU_W_RECORDS_TRUNCATED : SNAPGPU_OK;
+}
+
+// device-pointer form: reads, Read::clip's outcome and every output in HBM (d_results .. d_n_secondary may be NULL: not wanted); *n_records is a
+// host word.  max_read_len as in snapgpu_sam_fields_single_device.  Synchronous on `stream` (NULL: the context's).
+extern "C" int snapgpu_align_sam_single_records_device(snapgpu_ctx *ctx, uint32_t n, uint32_t max_read_len, const void *d_bases, const void *d_quals,
+                                                       const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_skip, int use_m,
+                                                       int adjust_primary, void *d_results, void *d_first_alt, void *d_secondary, uint32_t secondary_stride,
+                                                       void *d_n_secondary, uint64_t record_capacity, uint64_t *n_records, void *d_rec_begin, void *d_rec_read,
+                                                       void *d_rec_kind, void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
+                                                       void *d_n_ops, void *d_nm, void *d_reference_history_dependent, void *stream)
+{
+    const char *who = "snapgpu_align_sam_single_records_device";
+    if (!ctx || !n_records || (n && (!d_bases || !d_quals || !d_offsets || !d_front_clip || !d_data_len || !d_skip || !d_rec_begin)) ||
+        (n && record_capacity && (!d_rec_read || !d_rec_kind || !d_flag || !d_contig || !d_pos || !d_mapq || !d_ops || !d_n_ops || !d_nm || !d_reference_history_dependent)) ||
+        (d_secondary && secondary_stride == 0))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: null argument");
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: ops_stride must be at least 3");
+    if (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: max_read_len out of range");
+    if (ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: a single-end context is needed (no snapgpu_enable_paired)");
+    if (adjust_primary && ctx->secondary && !ctx->sec_cfg.adjust)
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: a context with secondary results takes -ae from snapgpu_enable_secondary (adjust_alignments)");
+    *n_records = 0;
+    if (n == 0) {                                       // rec_begin[0] = 0, as the host form leaves it
+        if (!d_rec_begin) return SNAPGPU_OK;
+        hipStream_t s0 = stream ? (hipStream_t)stream : ctx->stream;
+        HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+        HIPCHK(ctx, hipMemsetAsync(d_rec_begin, 0, 8, s0), SNAPGPU_E_LAUNCH);
+        HIPCHK(ctx, hipStreamSynchronize(s0), SNAPGPU_E_LAUNCH);
+        return SNAPGPU_OK;
+    }
+    const uint32_t RL = max_read_len < 64 ? 64 : max_read_len;
+    if ((size_t)4 * agc_lds_bytes(RL) > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, std::string(who) + ": reads too long for the LDS rows");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    const bool sec = ctx->secondary;
+    const size_t rb = (size_t)n * sizeof(snapgpu_single_result);
+    SamRecIO io;
+    io.bases = d_bases; io.quals = d_quals; io.offsets = d_offsets; io.front_clip = d_front_clip; io.data_len = d_data_len; io.skip = d_skip;
+    io.primary = d_results ? d_results : (void *)st.scratch(rb); io.first_alt = d_first_alt ? d_first_alt : (void *)st.scratch(rb);
+    io.sec_stride = d_secondary ? secondary_stride : samrec_first_stride(ctx);
+    io.secondary = nullptr; io.n_secondary = nullptr;
+    if (sec) {
+        io.secondary = d_secondary ? d_secondary : (void *)st.scratch((size_t)n * io.sec_stride * sizeof(snapgpu_single_result) + 16);
+        io.n_secondary = d_n_secondary ? d_n_secondary : (void *)st.scratch((size_t)n * 4);
+    } else if (d_n_secondary) HIPCHK(ctx, hipMemsetAsync(d_n_secondary, 0, (size_t)n * 4, st.s), SNAPGPU_E_LAUNCH);
+    io.rec_begin = d_rec_begin; io.rec_read = d_rec_read; io.rec_kind = d_rec_kind;
+    io.flag = d_flag; io.contig = d_contig; io.pos = d_pos; io.mapq = d_mapq; io.ops = d_ops; io.n_ops = d_n_ops; io.nm = d_nm; io.stale = d_reference_history_dependent;
+    if (st.rc) return st.rc;
+    SamRecSummary sum; memset(&sum, 0, sizeof(sum));
+    int rc = sam_records_core(ctx, who, st, n, RL, io, record_capacity, ops_stride, use_m, adjust_primary != 0, &sum);
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    if (sum.total && record_capacity && (rc = finish_timing(ctx))) return rc;
+    *n_records = sum.total;
+    if (sum.refused & SAMREC_RERUN_MISMATCH) return fail(ctx, SNAPGPU_E_LAUNCH, RERUN_MISMATCH_MSG);
+    if (sum.refused & SAMREC_AE_CLIPPED) return fail(ctx, SNAPGPU_E_UNSUPPORTED, AE_CLIPPED_MSG);
+    return sum.total > record_capacity ? SNAPGPU_W_RECORDS_TRUNCATED : SNAPGPU_OK;
 }
 
 // paired-end writer: results -> the computed fields of both SAM records of each pair (sam_fields.h, cigar_k.hip)
