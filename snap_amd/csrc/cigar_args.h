@@ -1,4 +1,4 @@
-// cigar_args.h -- kernel arguments of k_cigar_lv (cigar_k.hip), shared with the host side (snapgpu.hip).
+// cigar_args.h -- arguments of the kernels in cigar_k.hip, shared with the host side (snapgpu.hip).
 #pragma once
 #include "dev_common.h"
 #include "../../include/snapgpu.h"
@@ -25,36 +25,32 @@ struct CigarAGArgs {
     uint32_t *ops; int32_t *n_ops; int32_t *edit_distance; int32_t *add_front_clipping; int64_t *extra_after; int32_t *tail_ins; int32_t *stale;
 };
 
-struct SamFieldsArgs {
+// The SAM-field kernels (cigar_k.hip: k_sam_fields*, k_samf_dp8*) format items: the reads of a batch, the records of a record list, or the
+// 2 * n_pairs mates of a paired batch.  What the three launches share; the outputs, the CIGAR rows and the SamfPre rows are per item.
+struct SamFieldsCommon {
     DevIndex ix;
     AGCParamsPOD prm;
-    uint32_t n, RL, ops_stride, use_m, use_affine_gap;
+    uint32_t RL, ops_stride, use_m, use_affine_gap;
     const uint8_t *bases; const uint8_t *quals; const uint64_t *offsets;       // the reads as they came from the file (unclipped)
     const int32_t *front_clip; const int32_t *data_len;                          // Read::clip's result: bases clipped in front, bases kept
-    const snapgpu_single_result *results;
-    uint8_t *scratch; uint64_t scratch_stride;
+    uint8_t *scratch; uint64_t scratch_stride;                                   // per wave: samf_scratch_layout (cigar_k.hip)
     uint32_t *work_counter;
     int32_t *flag; int32_t *contig; int64_t *pos; int32_t *mapq; uint32_t *ops; int32_t *n_ops; int32_t *nm; int32_t *stale;
-    // the banded row loops run ahead of the records, eight reads to a wavefront (cigar_ag.h: SamfPre; k_samf_dp8): n * pre_stride bytes, or NULL
+    // the banded row loops run ahead of the records, eight items to a wavefront (cigar_ag.h: SamfPre; k_samf_dp8*): items * pre_stride bytes, or NULL
     uint8_t *pre; uint64_t pre_stride; uint32_t *pre_counter;
     uint32_t *pre_valid;                                                         // SamfPre records the pre-pass left valid (snapgpu_debug_samf_pre_valid)
 };
 
-struct SamFieldsPairedArgs {
-    DevIndex ix;
-    AGCParamsPOD prm;
-    uint32_t n_pairs, RL, ops_stride, use_m, use_affine_gap;
-    const uint8_t *bases; const uint8_t *quals; const uint64_t *offsets;       // 2 * n_pairs + 1: read 0 and read 1 of each pair, unclipped
-    const int32_t *front_clip; const int32_t *data_len;                          // [2 * n_pairs]
+struct SamFieldsArgs : SamFieldsCommon {
+    uint32_t n;
+    const snapgpu_single_result *results;                                        // [n]
+};
+
+struct SamFieldsPairedArgs : SamFieldsCommon {                                   // the per-read arrays: [2 * n_pairs], read 0 and read 1 of each pair
+    uint32_t n_pairs;
     const snapgpu_paired_result *results;                                        // [n_pairs]
-    uint8_t *scratch; uint64_t scratch_stride;
-    uint32_t *work_counter;
-    // per read [2 * n_pairs]
-    int32_t *flag; int32_t *contig; int64_t *pos; int32_t *mapq; uint32_t *ops; int32_t *n_ops; int32_t *nm; int32_t *rnext; int64_t *pnext; int64_t *tlen; int32_t *stale;
+    int32_t *rnext; int64_t *pnext; int64_t *tlen;                               // [2 * n_pairs]
     int32_t *first_written;                                                      // [n_pairs]: which read's record comes first in the file
-    // the banded row loops of the 2 * n_pairs mates run ahead of the records (k_samf_dp8_paired): one SamfPre per mate, or NULL
-    uint8_t *pre; uint64_t pre_stride; uint32_t *pre_counter;
-    uint32_t *pre_valid;
 };
 
 // snapgpu_align_sam_single_records: the records of a batch are a list over its reads (sam_records.h).  Record r belongs to read rec_read[r];
@@ -72,20 +68,9 @@ struct SamRecSrc {
     const uint64_t *rec_begin; const uint32_t *rec_read; const uint8_t *rec_kind;       // [n reads + 1], [records], [records]
 };
 
-// the SAM-field kernels over a record list: SamFieldsArgs with n = records to format, the per-read arrays indexed through src.rec_read and the
-// outputs (and the SamfPre rows) per record
-struct SamFieldsRecArgs {
-    DevIndex ix;
-    AGCParamsPOD prm;
-    uint32_t n, RL, ops_stride, use_m, use_affine_gap;
-    const uint8_t *bases; const uint8_t *quals; const uint64_t *offsets;
-    const int32_t *front_clip; const int32_t *data_len;
-    const snapgpu_single_result *results;                                        // (= src.primary)
-    uint8_t *scratch; uint64_t scratch_stride;
-    uint32_t *work_counter;
-    int32_t *flag; int32_t *contig; int64_t *pos; int32_t *mapq; uint32_t *ops; int32_t *n_ops; int32_t *nm; int32_t *stale;
-    uint8_t *pre; uint64_t pre_stride; uint32_t *pre_counter;
-    uint32_t *pre_valid;
+// the SAM-field kernels over a record list: n records to format, each reaching its read and its result through src
+struct SamFieldsRecArgs : SamFieldsCommon {
+    uint32_t n;
     SamRecSrc src;
 };
 
@@ -120,13 +105,15 @@ extern "C" void snapgpu_launch_samrec_count(const SamRecArgs *a, uint32_t blocks
 extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_list(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_clip_off(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
-extern "C" void snapgpu_launch_sam_fields_rec(const SamFieldsRecArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
-extern "C" void snapgpu_launch_samf_dp8_rec(const SamFieldsRecArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
-extern "C" void snapgpu_launch_sam_fields_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
-extern "C" void snapgpu_launch_sam_fields(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
-extern "C" void snapgpu_launch_samf_dp8(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
-extern "C" void snapgpu_launch_samf_dp8_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+// the field kernel and the pre-pass of each of the three launches (cigar_k.hip)
+void snapgpu_launch_sam_fields(const SamFieldsArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_sam_fields(const SamFieldsRecArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_sam_fields(const SamFieldsPairedArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_samf_dp8(const SamFieldsArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_samf_dp8(const SamFieldsRecArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
+void snapgpu_launch_samf_dp8(const SamFieldsPairedArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 extern "C" size_t snapgpu_samf_dp8_lds_per_wave(uint32_t RL);
+extern "C" uint64_t snapgpu_samf_scratch_stride(uint32_t RL);                 // samf_scratch_layout(RL).stride
 extern "C" void snapgpu_launch_cigar_ag(const CigarAGArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s);
 // snapgpu_adjust_alignments: AlignmentAdjuster::AdjustAlignment for a batch of results (adjust.h), one wavefront per result
 struct AdjustArgs {

@@ -1,5 +1,7 @@
-// cigar_k.hip -- kernel of snapgpu_compute_cigar_lv: SAMFormat::computeCigar (Landau-Vishkin variant) for a batch of written
-// reads, one wavefront per read, persistent grid.
+// cigar_k.hip -- the SAM writer's kernels, one wavefront per item on a persistent grid: SAMFormat::computeCigar for a batch of written reads
+// (k_cigar_lv, k_cigar_ag), result -> SAM fields (k_sam_fields*: one body, sam_fields_run, over the reads of a batch, the records of a record
+// list or the mates of a paired batch, with the pre-pass k_samf_dp8* ahead of it), AlignmentAdjuster (k_adjust_alignments) and the launches
+// of the record-list kernels (sam_records.h).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -c cigar_k.hip
 #include <hip/hip_runtime.h>
 #include "cigar_lv.h"
@@ -78,111 +80,126 @@ extern "C" void snapgpu_launch_cigar_ag(const CigarAGArgs *a, uint32_t blocks, s
     hipLaunchKernelGGL(k_cigar_ag, dim3(blocks), dim3(256), lds_bytes, s, *a);
 }
 
-// result -> computed fields of the SAM record (sam_fields.h): one wavefront per read
+// ---- result -> computed fields of the SAM record (sam_fields.h): one wavefront per item ----------------------------------------------------
 #ifndef SAMF_WAVES
 #define SAMF_WAVES 8            // waves per SIMD the SAM-field kernels are built for (blocks of four waves: as many blocks per CU).  The kernels are
                                 // latency-bound (8 of 64 lanes in the affine-gap CIGAR): 4.32 M reads/s at 4 (131 VGPRs, rounds 2-3), 5.31 M at 6, 5.73 M at 8 (profiles/r04n)
 #endif
-// (k_sam_fields_rec below is this body over a record list: a change here belongs there too)
+// the per-wave scratch for reads of up to RL bases: the read and its reverse complement (at 0, 2 * RL bytes), the Landau-Vishkin cells, the
+// affine-gap CIGAR state
+struct SamfScratch { uint32_t lv_cells, ag_scratch; uint64_t stride; };
+static __host__ __device__ __forceinline__ SamfScratch samf_scratch_layout(uint32_t RL) {
+    SamfScratch l;
+    l.lv_cells = (2 * RL + 255) & ~255u;
+    l.ag_scratch = l.lv_cells + ((lvc_scratch_bytes() + 255) & ~255u);
+    l.stride = (uint64_t)l.ag_scratch + ((agc_scratch_bytes(RL) + 255) & ~(uint64_t)255);
+    return l;
+}
+extern "C" uint64_t snapgpu_samf_scratch_stride(uint32_t RL) { return samf_scratch_layout(RL).stride; }
+
+// Item i of a launch: read i and result i of the batch (SamFieldsArgs), record i of a record list, which reaches its read and its result
+// where the align kernels left them (SamFieldsRecArgs, sam_records.h), or mate i & 1 of pair i >> 1 (SamFieldsPairedArgs).  SamfRes: the
+// fields of a result the writer looks at.  samf_item_flag: SAM_SECONDARY for a record that is not its read's primary (createSAMLine's
+// argument, SAM.cpp:1477-1479: writeReads passes i != 0 || !firstIsPrimary).
+struct SamfRes { int status, score, dir, add_front, used_ag, clipped_before, clipped_after, mapq, supplementary; long long loc; };
+static __device__ __forceinline__ SamfRes samf_res(const snapgpu_single_result *rp) {
+    return SamfRes{rp->status, rp->score, rp->direction, rp->clipping_for_read_adjustment, rp->used_affine_gap_scoring, rp->bases_clipped_before,
+                   rp->bases_clipped_after, rp->mapq, rp->supplementary, (long long)rp->location};
+}
+static __device__ __forceinline__ uint32_t samf_n_items(const SamFieldsArgs &a) { return a.n; }
+static __device__ __forceinline__ uint32_t samf_n_items(const SamFieldsRecArgs &a) { return a.n; }
+static __device__ __forceinline__ uint32_t samf_n_items(const SamFieldsPairedArgs &a) { return 2u * a.n_pairs; }
+static __device__ __forceinline__ uint32_t samf_item_read(const SamFieldsArgs &, uint32_t i) { return i; }
+static __device__ __forceinline__ uint32_t samf_item_read(const SamFieldsRecArgs &a, uint32_t i) { return a.src.rec_read[i]; }
+static __device__ __forceinline__ uint32_t samf_item_read(const SamFieldsPairedArgs &, uint32_t i) { return i; }
+static __device__ __forceinline__ SamfRes samf_item_result(const SamFieldsArgs &a, uint32_t i) { return samf_res(&a.results[i]); }
+static __device__ __forceinline__ SamfRes samf_item_result(const SamFieldsRecArgs &a, uint32_t i) {
+    const uint32_t rd = a.src.rec_read[i], kind = (uint32_t)a.src.rec_kind[i];
+    return samf_res(samrec_result(a.src, rd, kind, (uint32_t)((uint64_t)i - a.src.rec_begin[rd])));
+}
+static __device__ __forceinline__ SamfRes samf_item_result(const SamFieldsPairedArgs &a, uint32_t i) {
+    const snapgpu_paired_result *pr = &a.results[i >> 1]; const uint32_t w = i & 1u;
+    return SamfRes{pr->status[w], pr->score[w], pr->direction[w], pr->clipping_for_read_adjustment[w], pr->used_affine_gap_scoring[w],
+                   pr->bases_clipped_before[w], pr->bases_clipped_after[w], pr->mapq[w], pr->supplementary[w], (long long)pr->location[w]};
+}
+static __device__ __forceinline__ int samf_item_flag(const SamFieldsArgs &, uint32_t) { return 0; }
+static __device__ __forceinline__ int samf_item_flag(const SamFieldsRecArgs &a, uint32_t i) { return a.src.rec_kind[i] != SAMREC_PRIMARY ? 0x100 : 0; }
+
+// a wavefront's share of a field kernel's LDS and scratch
+struct SamfWave { int lane; uint8_t *lds, *oriented, *ag_scratch; uint32_t *lv_cells; AGCParams prm; };
+static __device__ __forceinline__ SamfWave samf_wave(const SamFieldsCommon &a, uint8_t *lds)
+{
+    SamfWave w;
+    w.lane = lane_id();
+    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t wave_slot = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_in_block;
+    const SamfScratch l = samf_scratch_layout(a.RL);
+    w.lds = lds + (size_t)wave_in_block * agc_lds_bytes(a.RL);
+    w.oriented = a.scratch + (size_t)wave_slot * a.scratch_stride;
+    w.lv_cells = (uint32_t *)(w.oriented + l.lv_cells);
+    w.ag_scratch = w.oriented + l.ag_scratch;
+    w.prm.match = a.prm.match; w.prm.sub = a.prm.sub; w.prm.gap_open = a.prm.gap_open; w.prm.gap_ext = a.prm.gap_ext;
+    return w;
+}
+// the next item of the launch's work counter (n and beyond: none is left)
+static __device__ __forceinline__ uint32_t samf_next(const SamFieldsCommon &a, int lane)
+{
+    uint32_t i = 0;
+    if (lane == 0) i = atomicAdd(a.work_counter, 1u);
+    return first_u32(i);
+}
+
+// the record of item i (uniform over the wave): its result as wave-uniform values, then sam_fields_single_item
+template <class A>
+static __device__ __forceinline__ SamFieldsOut samf_item_fields(const A &a, const SamfWave &w, uint32_t i, bool paired)
+{
+    const uint32_t rd = first_u32(samf_item_read(a, i));
+    const uint64_t b = first_u64(a.offsets[rd]), e = first_u64(a.offsets[rd + 1]);
+    const SamfRes v = samf_item_result(a, i);
+    snapgpu_single_result r;
+    r.status = (int32_t)first_u32((uint32_t)v.status); r.direction = (int32_t)first_u32((uint32_t)v.dir);
+    r.location = (int64_t)first_u64((uint64_t)v.loc); r.orig_location = 0;
+    r.score = (int32_t)first_u32((uint32_t)v.score); r.score_prior_to_clipping = 0;
+    r.mapq = (int32_t)first_u32((uint32_t)v.mapq);
+    r.clipping_for_read_adjustment = (int32_t)first_u32((uint32_t)v.add_front);
+    r.used_affine_gap_scoring = (int32_t)first_u32((uint32_t)v.used_ag);
+    r.bases_clipped_before = (int32_t)first_u32((uint32_t)v.clipped_before);
+    r.bases_clipped_after = (int32_t)first_u32((uint32_t)v.clipped_after);
+    r.ag_score = 0; r.supplementary = (int32_t)first_u32((uint32_t)v.supplementary); r.seed_offset = 0; r.match_probability = 0.0;
+    r.probability_all_candidates = 0.0; r.popular_seeds_skipped = 0; r.reserved = 0;
+    const int F0 = (int)first_u32((uint32_t)a.front_clip[rd]), D0 = (int)first_u32((uint32_t)a.data_len[rd]);
+    const SamfPre *pre = a.pre ? (const SamfPre *)(a.pre + (size_t)i * a.pre_stride) : nullptr;
+    return sam_fields_single_item(a.ix, w.prm, a.use_affine_gap != 0, a.use_m != 0, a.bases + b, a.quals + b, (int)(e - b), F0, D0, r,
+                                  w.lds, a.RL, w.oriented, w.lv_cells, w.ag_scratch, a.ops + (size_t)i * a.ops_stride, (int)a.ops_stride, paired, pre);
+}
+
+// A = SamFieldsArgs (k_sam_fields) or SamFieldsRecArgs (k_sam_fields_rec)
+template <class A>
+static __device__ __forceinline__ void sam_fields_run(const A &a, uint8_t *lds)
+{
+    const SamfWave w = samf_wave(a, lds);
+    while (true) {
+        const uint32_t i = samf_next(a, w.lane);
+        if (i >= samf_n_items(a)) break;
+        const SamFieldsOut o = samf_item_fields(a, w, i, false);
+        if (w.lane == 0) {
+            a.flag[i] = o.flag | samf_item_flag(a, i); a.contig[i] = o.contig; a.pos[i] = o.pos; a.mapq[i] = o.mapq; a.n_ops[i] = o.n_ops; a.nm[i] = o.nm; a.stale[i] = o.stale;
+        }
+        WAVE_SYNC();
+    }
+}
+
 __global__ __launch_bounds__(256, SAMF_WAVES) void k_sam_fields(SamFieldsArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = lane_id();
-    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t wave_slot = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_in_block;
-    uint8_t *my = lds + (size_t)wave_in_block * agc_lds_bytes(a.RL);
-    uint8_t *scratch = a.scratch + (size_t)wave_slot * a.scratch_stride;
-    uint8_t *oriented = scratch;                                                      // 2 * RL bytes
-    uint32_t *lv_cells = (uint32_t *)(scratch + ((2 * a.RL + 255) & ~255u));
-    uint8_t *ag_scratch = (uint8_t *)lv_cells + ((lvc_scratch_bytes() + 255) & ~255u);
-    AGCParams prm; prm.match = a.prm.match; prm.sub = a.prm.sub; prm.gap_open = a.prm.gap_open; prm.gap_ext = a.prm.gap_ext;
-    while (true) {
-        uint32_t i = 0;
-        if (lane == 0) i = atomicAdd(a.work_counter, 1u);
-        i = first_u32(i);
-        if (i >= a.n) break;
-        const uint64_t b = first_u64(a.offsets[i]), e = first_u64(a.offsets[i + 1]);
-        snapgpu_single_result r;                                                  // the fields the writer looks at, as wave-uniform values
-        {
-            const snapgpu_single_result *rp = &a.results[i];
-            r.status = (int32_t)first_u32((uint32_t)rp->status); r.direction = (int32_t)first_u32((uint32_t)rp->direction);
-            r.location = (int64_t)first_u64((uint64_t)rp->location); r.orig_location = 0;
-            r.score = (int32_t)first_u32((uint32_t)rp->score); r.score_prior_to_clipping = 0;
-            r.mapq = (int32_t)first_u32((uint32_t)rp->mapq);
-            r.clipping_for_read_adjustment = (int32_t)first_u32((uint32_t)rp->clipping_for_read_adjustment);
-            r.used_affine_gap_scoring = (int32_t)first_u32((uint32_t)rp->used_affine_gap_scoring);
-            r.bases_clipped_before = (int32_t)first_u32((uint32_t)rp->bases_clipped_before);
-            r.bases_clipped_after = (int32_t)first_u32((uint32_t)rp->bases_clipped_after);
-            r.ag_score = 0; r.supplementary = (int32_t)first_u32((uint32_t)rp->supplementary); r.seed_offset = 0; r.match_probability = 0.0;
-            r.probability_all_candidates = 0.0; r.popular_seeds_skipped = 0; r.reserved = 0;
-        }
-        uint32_t *ops = a.ops + (size_t)i * a.ops_stride;
-        const int F0 = (int)first_u32((uint32_t)a.front_clip[i]), D0 = (int)first_u32((uint32_t)a.data_len[i]);
-        const SamfPre *pre = a.pre ? (const SamfPre *)(a.pre + (size_t)i * a.pre_stride) : nullptr;
-        const SamFieldsOut o = sam_fields_single_item(a.ix, prm, a.use_affine_gap != 0, a.use_m != 0, a.bases + b, a.quals + b, (int)(e - b), F0, D0, r,
-                                                      my, a.RL, oriented, lv_cells, ag_scratch, ops, (int)a.ops_stride, false, pre);
-        if (lane == 0) {
-            a.flag[i] = o.flag; a.contig[i] = o.contig; a.pos[i] = o.pos; a.mapq[i] = o.mapq; a.n_ops[i] = o.n_ops; a.nm[i] = o.nm; a.stale[i] = o.stale;
-        }
-        WAVE_SYNC();
-    }
+    sam_fields_run(a, lds);
 }
 
-// The records of snapgpu_align_sam_single_records: k_sam_fields with record i reaching its read through the record list and its result where the
-// align kernels left it (sam_records.h), and SAM_SECONDARY in the flag of a record that is not its read's primary (createSAMLine's argument,
-// SAM.cpp:1477-1479: writeReads passes i != 0 || !firstIsPrimary).  A kernel of its own, so that k_sam_fields stays the code it was.
+// the records of snapgpu_align_sam_single_records
 __global__ __launch_bounds__(256, SAMF_WAVES) void k_sam_fields_rec(SamFieldsRecArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = lane_id();
-    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t wave_slot = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_in_block;
-    uint8_t *my = lds + (size_t)wave_in_block * agc_lds_bytes(a.RL);
-    uint8_t *scratch = a.scratch + (size_t)wave_slot * a.scratch_stride;
-    uint8_t *oriented = scratch;                                                      // 2 * RL bytes
-    uint32_t *lv_cells = (uint32_t *)(scratch + ((2 * a.RL + 255) & ~255u));
-    uint8_t *ag_scratch = (uint8_t *)lv_cells + ((lvc_scratch_bytes() + 255) & ~255u);
-    AGCParams prm; prm.match = a.prm.match; prm.sub = a.prm.sub; prm.gap_open = a.prm.gap_open; prm.gap_ext = a.prm.gap_ext;
-    while (true) {
-        uint32_t i = 0;
-        if (lane == 0) i = atomicAdd(a.work_counter, 1u);
-        i = first_u32(i);
-        if (i >= a.n) break;
-        const uint32_t rd = first_u32(a.src.rec_read[i]), kind = first_u32((uint32_t)a.src.rec_kind[i]);
-        const uint64_t b = first_u64(a.offsets[rd]), e = first_u64(a.offsets[rd + 1]);
-        snapgpu_single_result r;                                                  // the fields the writer looks at, as wave-uniform values
-        {
-            const snapgpu_single_result *rp = samrec_result(a.src, rd, kind, (uint32_t)((uint64_t)i - first_u64(a.src.rec_begin[rd])));
-            r.status = (int32_t)first_u32((uint32_t)rp->status); r.direction = (int32_t)first_u32((uint32_t)rp->direction);
-            r.location = (int64_t)first_u64((uint64_t)rp->location); r.orig_location = 0;
-            r.score = (int32_t)first_u32((uint32_t)rp->score); r.score_prior_to_clipping = 0;
-            r.mapq = (int32_t)first_u32((uint32_t)rp->mapq);
-            r.clipping_for_read_adjustment = (int32_t)first_u32((uint32_t)rp->clipping_for_read_adjustment);
-            r.used_affine_gap_scoring = (int32_t)first_u32((uint32_t)rp->used_affine_gap_scoring);
-            r.bases_clipped_before = (int32_t)first_u32((uint32_t)rp->bases_clipped_before);
-            r.bases_clipped_after = (int32_t)first_u32((uint32_t)rp->bases_clipped_after);
-            r.ag_score = 0; r.supplementary = (int32_t)first_u32((uint32_t)rp->supplementary); r.seed_offset = 0; r.match_probability = 0.0;
-            r.probability_all_candidates = 0.0; r.popular_seeds_skipped = 0; r.reserved = 0;
-        }
-        uint32_t *ops = a.ops + (size_t)i * a.ops_stride;
-        const int F0 = (int)first_u32((uint32_t)a.front_clip[rd]), D0 = (int)first_u32((uint32_t)a.data_len[rd]);
-        const SamfPre *pre = a.pre ? (const SamfPre *)(a.pre + (size_t)i * a.pre_stride) : nullptr;
-        const SamFieldsOut o = sam_fields_single_item(a.ix, prm, a.use_affine_gap != 0, a.use_m != 0, a.bases + b, a.quals + b, (int)(e - b), F0, D0, r,
-                                                      my, a.RL, oriented, lv_cells, ag_scratch, ops, (int)a.ops_stride, false, pre);
-        if (lane == 0) {
-            a.flag[i] = o.flag | (kind != SAMREC_PRIMARY ? 0x100 : 0); a.contig[i] = o.contig; a.pos[i] = o.pos; a.mapq[i] = o.mapq; a.n_ops[i] = o.n_ops; a.nm[i] = o.nm; a.stale[i] = o.stale;
-        }
-        WAVE_SYNC();
-    }
-}
-
-extern "C" void snapgpu_launch_sam_fields(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_sam_fields, dim3(blocks), dim3(256), lds_bytes, s, *a);
-}
-extern "C" void snapgpu_launch_sam_fields_rec(const SamFieldsRecArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_sam_fields_rec, dim3(blocks), dim3(256), lds_bytes, s, *a);
+    sam_fields_run(a, lds);
 }
 
 // ---- the banded row loops of a batch's records, eight reads to a wavefront (cigar_ag.h: SamfPre) -------------------------------------------
@@ -196,32 +213,6 @@ static __host__ __device__ __forceinline__ uint32_t samf_dp8_group_bytes(uint32_
     return ((RL + 15u) & ~15u) + ((samf_pre_rows(RL) + 15u) & ~15u) + 3u * 2u * samf_dp8_hn(RL);
 }
 extern "C" size_t snapgpu_samf_dp8_lds_per_wave(uint32_t RL) { return (size_t)8 * samf_dp8_group_bytes(RL); }
-
-// Where a read's result fields come from: the batch's snapgpu_single_result records, or mate r & 1 of pair r >> 1's snapgpu_paired_result.
-struct SamfDp8Res { int status, score, dir, add_front, used_ag, clipped_before, clipped_after; long long loc; };
-static __device__ __forceinline__ uint32_t samf_dp8_n(const SamFieldsArgs &a) { return a.n; }
-static __device__ __forceinline__ uint32_t samf_dp8_n(const SamFieldsPairedArgs &a) { return 2u * a.n_pairs; }
-static __device__ __forceinline__ SamfDp8Res samf_dp8_res(const SamFieldsArgs &a, uint32_t r) {
-    const snapgpu_single_result *rp = &a.results[r];
-    return SamfDp8Res{rp->status, rp->score, rp->direction, rp->clipping_for_read_adjustment, rp->used_affine_gap_scoring, rp->bases_clipped_before,
-                      rp->bases_clipped_after, (long long)rp->location};
-}
-static __device__ __forceinline__ uint32_t samf_dp8_n(const SamFieldsRecArgs &a) { return a.n; }
-// the read whose bases / clipping item r is formatted from (r itself unless the launch goes through a record list)
-static __device__ __forceinline__ uint32_t samf_dp8_read(const SamFieldsArgs &, uint32_t r) { return r; }
-static __device__ __forceinline__ uint32_t samf_dp8_read(const SamFieldsPairedArgs &, uint32_t r) { return r; }
-static __device__ __forceinline__ uint32_t samf_dp8_read(const SamFieldsRecArgs &a, uint32_t r) { return a.src.rec_read[r]; }
-static __device__ __forceinline__ SamfDp8Res samf_dp8_res(const SamFieldsRecArgs &a, uint32_t r) {
-    const uint32_t i = a.src.rec_read[r];
-    const snapgpu_single_result *rp = samrec_result(a.src, i, (uint32_t)a.src.rec_kind[r], (uint32_t)((uint64_t)r - a.src.rec_begin[i]));
-    return SamfDp8Res{rp->status, rp->score, rp->direction, rp->clipping_for_read_adjustment, rp->used_affine_gap_scoring, rp->bases_clipped_before,
-                      rp->bases_clipped_after, (long long)rp->location};
-}
-static __device__ __forceinline__ SamfDp8Res samf_dp8_res(const SamFieldsPairedArgs &a, uint32_t r) {
-    const snapgpu_paired_result *pr = &a.results[r >> 1]; const uint32_t w = r & 1u;
-    return SamfDp8Res{pr->status[w], pr->score[w], pr->direction[w], pr->clipping_for_read_adjustment[w], pr->used_affine_gap_scoring[w],
-                      pr->bases_clipped_before[w], pr->bases_clipped_after[w], (long long)pr->location[w]};
-}
 
 // A = SamFieldsArgs (k_samf_dp8: one SamfPre per read) or SamFieldsPairedArgs (k_samf_dp8_paired: one per mate, 2 * n_pairs of them).  A mate's
 // record goes through sam_fields_single_item's `paired` branch, whose attempt 0 differs from the single-end one in two places only: the aligner's
@@ -240,7 +231,7 @@ static __device__ __forceinline__ void samf_dp8_run(const A &a, uint8_t *lds)
     const int open = a.prm.gap_open, ext = a.prm.gap_ext, score_init = AGC_MAX_READ_LENGTH;
     const unsigned long long gmask = 0xffull << (8 * g);
     const long long nb = (long long)a.ix.n_bases;
-    const uint32_t n = samf_dp8_n(a);
+    const uint32_t n = samf_n_items(a);
     uint32_t n_valid = 0;
     while (true) {
         uint32_t base = 0;
@@ -255,8 +246,8 @@ static __device__ __forceinline__ void samf_dp8_run(const A &a, uint8_t *lds)
         uint64_t rb = 0;
         SamfPre *pre = (SamfPre *)(a.pre + (size_t)(elig ? r : base) * a.pre_stride);
         if (elig) {
-            const SamfDp8Res rp = samf_dp8_res(a, r);
-            const uint32_t rd = samf_dp8_read(a, r);
+            const SamfRes rp = samf_item_result(a, r);
+            const uint32_t rd = samf_item_read(a, r);
             rb = a.offsets[rd]; U = (int)(a.offsets[rd + 1] - rb);
             const int status = rp.status, score = rp.score, F0 = a.front_clip[rd], D0 = a.data_len[rd], addF = rp.add_front;
             loc = rp.loc; dir = rp.dir;
@@ -442,58 +433,19 @@ __global__ __launch_bounds__(256) void k_samf_dp8_paired(SamFieldsPairedArgs a)
 }
 
 
-extern "C" void snapgpu_launch_samf_dp8(const SamFieldsArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_samf_dp8, dim3(blocks), dim3(256), lds_bytes, s, *a);
-}
-extern "C" void snapgpu_launch_samf_dp8_rec(const SamFieldsRecArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_samf_dp8_rec, dim3(blocks), dim3(256), lds_bytes, s, *a);
-}
-extern "C" void snapgpu_launch_samf_dp8_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_samf_dp8_paired, dim3(blocks), dim3(256), lds_bytes, s, *a);
-}
-
 // paired-end writer: both reads of a pair by one wavefront, then SAMFormat::fillMateInfo for each (sam_fields.h)
 __global__ __launch_bounds__(256, SAMF_WAVES) void k_sam_fields_paired(SamFieldsPairedArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = lane_id();
-    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t wave_slot = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_in_block;
-    uint8_t *my = lds + (size_t)wave_in_block * agc_lds_bytes(a.RL);
-    uint8_t *scratch = a.scratch + (size_t)wave_slot * a.scratch_stride;
-    uint8_t *oriented = scratch;
-    uint32_t *lv_cells = (uint32_t *)(scratch + ((2 * a.RL + 255) & ~255u));
-    uint8_t *ag_scratch = (uint8_t *)lv_cells + ((lvc_scratch_bytes() + 255) & ~255u);
-    AGCParams prm; prm.match = a.prm.match; prm.sub = a.prm.sub; prm.gap_open = a.prm.gap_open; prm.gap_ext = a.prm.gap_ext;
+    const SamfWave wv = samf_wave(a, lds);
+    const int lane = wv.lane;
     while (true) {
-        uint32_t i = 0;
-        if (lane == 0) i = atomicAdd(a.work_counter, 1u);
-        i = first_u32(i);
+        const uint32_t i = samf_next(a, lane);
         if (i >= a.n_pairs) break;
-        const snapgpu_paired_result *pr = &a.results[i];
-        const bool aligned_as_pair = first_u32((uint32_t)pr->aligned_as_pair) != 0;
+        const bool aligned_as_pair = first_u32((uint32_t)a.results[i].aligned_as_pair) != 0;
         SamFieldsOut o[2];
         for (int w = 0; w < 2; w++) {
-            const uint32_t ri = 2 * i + (uint32_t)w;
-            const uint64_t b = first_u64(a.offsets[ri]), e = first_u64(a.offsets[ri + 1]);
-            snapgpu_single_result r;                                              // this mate's part of the PairedAlignmentResult
-            r.status = (int32_t)first_u32((uint32_t)pr->status[w]); r.direction = (int32_t)first_u32((uint32_t)pr->direction[w]);
-            r.location = (int64_t)first_u64((uint64_t)pr->location[w]); r.orig_location = 0;
-            r.score = (int32_t)first_u32((uint32_t)pr->score[w]); r.score_prior_to_clipping = 0;
-            r.mapq = (int32_t)first_u32((uint32_t)pr->mapq[w]);
-            r.clipping_for_read_adjustment = (int32_t)first_u32((uint32_t)pr->clipping_for_read_adjustment[w]);
-            r.used_affine_gap_scoring = (int32_t)first_u32((uint32_t)pr->used_affine_gap_scoring[w]);
-            r.bases_clipped_before = (int32_t)first_u32((uint32_t)pr->bases_clipped_before[w]);
-            r.bases_clipped_after = (int32_t)first_u32((uint32_t)pr->bases_clipped_after[w]);
-            r.ag_score = 0; r.supplementary = (int32_t)first_u32((uint32_t)pr->supplementary[w]); r.seed_offset = 0; r.match_probability = 0.0;
-            r.probability_all_candidates = 0.0; r.popular_seeds_skipped = 0; r.reserved = 0;
-            const int F0 = (int)first_u32((uint32_t)a.front_clip[ri]), D0 = (int)first_u32((uint32_t)a.data_len[ri]);
-            const SamfPre *pre = a.pre ? (const SamfPre *)(a.pre + (size_t)ri * a.pre_stride) : nullptr;
-            o[w] = sam_fields_single_item(a.ix, prm, a.use_affine_gap != 0, a.use_m != 0, a.bases + b, a.quals + b, (int)(e - b), F0, D0, r,
-                                          my, a.RL, oriented, lv_cells, ag_scratch, a.ops + (size_t)ri * a.ops_stride, (int)a.ops_stride, true, pre);
+            o[w] = samf_item_fields(a, wv, 2 * i + (uint32_t)w, true);
             WAVE_SYNC();
         }
         for (int w = 0; w < 2; w++) {
@@ -512,10 +464,12 @@ __global__ __launch_bounds__(256, SAMF_WAVES) void k_sam_fields_paired(SamFields
     }
 }
 
-extern "C" void snapgpu_launch_sam_fields_paired(const SamFieldsPairedArgs *a, uint32_t blocks, size_t lds_bytes, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_sam_fields_paired, dim3(blocks), dim3(256), lds_bytes, s, *a);
-}
+void snapgpu_launch_sam_fields(const SamFieldsArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s) { hipLaunchKernelGGL(k_sam_fields, dim3(blocks), dim3(256), lds_bytes, s, a); }
+void snapgpu_launch_sam_fields(const SamFieldsRecArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s) { hipLaunchKernelGGL(k_sam_fields_rec, dim3(blocks), dim3(256), lds_bytes, s, a); }
+void snapgpu_launch_sam_fields(const SamFieldsPairedArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s) { hipLaunchKernelGGL(k_sam_fields_paired, dim3(blocks), dim3(256), lds_bytes, s, a); }
+void snapgpu_launch_samf_dp8(const SamFieldsArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s) { hipLaunchKernelGGL(k_samf_dp8, dim3(blocks), dim3(256), lds_bytes, s, a); }
+void snapgpu_launch_samf_dp8(const SamFieldsRecArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s) { hipLaunchKernelGGL(k_samf_dp8_rec, dim3(blocks), dim3(256), lds_bytes, s, a); }
+void snapgpu_launch_samf_dp8(const SamFieldsPairedArgs &a, uint32_t blocks, size_t lds_bytes, hipStream_t s) { hipLaunchKernelGGL(k_samf_dp8_paired, dim3(blocks), dim3(256), lds_bytes, s, a); }
 
 // AlignmentAdjuster::AdjustAlignment (adjust.h) for a batch: one wavefront per result, persistent grid
 __global__ __launch_bounds__(256) void k_adjust_alignments(AdjustArgs a)

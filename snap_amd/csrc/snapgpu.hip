@@ -348,7 +348,6 @@ struct snapgpu_ctx {
     int num_cus = 0;
     int lookup_blocks_per_cu = 0;     // resident blocks per CU of k_lookup_seeds20 on this context's device (launch_lookup)
     int ag_variant = 0;               // chunks of 64 striped positions the affine-gap kernel variant holds in registers (0 = LDS form)
-    const int32_t *clip_front = nullptr, *clip_len = nullptr; const uint8_t *clip_skip = nullptr;    // snapgpu_align_sam_single: Read::clip's outcome for the launch in hand (device)
     // secondary results (snapgpu_enable_secondary)
     bool secondary = false;
     SecCfg sec_cfg{};
@@ -1697,8 +1696,13 @@ static int launch_unit_order(snapgpu_ctx *ctx, const void *d_bases, const void *
     return SNAPGPU_OK;
 }
 
+// Read::clip's outcome for an align launch over an unclipped batch (device pointers; skip NULL: no read is skipped).  A launch without a
+// window is over reads that are already clipped.  gathered: the batch is a selection of another's reads, so offsets[i + 1] is not where
+// read i ends and the heavy-first order, which weighs the reads by their offsets, is left out.
+struct ClipWindow { const int32_t *front_clip, *data_len; const uint8_t *skip; bool gathered; };
+
 static int launch_align(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals, const void *d_offsets,
-                        void *d_primary, void *d_first_alt, hipStream_t s,
+                        void *d_primary, void *d_first_alt, hipStream_t s, const ClipWindow *clip = nullptr,
                         void *d_secondary = nullptr, uint32_t sec_out_stride = 0, void *d_n_secondary = nullptr)
 {
     AlignArgs a;
@@ -1711,7 +1715,7 @@ static int launch_align(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const
     a.flag_list = nullptr; a.flag_count = nullptr; a.remap = nullptr; a.n_remap = nullptr; a.persist = nullptr; a.persist_stride = 0;
     a.is_replay = 0; a.order = nullptr; a.dbg = nullptr; a.dbg_slots = 0;
     a.se_slots = nullptr; a.se_n_slots = 0; a.se_spec = nullptr; a.se_spec_cap = 0; a.se_ctl = nullptr; a.se_eager = 0; a.se_keep = 1;
-    a.front_clip = ctx->clip_front; a.data_len = ctx->clip_len; a.skip = ctx->clip_skip;
+    a.front_clip = clip ? clip->front_clip : nullptr; a.data_len = clip ? clip->data_len : nullptr; a.skip = clip ? clip->skip : nullptr;
     const bool use_help = ctx->single_help && ctx->d_se_slots && !d_n_secondary &&
                           (ctx->single_help_forced == 1 || (ctx->feeders && ctx->feeders->load() <= 1));
     if (use_help) {                                                       // (fresh protocol state for the launch that is about to start)
@@ -1736,7 +1740,8 @@ static int launch_align(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const
     uint32_t blocks = ctx->n_wave_slots / 4;
     uint32_t need = (n + 3) / 4; if (blocks > need) blocks = need;
     HIPCHK(ctx, hipEventRecord(ctx->ev0, s), SNAPGPU_E_LAUNCH);
-    const bool heavy_first = ctx->single_heavy_first == 1 || (ctx->single_heavy_first < 0 && ctx->feeders && ctx->feeders->load() <= 1);
+    const bool heavy_first = !(clip && clip->gathered) &&
+                             (ctx->single_heavy_first == 1 || (ctx->single_heavy_first < 0 && ctx->feeders && ctx->feeders->load() <= 1));
     if (heavy_first && n > ctx->n_wave_slots) {                 // (inside the timed region: it is part of the pass)
         const int orc = launch_unit_order(ctx, d_bases, d_offsets, n, ctx->cfg.max_hits, s);
         if (orc) return orc;
@@ -1861,8 +1866,9 @@ static uint32_t paired_grid_share(const snapgpu_ctx *ctx, uint32_t all_blocks) {
 }
 
 static int launch_paired(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, const void *d_quals, const void *d_offsets,
-                         void *d_primary, void *d_first_alt, hipStream_t s, const PairedSecOut *so = nullptr)
+                         void *d_primary, void *d_first_alt, hipStream_t s, const ClipWindow *clip = nullptr, const PairedSecOut *so = nullptr)
 {
+    if (so && clip) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "launch_paired: the kernels with secondary results take clipped reads");
     PairedArgs a = so ? ctx->pargs_sec : ctx->pargs;
     a.ix = ctx->ix;                    // (the device-native tables may have been (re)built since snapgpu_enable_paired)
     if (so) {
@@ -1873,7 +1879,7 @@ static int launch_paired(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, cons
     a.bases = (const uint8_t *)d_bases; a.quals = (const uint8_t *)d_quals; a.offsets = (const uint64_t *)d_offsets;
     a.n_pairs = n; a.primary = (snapgpu_paired_result *)d_primary; a.first_alt = (snapgpu_paired_result *)d_first_alt;
     a.work_counter = ctx->d_work; a.counters = ctx->d_counters;
-    a.front_clip = so ? nullptr : ctx->clip_front; a.data_len = so ? nullptr : ctx->clip_len; a.skip = so ? nullptr : ctx->clip_skip;      // (snapgpu_align_sam_paired: the batch is unclipped)
+    a.front_clip = clip ? clip->front_clip : nullptr; a.data_len = clip ? clip->data_len : nullptr; a.skip = clip ? clip->skip : nullptr;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, s), SNAPGPU_E_LAUNCH);
     if (const int frc = ensure_flag_list(ctx, n)) return frc;
     uint32_t blocks = paired_grid_share(ctx, (so ? ctx->p_sec_slots : ctx->p_wave_slots) / 4);
@@ -1966,7 +1972,7 @@ static int launch_paired(snapgpu_ctx *ctx, uint32_t n, const void *d_bases, cons
 static uint32_t samf_blocks_per_cu() { static int v = 0; if (!v) { const char *e = getenv("SNAPGPU_SAMF_BLOCKS_PER_CU"); v = e ? atoi(e) : 8; if (v < 1 || v > 8) v = 8; } return (uint32_t)v; }
 
 // The SAM-field kernels (sam_fields.h, cigar_k.hip) for reads of up to RL bases: dynamic LDS of a workgroup of four waves, the persistent grid
-// (n_units: reads, or pairs) and the per-wave scratch: the read and its reverse complement, the Landau-Vishkin and the affine-gap CIGAR state.
+// (n_units: reads, or pairs) and the per-wave scratch (cigar_k.hip: samf_scratch_layout).
 struct SamfGeom { uint32_t RL, blocks; size_t lds; uint64_t scratch_stride; };
 static int samf_geometry(snapgpu_ctx *ctx, const char *who, uint32_t RL, uint32_t n_units, SamfGeom *g)
 {
@@ -1975,30 +1981,29 @@ static int samf_geometry(snapgpu_ctx *ctx, const char *who, uint32_t RL, uint32_
     if (g->lds > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, std::string(who) + ": reads too long for the LDS rows");
     g->blocks = (uint32_t)ctx->num_cus * samf_blocks_per_cu();
     const uint32_t need = (n_units + 3) / 4; if (g->blocks > need) g->blocks = need;
-    g->scratch_stride = ((2 * (uint64_t)RL + 255) & ~(uint64_t)255) + ((lvc_scratch_bytes() + 255) & ~255u) + ((agc_scratch_bytes(RL) + 255) & ~(uint64_t)255);
+    g->scratch_stride = snapgpu_samf_scratch_stride(RL);
     return SNAPGPU_OK;
 }
 
-// device pointers that SamFieldsArgs and SamFieldsPairedArgs have in common (results: snapgpu_single_result per read, or snapgpu_paired_result per pair)
-struct SamfBufs {
-    const void *bases, *quals, *offsets, *front_clip, *data_len, *results;
-    void *flag, *contig, *pos, *mapq, *ops, *n_ops, *nm, *stale;
-};
+// the reads and the per-item outputs of a SAM-field launch (device pointers) into its arguments
+static void samf_reads(SamFieldsCommon &a, const void *bases, const void *quals, const void *offsets, const void *front_clip, const void *data_len)
+{
+    a.bases = (const uint8_t *)bases; a.quals = (const uint8_t *)quals; a.offsets = (const uint64_t *)offsets;
+    a.front_clip = (const int32_t *)front_clip; a.data_len = (const int32_t *)data_len;
+}
+static void samf_outputs(SamFieldsCommon &a, void *flag, void *contig, void *pos, void *mapq, void *ops, void *n_ops, void *nm, void *stale)
+{
+    a.flag = (int32_t *)flag; a.contig = (int32_t *)contig; a.pos = (int64_t *)pos; a.mapq = (int32_t *)mapq;
+    a.ops = (uint32_t *)ops; a.n_ops = (int32_t *)n_ops; a.nm = (int32_t *)nm; a.stale = (int32_t *)stale;
+}
 
-// The banded row loops of a batch's records ahead of the records themselves, eight reads to a wavefront (cigar_ag.h: SamfPre, cigar_k.hip:
-// k_samf_dp8, k_samf_dp8_paired for the mates of a paired batch): fills a.pre / a.pre_stride / a.pre_counter and launches the kernel on the call's stream; the per-read results live in the
+// The banded row loops of a launch's n_items records ahead of the records themselves, eight to a wavefront (cigar_ag.h: SamfPre, cigar_k.hip:
+// k_samf_dp8*): fills a.pre / a.pre_stride / a.pre_counter and launches the kernel on the call's stream; the per-item results live in the
 // call's Stage.  SNAPGPU_SAMF_DP8=0 (measurement knob) or reads beyond 400 bp: nothing is launched and a.pre stays NULL.
 static bool samf_dp8_enabled() { static int v = -1; if (v < 0) { const char *e = getenv("SNAPGPU_SAMF_DP8"); v = e ? (atoi(e) != 0 ? 1 : 0) : 1; } return v == 1; }
-static uint32_t samf_n_reads(const SamFieldsArgs &a) { return a.n; }
-static uint32_t samf_n_reads(const SamFieldsPairedArgs &a) { return 2 * a.n_pairs; }                 // (one SamfPre per mate)
-static void samf_dp8_kernel(const SamFieldsArgs &a, uint32_t blocks, size_t lds, hipStream_t s) { snapgpu_launch_samf_dp8(&a, blocks, lds, s); }
-static void samf_dp8_kernel(const SamFieldsPairedArgs &a, uint32_t blocks, size_t lds, hipStream_t s) { snapgpu_launch_samf_dp8_paired(&a, blocks, lds, s); }
-static uint32_t samf_n_reads(const SamFieldsRecArgs &a) { return a.n; }                             // (one SamfPre per record)
-static void samf_dp8_kernel(const SamFieldsRecArgs &a, uint32_t blocks, size_t lds, hipStream_t s) { snapgpu_launch_samf_dp8_rec(&a, blocks, lds, s); }
 template <class A>
-static int launch_samf_dp8(snapgpu_ctx *ctx, A &a, Stage &st)
+static int launch_samf_dp8(snapgpu_ctx *ctx, A &a, uint32_t n, Stage &st)
 {
-    const uint32_t n = samf_n_reads(a);
     a.pre = nullptr; a.pre_stride = 0; a.pre_counter = ctx->d_work + 2; a.pre_valid = ctx->d_work + 8;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_work + 8, 0, 4, st.s), SNAPGPU_E_LAUNCH);          // (snapgpu_debug_samf_pre_valid: 0 when nothing is launched)
     if (!samf_dp8_enabled() || !a.use_affine_gap || a.RL > 400 || n == 0) return SNAPGPU_OK;
@@ -2016,48 +2021,27 @@ static int launch_samf_dp8(snapgpu_ctx *ctx, A &a, Stage &st)
     uint32_t blocks = (uint32_t)ctx->num_cus * per_cu;
     const uint32_t need = (n + 31) / 32; if (blocks > need) blocks = need;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_work + 2, 0, 4, st.s), SNAPGPU_E_LAUNCH);
-    samf_dp8_kernel(a, blocks, lds, st.s);
+    snapgpu_launch_samf_dp8(a, blocks, lds, st.s);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
     return SNAPGPU_OK;
 }
-static int samf_kernels(snapgpu_ctx *ctx, SamFieldsArgs &a, const SamfGeom &g, Stage &st)
-{
-    if (const int rc = launch_samf_dp8(ctx, a, st)) return rc;
-    snapgpu_launch_sam_fields(&a, g.blocks, g.lds, st.s);
-    return SNAPGPU_OK;
-}
-static int samf_kernels(snapgpu_ctx *ctx, SamFieldsRecArgs &a, const SamfGeom &g, Stage &st)
-{
-    if (const int rc = launch_samf_dp8(ctx, a, st)) return rc;
-    snapgpu_launch_sam_fields_rec(&a, g.blocks, g.lds, st.s);
-    return SNAPGPU_OK;
-}
-static int samf_kernels(snapgpu_ctx *ctx, SamFieldsPairedArgs &a, const SamfGeom &g, Stage &st)
-{
-    if (const int rc = launch_samf_dp8(ctx, a, st)) return rc;
-    snapgpu_launch_sam_fields_paired(&a, g.blocks, g.lds, st.s);
-    return SNAPGPU_OK;
-}
 
-// The SAM-field launch of a call, single (A = SamFieldsArgs, a.n set) or paired (SamFieldsPairedArgs, a.n_pairs and the pair fields set), over
-// n_reads reads already in HBM: the scratch slab into the call's Stage, the fields the two argument structs share, the cleared CIGAR
-// buffer and work counter, and the kernels between ev0 and ev1.  The caller synchronises (or downloads) and calls finish_timing.
+// The SAM-field launch of a call over n_items items already in HBM (a: its reads, outputs and tail set): the scratch slab into the call's
+// Stage, the rest of the shared arguments, the cleared CIGAR buffer and work counter, and the kernels between ev0 and ev1.  The caller
+// synchronises (or downloads) and calls finish_timing.
 template <class A>
-static int launch_sam_fields(snapgpu_ctx *ctx, A &a, const SamfGeom &g, const SamfBufs &b, uint32_t n_reads, uint32_t ops_stride, int use_m, Stage &st)
+static int launch_sam_fields(snapgpu_ctx *ctx, A &a, const SamfGeom &g, uint32_t n_items, uint32_t ops_stride, int use_m, Stage &st)
 {
     a.scratch = st.scratch((size_t)g.blocks * 4 * g.scratch_stride);
     if (st.rc) return st.rc;
     a.ix = ctx->ix; a.prm = agc_params(ctx);
     a.RL = g.RL; a.ops_stride = ops_stride; a.use_m = use_m ? 1u : 0u; a.use_affine_gap = ctx->params.use_affine_gap ? 1u : 0u;
-    a.bases = (const uint8_t *)b.bases; a.quals = (const uint8_t *)b.quals; a.offsets = (const uint64_t *)b.offsets;
-    a.front_clip = (const int32_t *)b.front_clip; a.data_len = (const int32_t *)b.data_len; a.results = (decltype(a.results))b.results;
     a.scratch_stride = g.scratch_stride; a.work_counter = ctx->d_work;
-    a.flag = (int32_t *)b.flag; a.contig = (int32_t *)b.contig; a.pos = (int64_t *)b.pos; a.mapq = (int32_t *)b.mapq;
-    a.ops = (uint32_t *)b.ops; a.n_ops = (int32_t *)b.n_ops; a.nm = (int32_t *)b.nm; a.stale = (int32_t *)b.stale;
-    HIPCHK(ctx, hipMemsetAsync(b.ops, 0, (size_t)n_reads * ops_stride * 4, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemsetAsync(a.ops, 0, (size_t)n_items * ops_stride * 4, st.s), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipMemsetAsync(ctx->d_work, 0, 4, st.s), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
-    if (const int rc = samf_kernels(ctx, a, g, st)) return rc;
+    if (const int rc = launch_samf_dp8(ctx, a, n_items, st)) return rc;
+    snapgpu_launch_sam_fields(a, g.blocks, g.lds, st.s);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
     return SNAPGPU_OK;
@@ -2361,38 +2345,55 @@ extern "C" int snapgpu_compute_cigar_ag(snapgpu_ctx *ctx, uint32_t n, const char
     return timed_launch_and_download(ctx, st, [&] { snapgpu_launch_cigar_ag(&a, blocks, lds, st.s); });
 }
 
-// result -> FLAG / RNAME index / POS / MAPQ / CIGAR / NM of the SAM record (sam_fields.h, cigar_k.hip)
+// result -> FLAG / RNAME index / POS / MAPQ / CIGAR / NM of the SAM record (sam_fields.h, cigar_k.hip), for `who` = snapgpu_sam_fields_single
+// (host: every pointer is a host array; the reads are checked, staged and the fields downloaded) or its device-pointer form (reads, clipping
+// and results already in HBM, e.g. right after snapgpu_align_single_device, outputs left in HBM; max_read_len sizes the per-wave LDS rows and
+// the scratch slab, which goes back to the pool on return: the call synchronises whatever the stream).
+static int sam_fields_single_call(snapgpu_ctx *ctx, const char *who, bool host, uint32_t n, uint32_t max_read_len, const void *bases, const void *quals,
+                                  const void *offsets, const void *front_clip, const void *data_len, const void *results, int use_m,
+                                  void *flag, void *contig, void *pos, void *mapq, void *ops, uint32_t ops_stride, void *n_ops, void *nm, void *stale, void *stream)
+{
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, std::string(who) + ": ops_stride must be at least 3");
+    if (!host && (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH)) return fail(ctx, SNAPGPU_E_INVALID, std::string(who) + ": max_read_len out of range");
+    if (n == 0) return SNAPGPU_OK;
+    int rc;
+    uint32_t RL = max_read_len < 64 ? 64 : max_read_len;
+    const snapgpu_single_result *h_results = (const snapgpu_single_result *)results;
+    if (host && (rc = check_sam_reads(ctx, who, n, (const uint64_t *)offsets, (const int32_t *)front_clip, (const int32_t *)data_len, &RL,
+                                      [&](uint32_t i) { return check_location(ctx, who, h_results[i].status, h_results[i].location); }))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    SamfGeom g;
+    if ((rc = samf_geometry(ctx, who, RL, n, &g))) return rc;
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    if (host) {
+        const size_t total = ((const uint64_t *)offsets)[n], n4 = (size_t)n * 4;
+        bases = st.in(bases, total); quals = st.in(quals, total); offsets = st.in(offsets, (size_t)(n + 1) * 8);
+        front_clip = st.in(front_clip, n4); data_len = st.in(data_len, n4); results = st.in(results, (size_t)n * sizeof(snapgpu_single_result));
+        flag = st.out(flag, n4); contig = st.out(contig, n4); pos = st.out(pos, (size_t)n * 8); mapq = st.out(mapq, n4); ops = st.out(ops, n4 * ops_stride);
+        n_ops = st.out(n_ops, n4); nm = st.out(nm, n4); stale = st.out(stale, n4);
+        if (st.rc) return st.rc;
+    }
+    SamFieldsArgs a; a.n = n; a.results = (const snapgpu_single_result *)results;
+    samf_reads(a, bases, quals, offsets, front_clip, data_len);
+    samf_outputs(a, flag, contig, pos, mapq, ops, n_ops, nm, stale);
+    if ((rc = launch_sam_fields(ctx, a, g, n, ops_stride, use_m, st))) return rc;
+    if (host) { if ((rc = st.download())) return rc; }
+    else HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    return finish_timing(ctx);
+}
+
 extern "C" int snapgpu_sam_fields_single(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
                                          const int32_t *front_clip, const int32_t *data_len, const snapgpu_single_result *results, int use_m,
                                          int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
                                          int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent)
 {
-    const char *who = "snapgpu_sam_fields_single";
     if (!ctx || (n && (!bases || !quals || !offsets || !front_clip || !data_len || !results || !flag || !contig || !pos || !mapq || !ops || !n_ops ||
                        !nm || !reference_history_dependent)))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single: ops_stride must be at least 3");
-    if (n == 0) return SNAPGPU_OK;
-    SamfGeom g; uint32_t RL;
-    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL,
-                             [&](uint32_t i) { return check_location(ctx, who, results[i].status, results[i].location); });
-    if (rc) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    if ((rc = samf_geometry(ctx, who, RL, n, &g))) return rc;
-    Stage st(ctx, ctx->stream);
-    const size_t total = offsets[n], n4 = (size_t)n * 4;
-    const SamfBufs b{st.in(bases, total), st.in(quals, total), st.in(offsets, (size_t)(n + 1) * 8), st.in(front_clip, n4), st.in(data_len, n4),
-                     st.in(results, (size_t)n * sizeof(snapgpu_single_result)),
-                     st.out(flag, n4), st.out(contig, n4), st.out(pos, (size_t)n * 8), st.out(mapq, n4), st.out(ops, n4 * ops_stride), st.out(n_ops, n4),
-                     st.out(nm, n4), st.out(reference_history_dependent, n4)};
-    if (st.rc) return st.rc;
-    SamFieldsArgs a; a.n = n;
-    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
-    return finish_timing(ctx);
+    return sam_fields_single_call(ctx, "snapgpu_sam_fields_single", true, n, 0, bases, quals, offsets, front_clip, data_len, results, use_m,
+                                  flag, contig, pos, mapq, ops, ops_stride, n_ops, nm, reference_history_dependent, nullptr);
 }
 
-// device-pointer form of snapgpu_sam_fields_single: reads, clipping and results already in HBM (e.g. right after
-// snapgpu_align_single_device), outputs left in HBM.  max_read_len sizes the per-wave LDS rows and the scratch slab.
 extern "C" int snapgpu_sam_fields_single_device(snapgpu_ctx *ctx, uint32_t n, uint32_t max_read_len, const void *d_bases, const void *d_quals,
                                                 const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_results, int use_m,
                                                 void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
@@ -2401,20 +2402,8 @@ extern "C" int snapgpu_sam_fields_single_device(snapgpu_ctx *ctx, uint32_t n, ui
     if (!ctx || (n && (!d_bases || !d_quals || !d_offsets || !d_front_clip || !d_data_len || !d_results || !d_flag || !d_contig || !d_pos || !d_mapq ||
                        !d_ops || !d_n_ops || !d_nm || !d_reference_history_dependent)))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: ops_stride must be at least 3");
-    if (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_single_device: max_read_len out of range");
-    if (n == 0) return SNAPGPU_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    SamfGeom g;
-    int rc = samf_geometry(ctx, "snapgpu_sam_fields_single_device", max_read_len < 64 ? 64 : max_read_len, n, &g);
-    if (rc) return rc;
-    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
-    const SamfBufs b{d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_results, d_flag, d_contig, d_pos, d_mapq, d_ops, d_n_ops, d_nm,
-                     d_reference_history_dependent};
-    SamFieldsArgs a; a.n = n;
-    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);           // (the scratch slab goes back to the pool on return; a caller-owned slab is the next step)
-    return finish_timing(ctx);
+    return sam_fields_single_call(ctx, "snapgpu_sam_fields_single_device", false, n, max_read_len, d_bases, d_quals, d_offsets, d_front_clip, d_data_len,
+                                  d_results, use_m, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_reference_history_dependent, stream);
 }
 
 // The single-end path of a SAM writer in one call, device-resident in between: ONE upload of the batch (the unclipped reads, Read::clip's
@@ -2447,18 +2436,16 @@ extern "C" int snapgpu_align_sam_single(snapgpu_ctx *ctx, uint32_t n, const char
     const size_t n4 = (size_t)n * 4, rb = (size_t)n * sizeof(snapgpu_single_result);
     const void *d_bases = bases, *d_quals = quals, *d_offsets = offsets;
     stage_reads(st, d_bases, d_quals, d_offsets, n);
-    const void *d_front_clip = st.in(front_clip, n4), *d_data_len = st.in(data_len, n4), *d_skip = st.in(skip, n);
+    const ClipWindow clip{st.in(front_clip, n4), st.in(data_len, n4), st.in(skip, n), false};
     void *d_results = st.out(results, rb), *d_first_alt = st.opt_out(first_alt, rb);
-    const SamfBufs b{d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_results,
-                     st.out(flag, n4), st.out(contig, n4), st.out(pos, (size_t)n * 8), st.out(mapq, n4), st.out(ops, n4 * ops_stride), st.out(n_ops, n4),
-                     st.out(nm, n4), st.out(reference_history_dependent, n4)};
+    SamFieldsArgs a; a.n = n; a.results = (const snapgpu_single_result *)d_results;
+    samf_reads(a, d_bases, d_quals, d_offsets, clip.front_clip, clip.data_len);
+    // (member by member, not through samf_outputs: statements keep the outputs in the order of the argument list, which is the order they come back in)
+    a.flag = st.out(flag, n4); a.contig = st.out(contig, n4); a.pos = st.out(pos, (size_t)n * 8); a.mapq = st.out(mapq, n4); a.ops = st.out(ops, n4 * ops_stride);
+    a.n_ops = st.out(n_ops, n4); a.nm = st.out(nm, n4); a.stale = st.out(reference_history_dependent, n4);
     if (st.rc) return st.rc;
-    ctx->clip_front = (const int32_t *)d_front_clip; ctx->clip_len = (const int32_t *)d_data_len; ctx->clip_skip = (const uint8_t *)d_skip;
-    rc = launch_align(ctx, n, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s);
-    ctx->clip_front = ctx->clip_len = nullptr; ctx->clip_skip = nullptr;
-    if (rc || (rc = finish_timing(ctx))) return rc;                // (the align launch's own hipEvent time, before the events are reused)
-    SamFieldsArgs a; a.n = n;
-    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
+    if ((rc = launch_align(ctx, n, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s, &clip)) || (rc = finish_timing(ctx))) return rc;      // (the align launch's own hipEvent time, before the events are reused)
+    if ((rc = launch_sam_fields(ctx, a, g, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
     return finish_timing(ctx);
 }
 
@@ -2498,10 +2485,9 @@ static int sam_records_core(snapgpu_ctx *ctx, const char *who, Stage &st, uint32
 
     // ---- BaseAligner::AlignRead over the clipped reads (a read that is skipped gets no secondary count from the kernel: it has none)
     if (sec) HIPCHK(ctx, hipMemsetAsync(io.n_secondary, 0, (size_t)n * 4, s), SNAPGPU_E_LAUNCH);
-    ctx->clip_front = ra.front_clip; ctx->clip_len = ra.data_len; ctx->clip_skip = (const uint8_t *)io.skip;
-    rc = launch_align(ctx, n, io.bases, io.quals, io.offsets, io.primary, io.first_alt, s, sec ? io.secondary : nullptr, sec ? io.sec_stride : 0,
+    const ClipWindow clip{ra.front_clip, ra.data_len, (const uint8_t *)io.skip, false};
+    rc = launch_align(ctx, n, io.bases, io.quals, io.offsets, io.primary, io.first_alt, s, &clip, sec ? io.secondary : nullptr, sec ? io.sec_stride : 0,
                       sec ? io.n_secondary : nullptr);
-    ctx->clip_front = ctx->clip_len = nullptr; ctx->clip_skip = nullptr;
     if (rc || (rc = finish_timing(ctx))) return rc;
     // ---- -ae without -om: finalizeSecondaryResults has only the primary to adjust (BaseAligner.cpp:2444-2452; a context with secondary results
     // adjusted inside the align kernel)
@@ -2538,11 +2524,8 @@ static int sam_records_core(snapgpu_ctx *ctx, const char *who, Stage &st, uint32
         HIPCHK(ctx, hipMemsetAsync(ovf, 0, mb * stride, s), SNAPGPU_E_LAUNCH);          // (a row the rerun did not fill would read as NotFound, and k_samrec_list checks its counts)
         snapgpu_launch_samrec_gather(&ra, m, s);
         HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-        const int heavy = ctx->single_heavy_first; ctx->single_heavy_first = 0;          // (the gathered offsets do not delimit the reads: no weights from them)
-        ctx->clip_front = ra.ovf_front_clip; ctx->clip_len = ra.ovf_data_len; ctx->clip_skip = nullptr;
-        rc = launch_align(ctx, m, io.bases, io.quals, ra.ovf_offsets, p2, a2, s, ovf, stride, ns2);
-        ctx->clip_front = ctx->clip_len = nullptr; ctx->single_heavy_first = heavy;
-        if (rc || (rc = finish_timing(ctx))) return rc;
+        const ClipWindow again{ra.ovf_front_clip, ra.ovf_data_len, nullptr, true};
+        if ((rc = launch_align(ctx, m, io.bases, io.quals, ra.ovf_offsets, p2, a2, s, &again, ovf, stride, ns2)) || (rc = finish_timing(ctx))) return rc;
     }
     // ---- the record list, then the fields of the records the caller has room for
     snapgpu_launch_samrec_list(&ra, lb, s);
@@ -2557,9 +2540,10 @@ static int sam_records_core(snapgpu_ctx *ctx, const char *who, Stage &st, uint32
     if (n_fmt > 0xFFFFFFFFull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 records in one call");
     SamfGeom g;
     if ((rc = samf_geometry(ctx, who, RL, (uint32_t)n_fmt, &g))) return rc;
-    const SamfBufs b{io.bases, io.quals, io.offsets, io.front_clip, io.data_len, io.primary, io.flag, io.contig, io.pos, io.mapq, io.ops, io.n_ops, io.nm, io.stale};
     SamFieldsRecArgs a; a.n = (uint32_t)n_fmt; a.src = ra.src;
-    if ((rc = launch_sam_fields(ctx, a, g, b, (uint32_t)n_fmt, ops_stride, use_m, st))) return rc;
+    samf_reads(a, io.bases, io.quals, io.offsets, io.front_clip, io.data_len);
+    samf_outputs(a, io.flag, io.contig, io.pos, io.mapq, io.ops, io.n_ops, io.nm, io.stale);
+    if ((rc = launch_sam_fields(ctx, a, g, (uint32_t)n_fmt, ops_stride, use_m, st))) return rc;
     return copy_refused();
 }
 
@@ -2567,6 +2551,78 @@ static int sam_records_core(snapgpu_ctx *ctx, const char *who, Stage &st, uint32
 static uint32_t samrec_first_stride(const snapgpu_ctx *ctx) { const int64_t m = ctx->sec_cfg.omax; return (uint32_t)(m < 1 ? 1 : (m < 8 ? m : 8)); }
 static const char *const RERUN_MISMATCH_MSG = "snapgpu_align_sam_single_records: the rerun of a read found a different number of secondary results than its first pass";
 static const char *const AE_CLIPPED_MSG = "-ae: a read the reader clipped reaches the end of its contig, which the adjuster does not reproduce (see snapgpu_adjust_alignments)";
+
+// snapgpu_align_sam_single_records (host: every pointer but n_records is a host array; the reads are checked and staged, and only the
+// formatted records come down) or its device-pointer form (reads, Read::clip's outcome and every output in HBM; results .. n_secondary may
+// be NULL: not wanted; max_read_len as in snapgpu_sam_fields_single_device; synchronous on `stream`, NULL: the context's).
+static int sam_records_call(snapgpu_ctx *ctx, const char *who, bool host, uint32_t n, uint32_t max_read_len, const void *bases, const void *quals,
+                            const void *offsets, const void *front_clip, const void *data_len, const void *skip, int use_m, int adjust_primary,
+                            void *results, void *first_alt, void *secondary, uint32_t secondary_stride, void *n_secondary, uint64_t cap,
+                            uint64_t *n_records, void *rec_begin, void *rec_read, void *rec_kind, void *flag, void *contig, void *pos, void *mapq,
+                            void *ops, uint32_t ops_stride, void *n_ops, void *nm, void *stale, void *stream)
+{
+    const std::string w(who);
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, w + ": ops_stride must be at least 3");
+    if (!host && (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH)) return fail(ctx, SNAPGPU_E_INVALID, w + ": max_read_len out of range");
+    if (ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, w + ": a single-end context is needed (no snapgpu_enable_paired)");
+    if (adjust_primary && ctx->secondary && !ctx->sec_cfg.adjust)
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": a context with secondary results takes -ae from snapgpu_enable_secondary (adjust_alignments)");
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    *n_records = 0;
+    if (host) *(uint64_t *)rec_begin = 0;
+    if (n == 0) {                                       // rec_begin[0] = 0 in the device form too
+        if (host || !rec_begin) return SNAPGPU_OK;
+        HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+        HIPCHK(ctx, hipMemsetAsync(rec_begin, 0, 8, s), SNAPGPU_E_LAUNCH);
+        HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
+        return SNAPGPU_OK;
+    }
+    int rc;
+    uint32_t RL = max_read_len < 64 ? 64 : max_read_len;
+    if (host && (rc = check_sam_reads(ctx, who, n, (const uint64_t *)offsets, (const int32_t *)front_clip, (const int32_t *)data_len, &RL, [&](uint32_t i) {
+        if (!((const uint8_t *)skip)[i] && (uint32_t)((const int32_t *)data_len)[i] > ctx->params.max_read_len)
+            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (BaseAligner.cpp:354-358)");
+        return (int)SNAPGPU_OK;
+    }))) return rc;
+    if ((size_t)4 * agc_lds_bytes(RL) > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": reads too long for the LDS rows");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, s);
+    const bool sec = ctx->secondary;
+    const size_t n4 = (size_t)n * 4, rb = (size_t)n * sizeof(snapgpu_single_result), c4 = (size_t)cap * 4;
+    // a per-read output the caller may not want (NULL: an internal buffer), and a per-record output (the host form's comes down; NULL: a device-only buffer)
+    auto per_read = [&](void *p, size_t bytes, size_t slack = 0) -> void * { return host ? (void *)st.out(p, bytes, slack) : p ? p : (void *)st.scratch(bytes + slack); };
+    auto per_record = [&](void *p, size_t bytes) -> void * { return host ? (void *)st.out(p, bytes) : p; };
+    SamRecIO io;
+    io.bases = bases; io.quals = quals; io.offsets = offsets; io.front_clip = front_clip; io.data_len = data_len; io.skip = skip;
+    if (host) {
+        stage_reads(st, io.bases, io.quals, io.offsets, n);
+        io.front_clip = st.in(front_clip, n4); io.data_len = st.in(data_len, n4); io.skip = st.in(skip, n);
+    }
+    io.primary = per_read(results, rb); io.first_alt = per_read(first_alt, rb);
+    io.sec_stride = secondary ? secondary_stride : samrec_first_stride(ctx);
+    io.secondary = nullptr; io.n_secondary = nullptr;
+    const size_t sec_bytes = (size_t)n * io.sec_stride * sizeof(snapgpu_single_result);
+    if (sec) { io.secondary = per_read(secondary, sec_bytes, 16); io.n_secondary = per_read(n_secondary, n4); }
+    io.rec_begin = per_record(rec_begin, (size_t)(n + 1) * 8); io.rec_read = per_record(rec_read, c4); io.rec_kind = per_record(rec_kind, (size_t)cap);
+    io.flag = per_record(flag, c4); io.contig = per_record(contig, c4); io.pos = per_record(pos, (size_t)cap * 8); io.mapq = per_record(mapq, c4);
+    io.ops = per_record(ops, c4 * ops_stride); io.n_ops = per_record(n_ops, c4); io.nm = per_record(nm, c4); io.stale = per_record(stale, c4);
+    if (st.rc) return st.rc;
+    if (host && sec && secondary) HIPCHK(ctx, hipMemsetAsync(io.secondary, 0, sec_bytes, st.s), SNAPGPU_E_LAUNCH);
+    if (!sec && n_secondary) { if (host) memset(n_secondary, 0, n4); else HIPCHK(ctx, hipMemsetAsync(n_secondary, 0, n4, st.s), SNAPGPU_E_LAUNCH); }
+    SamRecSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = sam_records_core(ctx, who, st, n, RL, io, cap, ops_stride, use_m, adjust_primary != 0, &sum))) return rc;
+    const size_t f = (size_t)(sum.total < cap ? sum.total : cap);                                    // the records that were formatted
+    if (host) {                                                                                      // only they come down
+        st.limit(io.rec_read, f * 4); st.limit(io.rec_kind, f); st.limit(io.flag, f * 4); st.limit(io.contig, f * 4); st.limit(io.pos, f * 8); st.limit(io.mapq, f * 4);
+        st.limit(io.ops, f * 4 * ops_stride); st.limit(io.n_ops, f * 4); st.limit(io.nm, f * 4); st.limit(io.stale, f * 4);
+        if ((rc = st.download())) return rc;
+    } else HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    if (f && (rc = finish_timing(ctx))) return rc;
+    *n_records = sum.total;
+    if (sum.refused & SAMREC_RERUN_MISMATCH) return fail(ctx, SNAPGPU_E_LAUNCH, RERUN_MISMATCH_MSG);
+    if (sum.refused & SAMREC_AE_CLIPPED) return fail(ctx, SNAPGPU_E_UNSUPPORTED, AE_CLIPPED_MSG);
+    return sum.total > cap ? SNAPGPU_W_RECORDS_TRUNCATED : SNAPGPU_OK;
+}
 
 extern "C" int snapgpu_align_sam_single_records(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
                                                 const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
@@ -2576,60 +2632,15 @@ extern "C" int snapgpu_align_sam_single_records(snapgpu_ctx *ctx, uint32_t n, co
                                                 int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
                                                 int32_t *n_ops, int32_t *nm, int32_t *reference_history_dependent)
 {
-    const char *who = "snapgpu_align_sam_single_records";
     if (!ctx || !n_records || !rec_begin || (n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip)) ||
         (n && record_capacity && (!rec_read || !rec_kind || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm || !reference_history_dependent)) ||
         (secondary && secondary_stride == 0))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records: ops_stride must be at least 3");
-    if (ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records: a single-end context is needed (no snapgpu_enable_paired)");
-    if (adjust_primary && ctx->secondary && !ctx->sec_cfg.adjust)
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records: a context with secondary results takes -ae from snapgpu_enable_secondary (adjust_alignments)");
-    *n_records = 0; rec_begin[0] = 0;
-    if (n == 0) return SNAPGPU_OK;
-    uint32_t RL;
-    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
-        if (!skip[i] && (uint32_t)data_len[i] > ctx->params.max_read_len)
-            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (BaseAligner.cpp:354-358)");
-        return (int)SNAPGPU_OK;
-    });
-    if (rc) return rc;
-    if ((size_t)4 * agc_lds_bytes(RL) > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, std::string(who) + ": reads too long for the LDS rows");
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    Stage st(ctx, ctx->stream);
-    const bool sec = ctx->secondary;
-    const uint64_t cap = record_capacity;
-    const size_t n4 = (size_t)n * 4, rb = (size_t)n * sizeof(snapgpu_single_result), c4 = (size_t)cap * 4;
-    SamRecIO io;
-    io.bases = bases; io.quals = quals; io.offsets = offsets;
-    stage_reads(st, io.bases, io.quals, io.offsets, n);
-    io.front_clip = st.in(front_clip, n4); io.data_len = st.in(data_len, n4); io.skip = st.in(skip, n);
-    io.primary = st.out(results, rb); io.first_alt = st.out(first_alt, rb);                          // (a NULL host pointer: a device-only buffer)
-    io.sec_stride = secondary ? secondary_stride : samrec_first_stride(ctx);
-    io.secondary = nullptr; io.n_secondary = nullptr;
-    const size_t sec_bytes = (size_t)n * io.sec_stride * sizeof(snapgpu_single_result);
-    if (sec) { io.secondary = st.out(secondary, sec_bytes, 16); io.n_secondary = st.out(n_secondary, n4); }
-    io.rec_begin = st.out(rec_begin, (size_t)(n + 1) * 8); io.rec_read = st.out(rec_read, c4); io.rec_kind = st.out(rec_kind, (size_t)cap);
-    io.flag = st.out(flag, c4); io.contig = st.out(contig, c4); io.pos = st.out(pos, (size_t)cap * 8); io.mapq = st.out(mapq, c4);
-    io.ops = st.out(ops, c4 * ops_stride); io.n_ops = st.out(n_ops, c4); io.nm = st.out(nm, c4); io.stale = st.out(reference_history_dependent, c4);
-    if (st.rc) return st.rc;
-    if (sec && secondary) HIPCHK(ctx, hipMemsetAsync(io.secondary, 0, sec_bytes, st.s), SNAPGPU_E_LAUNCH);
-    if (!sec && n_secondary) memset(n_secondary, 0, n4);
-    SamRecSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_records_core(ctx, who, st, n, RL, io, cap, ops_stride, use_m, adjust_primary != 0, &sum))) return rc;
-    const size_t f = (size_t)(sum.total < cap ? sum.total : cap);                                    // the records that were formatted: only they come down
-    st.limit(io.rec_read, f * 4); st.limit(io.rec_kind, f); st.limit(io.flag, f * 4); st.limit(io.contig, f * 4); st.limit(io.pos, f * 8); st.limit(io.mapq, f * 4);
-    st.limit(io.ops, f * 4 * ops_stride); st.limit(io.n_ops, f * 4); st.limit(io.nm, f * 4); st.limit(io.stale, f * 4);
-    if ((rc = st.download())) return rc;
-    if (f && (rc = finish_timing(ctx))) return rc;
-    *n_records = sum.total;
-    if (sum.refused & SAMREC_RERUN_MISMATCH) return fail(ctx, SNAPGPU_E_LAUNCH, RERUN_MISMATCH_MSG);
-    if (sum.refused & SAMREC_AE_CLIPPED) return fail(ctx, SNAPGPU_E_UNSUPPORTED, AE_CLIPPED_MSG);
-    return sum.total > cap ? SNAPGPU_W_RECORDS_TRUNCATED : SNAPGPU_OK;
+    return sam_records_call(ctx, "snapgpu_align_sam_single_records", true, n, 0, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary,
+                            results, first_alt, secondary, secondary_stride, n_secondary, record_capacity, n_records, rec_begin, rec_read, rec_kind,
+                            flag, contig, pos, mapq, ops, ops_stride, n_ops, nm, reference_history_dependent, nullptr);
 }
 
-// device-pointer form: reads, Read::clip's outcome and every output in HBM (d_results .. d_n_secondary may be NULL: not wanted); *n_records is a
-// host word.  max_read_len as in snapgpu_sam_fields_single_device.  Synchronous on `stream` (NULL: the context's).
 extern "C" int snapgpu_align_sam_single_records_device(snapgpu_ctx *ctx, uint32_t n, uint32_t max_read_len, const void *d_bases, const void *d_quals,
                                                        const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_skip, int use_m,
                                                        int adjust_primary, void *d_results, void *d_first_alt, void *d_secondary, uint32_t secondary_stride,
@@ -2637,116 +2648,80 @@ extern "C" int snapgpu_align_sam_single_records_device(snapgpu_ctx *ctx, uint32_
                                                        void *d_rec_kind, void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
                                                        void *d_n_ops, void *d_nm, void *d_reference_history_dependent, void *stream)
 {
-    const char *who = "snapgpu_align_sam_single_records_device";
     if (!ctx || !n_records || (n && (!d_bases || !d_quals || !d_offsets || !d_front_clip || !d_data_len || !d_skip || !d_rec_begin)) ||
         (n && record_capacity && (!d_rec_read || !d_rec_kind || !d_flag || !d_contig || !d_pos || !d_mapq || !d_ops || !d_n_ops || !d_nm || !d_reference_history_dependent)) ||
         (d_secondary && secondary_stride == 0))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: ops_stride must be at least 3");
-    if (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: max_read_len out of range");
-    if (ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: a single-end context is needed (no snapgpu_enable_paired)");
-    if (adjust_primary && ctx->secondary && !ctx->sec_cfg.adjust)
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_records_device: a context with secondary results takes -ae from snapgpu_enable_secondary (adjust_alignments)");
-    *n_records = 0;
-    if (n == 0) {                                       // rec_begin[0] = 0, as the host form leaves it
-        if (!d_rec_begin) return SNAPGPU_OK;
-        hipStream_t s0 = stream ? (hipStream_t)stream : ctx->stream;
-        HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-        HIPCHK(ctx, hipMemsetAsync(d_rec_begin, 0, 8, s0), SNAPGPU_E_LAUNCH);
-        HIPCHK(ctx, hipStreamSynchronize(s0), SNAPGPU_E_LAUNCH);
-        return SNAPGPU_OK;
-    }
-    const uint32_t RL = max_read_len < 64 ? 64 : max_read_len;
-    if ((size_t)4 * agc_lds_bytes(RL) > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, std::string(who) + ": reads too long for the LDS rows");
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
-    const bool sec = ctx->secondary;
-    const size_t rb = (size_t)n * sizeof(snapgpu_single_result);
-    SamRecIO io;
-    io.bases = d_bases; io.quals = d_quals; io.offsets = d_offsets; io.front_clip = d_front_clip; io.data_len = d_data_len; io.skip = d_skip;
-    io.primary = d_results ? d_results : (void *)st.scratch(rb); io.first_alt = d_first_alt ? d_first_alt : (void *)st.scratch(rb);
-    io.sec_stride = d_secondary ? secondary_stride : samrec_first_stride(ctx);
-    io.secondary = nullptr; io.n_secondary = nullptr;
-    if (sec) {
-        io.secondary = d_secondary ? d_secondary : (void *)st.scratch((size_t)n * io.sec_stride * sizeof(snapgpu_single_result) + 16);
-        io.n_secondary = d_n_secondary ? d_n_secondary : (void *)st.scratch((size_t)n * 4);
-    } else if (d_n_secondary) HIPCHK(ctx, hipMemsetAsync(d_n_secondary, 0, (size_t)n * 4, st.s), SNAPGPU_E_LAUNCH);
-    io.rec_begin = d_rec_begin; io.rec_read = d_rec_read; io.rec_kind = d_rec_kind;
-    io.flag = d_flag; io.contig = d_contig; io.pos = d_pos; io.mapq = d_mapq; io.ops = d_ops; io.n_ops = d_n_ops; io.nm = d_nm; io.stale = d_reference_history_dependent;
-    if (st.rc) return st.rc;
-    SamRecSummary sum; memset(&sum, 0, sizeof(sum));
-    int rc = sam_records_core(ctx, who, st, n, RL, io, record_capacity, ops_stride, use_m, adjust_primary != 0, &sum);
-    if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
-    if (sum.total && record_capacity && (rc = finish_timing(ctx))) return rc;
-    *n_records = sum.total;
-    if (sum.refused & SAMREC_RERUN_MISMATCH) return fail(ctx, SNAPGPU_E_LAUNCH, RERUN_MISMATCH_MSG);
-    if (sum.refused & SAMREC_AE_CLIPPED) return fail(ctx, SNAPGPU_E_UNSUPPORTED, AE_CLIPPED_MSG);
-    return sum.total > record_capacity ? SNAPGPU_W_RECORDS_TRUNCATED : SNAPGPU_OK;
+    return sam_records_call(ctx, "snapgpu_align_sam_single_records_device", false, n, max_read_len, d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_skip,
+                            use_m, adjust_primary, d_results, d_first_alt, d_secondary, secondary_stride, d_n_secondary, record_capacity, n_records,
+                            d_rec_begin, d_rec_read, d_rec_kind, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_reference_history_dependent, stream);
 }
 
-// paired-end writer: results -> the computed fields of both SAM records of each pair (sam_fields.h, cigar_k.hip)
+// paired-end writer: results -> the computed fields of both SAM records of each pair (sam_fields.h, cigar_k.hip); host / max_read_len / stream as
+// sam_fields_single_call (the device form: e.g. right after snapgpu_align_paired_device)
+static int sam_fields_paired_call(snapgpu_ctx *ctx, const char *who, bool host, uint32_t n_pairs, uint32_t max_read_len, const void *bases, const void *quals,
+                                  const void *offsets, const void *front_clip, const void *data_len, const void *results, int use_m,
+                                  void *flag, void *contig, void *pos, void *mapq, void *ops, uint32_t ops_stride, void *n_ops, void *nm,
+                                  void *rnext, void *pnext, void *tlen, void *first_written, void *stale, void *stream)
+{
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, std::string(who) + ": ops_stride must be at least 3");
+    if (!host && (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH)) return fail(ctx, SNAPGPU_E_INVALID, std::string(who) + ": max_read_len out of range");
+    if (n_pairs == 0) return SNAPGPU_OK;
+    if (!host && n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, std::string(who) + ": too many pairs");
+    const uint32_t n = 2 * n_pairs;
+    int rc;
+    uint32_t RL = max_read_len < 64 ? 64 : max_read_len;
+    const snapgpu_paired_result *h_results = (const snapgpu_paired_result *)results;
+    if (host && (rc = check_sam_reads(ctx, who, n, (const uint64_t *)offsets, (const int32_t *)front_clip, (const int32_t *)data_len, &RL,
+                                      [&](uint32_t i) { return check_location(ctx, who, h_results[i >> 1].status[i & 1], h_results[i >> 1].location[i & 1]); }))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    SamfGeom g;
+    if ((rc = samf_geometry(ctx, who, RL, n_pairs, &g))) return rc;
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    if (host) {                                 // (the outputs come back in the order of the argument list)
+        const size_t total = ((const uint64_t *)offsets)[n], n4 = (size_t)n * 4, n8 = (size_t)n * 8;
+        bases = st.in(bases, total); quals = st.in(quals, total); offsets = st.in(offsets, (size_t)(n + 1) * 8);
+        front_clip = st.in(front_clip, n4); data_len = st.in(data_len, n4); results = st.in(results, (size_t)n_pairs * sizeof(snapgpu_paired_result));
+        flag = st.out(flag, n4); contig = st.out(contig, n4); pos = st.out(pos, n8); mapq = st.out(mapq, n4); ops = st.out(ops, n4 * ops_stride);
+        n_ops = st.out(n_ops, n4); nm = st.out(nm, n4); rnext = st.out(rnext, n4); pnext = st.out(pnext, n8); tlen = st.out(tlen, n8);
+        first_written = st.out(first_written, (size_t)n_pairs * 4); stale = st.out(stale, n4);
+        if (st.rc) return st.rc;
+    }
+    SamFieldsPairedArgs a; a.n_pairs = n_pairs; a.results = (const snapgpu_paired_result *)results;
+    samf_reads(a, bases, quals, offsets, front_clip, data_len);
+    samf_outputs(a, flag, contig, pos, mapq, ops, n_ops, nm, stale);
+    a.rnext = (int32_t *)rnext; a.pnext = (int64_t *)pnext; a.tlen = (int64_t *)tlen; a.first_written = (int32_t *)first_written;
+    if ((rc = launch_sam_fields(ctx, a, g, n, ops_stride, use_m, st))) return rc;
+    if (host) { if ((rc = st.download())) return rc; }
+    else HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    return finish_timing(ctx);
+}
+
 extern "C" int snapgpu_sam_fields_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
                                          const int32_t *front_clip, const int32_t *data_len, const snapgpu_paired_result *results, int use_m,
                                          int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
                                          int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
                                          int32_t *reference_history_dependent)
 {
-    const char *who = "snapgpu_sam_fields_paired";
     if (!ctx || (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !results || !flag || !contig || !pos || !mapq || !ops ||
                              !n_ops || !nm || !rnext || !pnext || !tlen || !first_written || !reference_history_dependent)))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired: ops_stride must be at least 3");
-    if (n_pairs == 0) return SNAPGPU_OK;
-    const uint32_t n = 2 * n_pairs;
-    SamfGeom g; uint32_t RL;
-    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL,
-                             [&](uint32_t i) { return check_location(ctx, who, results[i >> 1].status[i & 1], results[i >> 1].location[i & 1]); });
-    if (rc) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    if ((rc = samf_geometry(ctx, who, RL, n_pairs, &g))) return rc;
-    Stage st(ctx, ctx->stream);
-    const size_t total = offsets[n], n4 = (size_t)n * 4, n8 = (size_t)n * 8;
-    SamfBufs b{st.in(bases, total), st.in(quals, total), st.in(offsets, (size_t)(n + 1) * 8), st.in(front_clip, n4), st.in(data_len, n4),
-               st.in(results, (size_t)n_pairs * sizeof(snapgpu_paired_result)),
-               st.out(flag, n4), st.out(contig, n4), st.out(pos, n8), st.out(mapq, n4), st.out(ops, n4 * ops_stride), st.out(n_ops, n4), st.out(nm, n4), nullptr};
-    SamFieldsPairedArgs a;
-    a.n_pairs = n_pairs;
-    a.rnext = st.out(rnext, n4); a.pnext = st.out(pnext, n8); a.tlen = st.out(tlen, n8); a.first_written = st.out(first_written, (size_t)n_pairs * 4);
-    b.stale = st.out(reference_history_dependent, n4);          // (declared last: the outputs come back in the order of the argument list)
-    if (st.rc) return st.rc;
-    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
-    return finish_timing(ctx);
+    return sam_fields_paired_call(ctx, "snapgpu_sam_fields_paired", true, n_pairs, 0, bases, quals, offsets, front_clip, data_len, results, use_m,
+                                  flag, contig, pos, mapq, ops, ops_stride, n_ops, nm, rnext, pnext, tlen, first_written, reference_history_dependent, nullptr);
 }
 
-// device-pointer form of snapgpu_sam_fields_paired: reads, clipping and results already in HBM (e.g. right after
-// snapgpu_align_paired_device), outputs left in HBM.  max_read_len sizes the per-wave LDS rows and the scratch slab.
 extern "C" int snapgpu_sam_fields_paired_device(snapgpu_ctx *ctx, uint32_t n_pairs, uint32_t max_read_len, const void *d_bases, const void *d_quals,
                                                 const void *d_offsets, const void *d_front_clip, const void *d_data_len, const void *d_results, int use_m,
                                                 void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
                                                 void *d_n_ops, void *d_nm, void *d_rnext, void *d_pnext, void *d_tlen, void *d_first_written,
                                                 void *d_reference_history_dependent, void *stream)
 {
-    const char *who = "snapgpu_sam_fields_paired_device";
     if (!ctx || (n_pairs && (!d_bases || !d_quals || !d_offsets || !d_front_clip || !d_data_len || !d_results || !d_flag || !d_contig || !d_pos || !d_mapq ||
                              !d_ops || !d_n_ops || !d_nm || !d_rnext || !d_pnext || !d_tlen || !d_first_written || !d_reference_history_dependent)))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired_device: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired_device: ops_stride must be at least 3");
-    if (max_read_len == 0 || max_read_len > AGC_MAX_READ_LENGTH) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired_device: max_read_len out of range");
-    if (n_pairs == 0) return SNAPGPU_OK;
-    if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_sam_fields_paired_device: too many pairs");
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    SamfGeom g;
-    int rc = samf_geometry(ctx, who, max_read_len < 64 ? 64 : max_read_len, n_pairs, &g);
-    if (rc) return rc;
-    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
-    const SamfBufs b{d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_results, d_flag, d_contig, d_pos, d_mapq, d_ops, d_n_ops, d_nm,
-                     d_reference_history_dependent};
-    SamFieldsPairedArgs a; a.n_pairs = n_pairs;
-    a.rnext = (int32_t *)d_rnext; a.pnext = (int64_t *)d_pnext; a.tlen = (int64_t *)d_tlen; a.first_written = (int32_t *)d_first_written;
-    if ((rc = launch_sam_fields(ctx, a, g, b, 2 * n_pairs, ops_stride, use_m, st))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);           // (the scratch slab and the pre-pass records go back to the pool on return)
-    return finish_timing(ctx);
+    return sam_fields_paired_call(ctx, "snapgpu_sam_fields_paired_device", false, n_pairs, max_read_len, d_bases, d_quals, d_offsets, d_front_clip, d_data_len,
+                                  d_results, use_m, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_rnext, d_pnext, d_tlen, d_first_written,
+                                  d_reference_history_dependent, stream);
 }
 
 // The paired-end path of a SAM writer in one call, device-resident in between: ONE upload of the batch (the unclipped mates, Read::clip's
@@ -2785,25 +2760,24 @@ extern "C" int snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, cons
     const size_t n4 = (size_t)n * 4, n8 = (size_t)n * 8, rb = (size_t)n_pairs * sizeof(snapgpu_paired_result);
     const void *d_bases = bases, *d_quals = quals, *d_offsets = offsets;
     stage_reads(st, d_bases, d_quals, d_offsets, n);
-    const void *d_front_clip = st.in(front_clip, n4), *d_data_len = st.in(data_len, n4), *d_skip = st.in(skip, n_pairs);
+    const ClipWindow clip{st.in(front_clip, n4), st.in(data_len, n4), st.in(skip, n_pairs), false};
     void *d_results = st.out(results, rb), *d_first_alt = st.opt_out(first_alt, rb);      // (results == NULL: a device-only buffer)
     uint32_t h_overflowed = 0;
     uint32_t *d_overflowed = st.out(&h_overflowed, 4);
-    SamfBufs b{d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_results,
-               st.out(flag, n4), st.out(contig, n4), st.out(pos, n8), st.out(mapq, n4), st.out(ops, n4 * ops_stride), st.out(n_ops, n4), st.out(nm, n4), nullptr};
-    SamFieldsPairedArgs a; a.n_pairs = n_pairs;
+    SamFieldsPairedArgs a; a.n_pairs = n_pairs; a.results = (const snapgpu_paired_result *)d_results;
+    samf_reads(a, d_bases, d_quals, d_offsets, clip.front_clip, clip.data_len);
+    // (member by member, as in snapgpu_align_sam_single: the outputs in the order of the argument list)
+    a.flag = st.out(flag, n4); a.contig = st.out(contig, n4); a.pos = st.out(pos, n8); a.mapq = st.out(mapq, n4); a.ops = st.out(ops, n4 * ops_stride);
+    a.n_ops = st.out(n_ops, n4); a.nm = st.out(nm, n4);
     a.rnext = st.out(rnext, n4); a.pnext = st.out(pnext, n8); a.tlen = st.out(tlen, n8); a.first_written = st.out(first_written, (size_t)n_pairs * 4);
-    b.stale = st.out(reference_history_dependent, n4);
+    a.stale = st.out(reference_history_dependent, n4);
     if (st.rc) return st.rc;
-    ctx->clip_front = (const int32_t *)d_front_clip; ctx->clip_len = (const int32_t *)d_data_len; ctx->clip_skip = (const uint8_t *)d_skip;
-    rc = launch_paired(ctx, n_pairs, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s);
-    ctx->clip_front = ctx->clip_len = nullptr; ctx->clip_skip = nullptr;
-    if (rc || (rc = finish_timing(ctx))) return rc;                // (the align launches' own hipEvent time, before the events are reused)
+    if ((rc = launch_paired(ctx, n_pairs, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s, &clip)) || (rc = finish_timing(ctx))) return rc;      // (the align launches' own hipEvent time, before the events are reused)
     // what snapgpu_align_paired reports for a pool overflow, without the results on the host: the pairs still flagged after the second pass, counted
     HIPCHK(ctx, hipMemsetAsync(d_overflowed, 0, 4, st.s), SNAPGPU_E_LAUNCH);
     snapgpu_launch_collect_flagged((snapgpu_paired_result *)d_results, n_pairs, ctx->d_flag_list, d_overflowed, 0, st.s);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    if ((rc = launch_sam_fields(ctx, a, g, b, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
+    if ((rc = launch_sam_fields(ctx, a, g, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
     if ((rc = finish_timing(ctx))) return rc;
     return h_overflowed ? fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG) : SNAPGPU_OK;
 }
@@ -2840,7 +2814,7 @@ static int align_single_call(snapgpu_ctx *ctx, bool host, uint32_t n, const void
         if (st.rc) return st.rc;
         if (n_secondary && sec_bytes) HIPCHK(ctx, hipMemsetAsync(secondary, 0, sec_bytes, st.s), SNAPGPU_E_LAUNCH);
     }
-    if ((rc = launch_align(ctx, n, bases, quals, offsets, primary, first_alt, st.s, secondary, secondary_stride, n_secondary))) return rc;
+    if ((rc = launch_align(ctx, n, bases, quals, offsets, primary, first_alt, st.s, nullptr, secondary, secondary_stride, n_secondary))) return rc;
     if (host && (rc = st.download())) return rc;
     if (!stream && (rc = finish_timing(ctx))) return rc;
     return host && h_n_secondary ? scan_results(ctx, n, nullptr, h_n_secondary, secondary_stride, nullptr, 0) : SNAPGPU_OK;
@@ -2907,7 +2881,7 @@ static int align_paired_call(snapgpu_ctx *ctx, bool host, uint32_t n_pairs, cons
         if (sec_bytes) HIPCHK(ctx, hipMemsetAsync(d_so.secondary, 0, sec_bytes, st.s), SNAPGPU_E_LAUNCH);
         if (ssec_bytes) HIPCHK(ctx, hipMemsetAsync(d_so.single_secondary, 0, ssec_bytes, st.s), SNAPGPU_E_LAUNCH);
     }
-    if ((rc = launch_paired(ctx, n_pairs, bases, quals, offsets, primary, first_alt, st.s, so ? &d_so : nullptr))) return rc;
+    if ((rc = launch_paired(ctx, n_pairs, bases, quals, offsets, primary, first_alt, st.s, nullptr, so ? &d_so : nullptr))) return rc;
     if (host && (rc = st.download())) return rc;
     if (!stream && (rc = finish_timing(ctx))) return rc;
     if (!host) return SNAPGPU_OK;

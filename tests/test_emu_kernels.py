@@ -361,6 +361,12 @@ def test_emu_align_sam_single(emu, golden_index, tag):
     gc.check_align_sam_single_against_reference_cli(golden_index, z, tag, n=500)
 
 
+def test_emu_sam_fields_equal_the_primary_records(emu, golden_index):
+    """The two instantiations of sam_fields_run (k_sam_fields, k_sam_fields_rec) against each other on the emulated device."""
+    import tests.test_zz_gpu_cigar as gc
+    gc.check_sam_fields_equal_the_primary_records(golden_index, np.load(os.path.join(util.GOLDEN, "sam_fields.npz")), n=200)
+
+
 @pytest.mark.parametrize("opts", [[], ["-G-", "-=", "-C++", "-b", "97"], ["-G-", "-ea", "-om", "1", "-omax", "4"], ["-ae"], ["-ae", "-om", "1"]])     # -b 97: nine batches, the last one short; -C++: '#' heads
                                                                                                                   # clipped too; -om / -ea: secondary and first-ALT records
 def test_emu_native_fastq_to_sam(emu, tmp_path, opts):

@@ -290,6 +290,44 @@ def test_align_sam_single_vs_reference_cli_fixture(golden_index, tag):
     assert check_align_sam_single_against_reference_cli(golden_index, z, tag) > 10
 
 
+def check_sam_fields_equal_the_primary_records(golden_index, z, n):
+    """k_sam_fields and k_sam_fields_rec are one body over two descriptions of "item i": on a plain single-end context, samFields over
+    AlignRead's results equals, field for field, the primary records (rec_kind 0) of alignSamRecords on the same reads, with use_m 0 and 1."""
+    from snap_amd.aligner import BaseAligner
+    prm = abi.default_params(max_read_len=400)
+    offs = z["offsets"][:n + 1]
+    bases, quals = z["bases"][:int(offs[-1])], z["quals"][:int(offs[-1])]
+    fc, dl = z["default_front_clip"][:n], z["default_data_len"][:n]
+    first = offs[:-1].astype(np.int64) + fc
+    skip = np.array([dl[i] < 50 or int((bases[first[i]:first[i] + dl[i]] == ord("N")).sum()) > int(prm.max_k) for i in range(n)], dtype=np.uint8)
+    keep = np.flatnonzero(skip == 0)
+    assert 0 < keep.size < n                                                # (the reads the aligner is not given are formatted too)
+    take = np.concatenate([np.arange(first[i], first[i] + dl[i]) for i in keep])
+    a = BaseAligner(golden_index, prm)
+    try:
+        res, _ = a.AlignRead(bases[take], quals[take], np.concatenate([[0], np.cumsum(dl[keep])]).astype(np.uint64))
+        ops = {}
+        for use_m in (False, True):
+            rec = a.alignSamRecords(bases, quals, offs, fc, dl, skip, use_m=use_m)
+            prim = np.flatnonzero(rec["rec_kind"] == 0)
+            assert not rec["truncated"] and prim.size == n and (rec["rec_read"][prim] == np.arange(n)).all()
+            bad = util.compare_results(res, rec["results"][keep])
+            assert not bad, bad[:3] if isinstance(bad, list) else bad
+            results = rec["results"].copy(); results[keep] = res            # (a read that is skipped: NotFound, as the writer sees it)
+            two = a.samFields(bases, quals, offs, fc, dl, results, use_m=use_m)
+            for k in ("flag", "contig", "pos", "mapq", "n_ops", "ops", "nm", "stale"):
+                assert (two[k] == rec[k][prim]).all(), (use_m, k, np.flatnonzero((two[k] != rec[k][prim]).reshape(n, -1).any(axis=1))[:5])
+            ops[use_m] = two["ops"]
+        assert (ops[False] != ops[True]).any()                              # =/X against M: use_m reached the kernels
+    finally:
+        a.close()
+
+
+def test_sam_fields_equal_the_primary_records(golden_index):
+    import os
+    check_sam_fields_equal_the_primary_records(golden_index, np.load(os.path.join(util.GOLDEN, "sam_fields.npz")), n=1500)
+
+
 # ---------------------------------------------------------------------------------------------- paired-end writer
 def check_sam_fields_paired_against_reference_cli(z, tag, n_pairs=None):
     """All 9 computed fields of both records of each pair and the order of the two records, as the unmodified reference CLI printed them
