@@ -525,6 +525,7 @@ static __device__ __forceinline__ AGCOut agc_banded_par(const AGCState &s, int p
 struct SamfPre { int32_t valid, plen, w, bcb; int64_t loc; int32_t score, text_used, dir, rows, pad0, pad1; };
 static_assert(sizeof(SamfPre) == 48, "SamfPre layout");
 #define SAMF_PRE_ROW 32                      // traceback bytes a row can evaluate: two segments x two vectors x 8
+// RL + 16 rows hold every row whose band reaches the last column (row <= plen - 1 + w <= RL + 6); a later row scores there only through a gap, below the row the gap left, and `>` keeps that one.
 static __host__ __device__ __forceinline__ uint32_t samf_pre_rows(uint32_t RL) { return RL + 16; }
 static __host__ __device__ __forceinline__ size_t samf_pre_stride(uint32_t RL) { return (sizeof(SamfPre) + (size_t)samf_pre_rows(RL) * SAMF_PRE_ROW + 63) & ~(size_t)63; }
 #define SAMF_PRE_MAX_W 7                     // 2 w + 1 <= 16: at most two vectors per segment

@@ -2,7 +2,13 @@
 reference's answers (tests/golden/cigar_lv.npz, scripts/make_golden_cigar.py) and against the C restatement on fresh items.
 
 Written in a round that had no GPU time left: the kernel was verified on the wavefront emulator (tests/test_emu_kernels.py) and
-compiled for gfx950, not yet run on hardware -- hence the file name, which makes it the last module of the `-m gpu` run."""
+compiled for gfx950, not yet run on hardware -- hence the file name, which makes it the last module of the `-m gpu` run.
+
+SAM-side coverage further down: result -> record fields against the reference CLI's fixtures (check_sam_fields_against_reference_cli,
+check_align_sam_single_against_reference_cli, check_sam_fields_equal_the_primary_records, check_sam_fields_paired_against_reference_cli).
+The row-loop pre-pass ahead of those kernels has its own module, tests/test_zz_gpu_samf_prepass.py: check_who_took_the_prepass,
+check_no_prepass_without_affine_gap, check_on_equals_off, check_against_reference, check_single_properties, check_paired_against_single,
+check_records_valid."""
 import numpy as np
 import pytest
 
