@@ -160,17 +160,26 @@ struct SecCfg {
 // the kernels that are timed for throughput are built without (SNAPGPU_PHASE_TIMERS=1 selects the timed instantiation for a breakdown run).
 // PLANES: the plane Landau-Vishkin (planes.h; SNAPGPU_LV_PLANES=1) is compiled in.  Its own instantiations (single_planes_k.hip): carried by
 // every kernel it cost the default ones 110-120 bytes of scratch per lane (exact form 520 -> 408, fast form 712 -> 592) for an option that is off.
-// REGDIR: the candidate table's DIRECTORY in a vector register -- lane j holds the key (bucket number * 2 + direction) of element j, j < 64 -- so that
-// findElement, which the reference does once per seed hit and which was two dependent HBM loads here (the u16 head, then the chained element), is one compare and
-// a ballot while the read has at most 64 buckets (nearly every read); the HBM hash is built when the 65th arrives and used from then on.  Only where this
-// object lives in registers (k_align_single): in the paired-end kernel it is one LDS object per wave and has no per-lane members.
-struct AlignerDirState { uint32_t dirkey; };
-struct AlignerNoDirState {};
-template <bool REGDIR> struct AlignerDirBase { using type = AlignerNoDirState; };
-template <> struct AlignerDirBase<true> { using type = AlignerDirState; };
+// HELP: the help for heavy reads (se_help.h) is compiled in: its state (an empty base otherwise) and the code that publishes, takes and closes
+// a list.  Only the fast single-end kernels have it: the exact replay cannot share a walk that is ordered through the traceback arrays, and the
+// paired-end kernels never had it -- both carried eleven words of it, all NULL / 0, in an object every word of which is live across the
+// Landau-Vishkin and affine-gap calls.
+struct AlignerHelpState {
+    SEHelpSlot *se_slots; uint32_t se_n_slots; SESpec *se_spec; uint32_t se_spec_cap;
+    uint32_t *se_ctl;                  // [0] reads of the launch that are done, [1] waves that have run out of reads, [2] lists open now
+    uint32_t se_eager;                 // publish whether or not anybody is idle (tests)
+    uint32_t *se_items, *se_first;     // this wave's list / per-element start (HBM slab)
+    unsigned long long *se_diag;       // snapgpu_counters::reserved[1 .. 2]
+    int se_slot; uint32_t se_n, se_tried, cur_read; SESpec *se_mine;
+};
+struct AlignerNoHelpState {};
+template <bool HELP> struct AlignerHelpBase { using type = AlignerNoHelpState; };
+template <> struct AlignerHelpBase<true> { using type = AlignerHelpState; };
 
-template <int AGC, bool SEC = false, bool EXACT = false, bool TIMED = false, bool PLANES = false, bool REGDIR = false>
-struct Aligner : AlignerDirBase<REGDIR>::type {
+// (This object lives in LDS, one per WAVE, in every kernel -- kernel_common.h: SE_FRAME_BYTES, paired_args.h: PE_FRAME_BYTES -- so it has no
+//  per-lane members and no reference members.)
+template <int AGC, bool SEC = false, bool EXACT = false, bool TIMED = false, bool PLANES = false, bool HELP = false>
+struct Aligner : AlignerHelpBase<HELP>::type {
     // ---- constant for the launch
     // held by value: a reference member would make the kernel-argument struct escape through a
     // flat pointer and pin this whole object (ScoreSets, results, counters) in scratch memory
@@ -199,7 +208,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
     uint32_t ag_hw0, ag_hw1;               // EXACT only: bytes of each image written since it was last zeroed (what the next read must clear)
     uint32_t ag_epoch, ag_tag;             // EXACT only: reads since the images were last cleared (1 .. 15) and its tag bits (dev_common.h: bt_cell): cells of other reads read as zero
     // ---- per-read state (wave-uniform)
-    // (not a stored value: in the paired-end kernel this object lives in LDS, one per WAVE -- paired_args.h: PE_FRAME_BYTES)
+    // (not a stored value: this object lives in LDS, one per WAVE)
     struct LaneId { __device__ __forceinline__ operator int() const { return lane_id(); } };
     LaneId lane;
     int read_len;
@@ -216,13 +225,6 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
                                        // (two scalars, not an array: an index that is not a compile-time constant would pin the object in scratch)
     uint32_t max_k;                    // BaseAligner::maxK: cfg.max_k, or what setMaxK() last said (ChimericPairedEndAligner.cpp:278,301)
     uint32_t ag_calls_unit;            // affine-gap calls since the unit (read; the paired kernel: pair) began -- see wave_set_priority
-    // ---- help for heavy reads (se_help.h); all NULL / 0 where there is none (the paired-end kernel, the exact replay)
-    SEHelpSlot *se_slots; uint32_t se_n_slots; SESpec *se_spec; uint32_t se_spec_cap;
-    uint32_t *se_ctl;                  // [0] reads of the launch that are done, [1] waves that have run out of reads, [2] lists open now
-    uint32_t se_eager;                 // publish whether or not anybody is idle (tests)
-    uint32_t *se_items, *se_first;     // this wave's list / per-element start (HBM slab)
-    unsigned long long *se_diag;       // snapgpu_counters::reserved[1 .. 2]
-    int se_slot; uint32_t se_n, se_tried, cur_read; SESpec *se_mine;
     // candidates for BaseAligner::alignAffineGap, collected by the Hamming pass only (BaseAligner.cpp:1445-1456)
     GP<snapgpu_single_result> agc;
     uint32_t agc_cap, n_agc, agc_overflow;
@@ -377,20 +379,9 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
         return (uint32_t)(k >> 40) & (cfg.ht_size - 1);
     }
     // findElement (BaseAligner.cpp:1811-1840): returns element index or 0xFFFF
-    static __device__ __forceinline__ uint32_t dir_key(int64_t base, int dir) { return (uint32_t)(((uint64_t)base / BUCKET) * 2 + (uint64_t)dir); }   // (locations fit 32 bits: < 2^28)
-#ifndef SNAPGPU_DIR_CAP
-#define SNAPGPU_DIR_CAP 64            // (test builds lower it so that ordinary fixtures cross the directory-to-hash transition)
-#endif
-    static constexpr uint32_t DIR_CAP = SNAPGPU_DIR_CAP;
     __device__ __forceinline__ uint16_t find_element(int64_t loc, int dir) const {
         int64_t low = (int64_t)((uint64_t)loc % BUCKET);
         int64_t base = loc - low;
-        if constexpr (REGDIR) {
-            if (n_used <= DIR_CAP) {                                          // the whole table is in the directory
-                const unsigned long long m = BALLOT(this->dirkey == dir_key(base, dir));
-                return m ? (uint16_t)__builtin_ctzll(m) : (uint16_t)0xFFFF;
-            }
-        }
         uint16_t h = (uint16_t)first_u32(heads[head_slot(base, dir)]);
         while (h != 0) {
             // base (dwords 4,5) and hnext|dir|flags (dword 18) of the chained element in one load instead of three dependent ones
@@ -408,7 +399,6 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
     __device__ __forceinline__ void clear_candidates() {                     // BaseAligner.cpp:2332-2339
         n_used = 0;
         highest_used_weight_list = 0;
-        if constexpr (REGDIR) this->dirkey = 0xFFFFFFFFu;
         for (uint32_t i = lane; i < cfg.num_weight_lists; i += WAVE) {
             wl_next[i] = sent(i); wl_prev[i] = sent(i);
         }
@@ -417,7 +407,6 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
 
     // undo the head-table entries of this read (lane-parallel)
     __device__ __forceinline__ void release_candidates() {
-        if (REGDIR && n_used <= DIR_CAP) return;                              // (the hash was never built)
         for (uint32_t i = lane; i < n_used; i += WAVE) {
             heads[head_slot(pool[i].base, pool[i].dir)] = 0;
         }
@@ -446,21 +435,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
         n_used++;
         Elem *e = &pool[ei];
         uint32_t hs = head_slot(base, dir);
-        uint16_t old_head = 0;
-        bool hashed = true;
-        if constexpr (REGDIR) {
-            if (ei < DIR_CAP) { this->dirkey = lane == (int)ei ? dir_key(base, dir) : this->dirkey; hashed = false; }
-            else if (ei == DIR_CAP) {                                         // the directory is full: the hash takes over, starting with what the directory holds
-                for (uint32_t j = 0; j < DIR_CAP; j++) {
-                    uint64_t k = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)this->dirkey, (int)j) * 0x9E3779B97F4A7C15ull;
-                    const uint32_t hj = (uint32_t)(k >> 40) & (cfg.ht_size - 1);
-                    const uint16_t oh = (uint16_t)first_u32(heads[hj]);
-                    if (lane == 0) { pool[j].hnext = oh; heads[hj] = (uint16_t)(j + 1); }
-                    WAVE_SYNC();
-                }
-            }
-        }
-        if (hashed) old_head = (uint16_t)first_u32(heads[hs]);
+        uint16_t old_head = (uint16_t)first_u32(heads[hs]);
         if (lane == 0) {
             e->used = 1ull << low;
             e->scored = 0;
@@ -475,7 +450,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
             e->best_loc = 0; e->seed_offset = 0;
             e->cand_seed_offset[low] = (uint16_t)seed_offset;
             e->hnext = old_head;
-            if (hashed) heads[hs] = (uint16_t)(ei + 1);
+            heads[hs] = (uint16_t)(ei + 1);
         }
         WAVE_SYNC();
         list_push_tail(1, ei);
@@ -869,7 +844,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
     }
 
     // ------------------------------------------------------------------ help for heavy reads (se_help.h)
-    __device__ __forceinline__ bool se_wanted() const { return se_eager || XW::ld(se_ctl[1]) != 0u; }
+    __device__ __forceinline__ bool se_wanted() const { return this->se_eager || XW::ld(this->se_ctl[1]) != 0u; }
 
     // List what the forced walk still has to visit -- weight lists from wl down, first in first out, every unscored candidate of each
     // element -- and offer it to the idle waves.
@@ -877,17 +852,17 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
         // a slot first (the list is only worth building if there is one); none free: look again some elements further on
         int s = -1;
         if (lane == 0) {
-            const uint32_t start = (cur_read * 7u) % se_n_slots;
-            for (uint32_t k = 0; k < se_n_slots; k++) {
-                const uint32_t i = start + k < se_n_slots ? start + k : start + k - se_n_slots;
-                if (XW::ld_lane(se_slots[i].state) != 0u) continue;
-                if (atomicCAS(&se_slots[i].state, 0u, 3u) == 0u) { s = (int)i; break; }
+            const uint32_t start = (this->cur_read * 7u) % this->se_n_slots;
+            for (uint32_t k = 0; k < this->se_n_slots; k++) {
+                const uint32_t i = start + k < this->se_n_slots ? start + k : start + k - this->se_n_slots;
+                if (XW::ld_lane(this->se_slots[i].state) != 0u) continue;
+                if (atomicCAS(&this->se_slots[i].state, 0u, 3u) == 0u) { s = (int)i; break; }
             }
         }
         s = (int)first_u32((uint32_t)s);
-        if (s < 0) { se_tried = 0x80000000u | 32u; return; }
-        se_tried = 1;
-        for (uint32_t i = (uint32_t)lane; i < n_used; i += WAVE) se_first[i] = 0xffffffffu;
+        if (s < 0) { this->se_tried = 0x80000000u | 32u; return; }
+        this->se_tried = 1;
+        for (uint32_t i = (uint32_t)lane; i < n_used; i += WAVE) this->se_first[i] = 0xffffffffu;
         WAVE_SYNC();
         uint32_t n = 0;
         for (uint32_t w = wl; w >= 1 && n + BUCKET <= cfg.se_items_cap; w--) {
@@ -899,44 +874,44 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
                 const uint64_t scored = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)v, 3) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, 2);
                 const uint16_t nxt = (uint16_t)((uint32_t)__builtin_amdgcn_readlane((int)v, 4) & 0xffffu);
                 const uint64_t m = used & ~scored;
-                if (lane == 0) se_first[ei] = n;
-                if (lane < BUCKET && ((m >> lane) & 1ull)) se_items[n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = ((uint32_t)ei << 6) | (uint32_t)lane;
+                if (lane == 0) this->se_first[ei] = n;
+                if (lane < BUCKET && ((m >> lane) & 1ull)) this->se_items[n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = ((uint32_t)ei << 6) | (uint32_t)lane;
                 n += (uint32_t)__popcll(m);
                 ei = nxt;
             }
         }
         WAVE_SYNC();
-        if (n < SE_HELP_MIN_ITEMS || n > se_spec_cap) { if (lane == 0) atomicExch(&se_slots[s].state, 0u); return; }     // not worth it: give the slot back
-        SEHelpSlot *slot = &se_slots[s];
-        SESpec *spec = se_spec + (size_t)s * se_spec_cap;
+        if (n < SE_HELP_MIN_ITEMS || n > this->se_spec_cap) { if (lane == 0) atomicExch(&this->se_slots[s].state, 0u); return; }     // not worth it: give the slot back
+        SEHelpSlot *slot = &this->se_slots[s];
+        SESpec *spec = this->se_spec + (size_t)s * this->se_spec_cap;
         for (uint32_t t = (uint32_t)lane; t < n; t += WAVE) spec[t].state = 0u;
         WAVE_SYNC();
         if (lane == 0) {
             const uint32_t w0 = atomicExch(&slot->next, SE_HELP_LOOKAHEAD), w1 = atomicExch(&slot->helpers, 0u);
             if ((w0 ^ w1) == 0xFFFFFFF5u) atomicExch(&slot->helpers, 0u);      // (uses both return values: the exchanges have completed)
-            XW::st(slot->read, cur_read); XW::st(slot->n, n); XW::st(slot->owner_pos, 0u);
+            XW::st(slot->read, this->cur_read); XW::st(slot->n, n); XW::st(slot->owner_pos, 0u);
             XW::st(slot->lim_alt, (int32_t)score_limit(true)); XW::st(slot->lim_non_alt, (int32_t)score_limit(false));
             XW::st(slot->best_all, (uint32_t)all().best_score);
-            XW::st(*(uint64_t *)&slot->items, (uint64_t)(uintptr_t)se_items); XW::st(*(uint64_t *)&slot->pool, (uint64_t)(uintptr_t)(Elem *)pool);
+            XW::st(*(uint64_t *)&slot->items, (uint64_t)(uintptr_t)this->se_items); XW::st(*(uint64_t *)&slot->pool, (uint64_t)(uintptr_t)(Elem *)pool);
             XW::st(*(uint64_t *)&slot->spec, (uint64_t)(uintptr_t)spec);
             XW::fence_release();                            // the candidate table, the list and the cleared records, for the other XCDs
             atomicExch(&slot->state, 1u);
-            atomicAdd(&se_ctl[2], 1u);
-            if (se_diag) atomicAdd(&se_diag[1], 1ull << 32);
+            atomicAdd(&this->se_ctl[2], 1u);
+            if (this->se_diag) atomicAdd(&this->se_diag[1], 1ull << 32);
         }
         WAVE_SYNC();
-        se_slot = s; se_n = n; se_mine = spec;
+        this->se_slot = s; this->se_n = n; this->se_mine = spec;
     }
 
     // The owner arrives at candidate idx of element ei: take what an idle wave stored for it, if that was computed from the inputs the
     // owner has now; claim it otherwise (false: evaluate it here).
     __device__ __forceinline__ bool se_take(uint16_t ei, int idx, uint64_t listed0, int limit_e, uint32_t e_lps, int64_t loc0, int cand_seed_offset, CandEval &ce) {
-        const uint32_t t0 = first_u32(se_first[ei]);
+        const uint32_t t0 = first_u32(this->se_first[ei]);
         if (t0 == 0xffffffffu) return false;
         const uint32_t t = t0 + (uint32_t)__popcll(listed0 & ((1ull << idx) - 1ull));
-        if (t >= se_n) return false;
-        SEHelpSlot *slot = &se_slots[se_slot];
-        SESpec *sp = &se_mine[t];
+        if (t >= this->se_n) return false;
+        SEHelpSlot *slot = &this->se_slots[this->se_slot];
+        SESpec *sp = &this->se_mine[t];
         if (lane == 0) XW::st(slot->owner_pos, t + 1u);
         const uint64_t t_w0 = wave_clock();
         for (;;) {
@@ -947,7 +922,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
             if (st == 2u) break;
             XW::nap();
             if (wave_clock() - t_w0 > 1200000000ull) {      // ~0.5 s on one candidate: stop relying on the slot, leave a trace
-                if (lane == 0 && se_diag) atomicAdd(&se_diag[0], 1ull);
+                if (lane == 0 && this->se_diag) atomicAdd(&this->se_diag[0], 1ull);
                 se_abandon();
                 return false;
             }
@@ -958,7 +933,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
         uint32_t n_ag = XW::ld(sp->n_ag), stale = XW::ld(sp->stale);
         uint64_t bytes = XW::ld(sp->lv_ref_bytes);
         if (lim == limit_e) {
-            if (high && ((e_lps <= best_then) != (e_lps <= (uint32_t)all().best_score))) { if (lane == 0 && se_diag) atomicAdd(&se_diag[-1], 1ull << 16); return false; }  // the affine-gap decision (:1203) would differ
+            if (high && ((e_lps <= best_then) != (e_lps <= (uint32_t)all().best_score))) { if (lane == 0 && this->se_diag) atomicAdd(&this->se_diag[-1], 1ull << 16); return false; }  // the affine-gap decision (:1203) would differ
             ce.sc = XW::ld(sp->sc); ce.mp = XW::ld(sp->mp); ce.loc = XW::ld(sp->loc); ce.used_ag = XW::ld(sp->used_ag);
             ce.clip_before = XW::ld(sp->clip_before); ce.clip_after = XW::ld(sp->clip_after); ce.ag_score = XW::ld(sp->ag_score);
         } else {
@@ -966,14 +941,14 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
             // k (LandauVishkin.h:100-351; SURVEY.md Appendix C: 12 M comparisons), so what it says under the owner's limit follows: the
             // same when the edits of both sides still fit, "above the limit" otherwise.  Affine gap is another matter -- its band is the limit --
             // so an evaluation in which it ran, or would run now, is redone.
-            if (lim < limit_e || n_lv == 0u) { if (lane == 0 && se_diag) atomicAdd(&se_diag[-1], 1ull); return false; }
+            if (lim < limit_e || n_lv == 0u) { if (lane == 0 && this->se_diag) atomicAdd(&this->se_diag[-1], 1ull); return false; }
             const int lv1 = XW::ld(sp->lv1), lv2 = XW::ld(sp->lv2);
             const int plen0 = read_len - (cand_seed_offset + (int)ix.seed_len), plen1 = cand_seed_offset;
             const bool half1_runs = lv1 >= 0 && lv1 <= limit_e;
             bytes = (uint64_t)plen0 + (uint64_t)(2 * (limit_e < 0 ? 0 : limit_e)) + (half1_runs ? (uint64_t)plen1 : 0ull);
             if (half1_runs && lv2 >= 0 && lv1 + lv2 <= limit_e) {                 // both sides still fit
                 if (n_ag != 0u || (high && e_lps <= (uint32_t)all().best_score)) {      // affine gap ran under another band, or would run now
-                    if (lane == 0 && se_diag) atomicAdd(&se_diag[-1], 1ull << 16);
+                    if (lane == 0 && this->se_diag) atomicAdd(&this->se_diag[-1], 1ull << 16);
                     return false;
                 }
                 ce.sc = XW::ld(sp->sc); ce.mp = XW::ld(sp->mp); ce.loc = XW::ld(sp->loc); ce.used_ag = 0;
@@ -990,30 +965,30 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
         // later-call ones, and from here on the objects count as used
         ag_stale += stale; ag_replay += stale;
         if (n_ag) { ag_obj_used0 = 1; ag_obj_used1 = 1; ag_calls_unit += n_ag; }
-        if (lane == 0 && se_diag) atomicAdd(&se_diag[1], 1ull);
+        if (lane == 0 && this->se_diag) atomicAdd(&this->se_diag[1], 1ull);
         return true;
     }
 
     __device__ __forceinline__ void se_abandon() {          // after a watchdog: the slot is retired for the rest of the launch
-        if (lane == 0) { atomicExch(&se_slots[se_slot].state, 4u); atomicSub(&se_ctl[2], 1u); }
-        se_slot = -1;
+        if (lane == 0) { atomicExch(&this->se_slots[this->se_slot].state, 4u); atomicSub(&this->se_ctl[2], 1u); }
+        this->se_slot = -1;
     }
 
     // end of the read: no new helpers, wait for the attached ones to leave (they read this wave's candidate table), free the slot
     __device__ __forceinline__ void se_close() {
-        SEHelpSlot *slot = &se_slots[se_slot];
+        SEHelpSlot *slot = &this->se_slots[this->se_slot];
         uint32_t was = 0;
-        if (lane == 0) { was = atomicExch(&slot->state, 2u); atomicSub(&se_ctl[2], 1u); }
+        if (lane == 0) { was = atomicExch(&slot->state, 2u); atomicSub(&this->se_ctl[2], 1u); }
         was = first_u32(was);
         bool gave_up = was != 1u;
         const uint64_t t0 = wave_clock();
         while (!gave_up) {
             if (XW::aload(&slot->helpers) == 0u) break;
             XW::nap();
-            if (wave_clock() - t0 > 4800000000ull) { if (lane == 0 && se_diag) atomicAdd(&se_diag[0], 1ull << 16); gave_up = true; }
+            if (wave_clock() - t0 > 4800000000ull) { if (lane == 0 && this->se_diag) atomicAdd(&this->se_diag[0], 1ull << 16); gave_up = true; }
         }
         if (lane == 0) atomicExch(&slot->state, gave_up ? 4u : 0u);
-        se_slot = -1;
+        this->se_slot = -1;
     }
 
     // A wave that has run out of reads, attached to `slot` (the read is in this wave's LDS): evaluate candidates of the list until none
@@ -1074,7 +1049,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
                     XW::st(sp->lv1, (int32_t)ce.lv1); XW::st(sp->lv2, (int32_t)ce.lv2);
                     XW::stores_done();
                     atomicExch(&sp->state, 2u);
-                    if (se_diag) atomicAdd(&se_diag[-1], 1ull << 32);       // (snapgpu_counters::reserved[0]: evaluations stored << 32 | refused: limit | AG << 16)
+                    if (this->se_diag) atomicAdd(&this->se_diag[-1], 1ull << 32);       // (snapgpu_counters::reserved[0]: evaluations stored << 32 | refused: limit | AG << 16)
 #if defined(SNAPGPU_WAVE_EMU)
                     if (getenv("SNAPGPU_DEBUG_SE_HELP")) fprintf(stderr, "HELPED read %u item %u limit %d sc %u n_ag %u\n", XW::ld(slot->read), t, rec_limit, ce.sc, d_ag);
 #endif
@@ -1130,10 +1105,10 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
                 return false;
             }
 
-            if constexpr (!EXACT && !HAM) {             // idle waves can take over part of what is left of a forced walk (se_help.h)
-                if (force_result && se_slots != nullptr && se_slot < 0) {
-                    if (se_tried & 0x80000000u) { se_tried = (se_tried & 0x7fffffffu) > 1u ? se_tried - 1u : 0u; }     // (no slot was free: count down to the next look)
-                    else if (!se_tried && se_wanted()) se_publish(wl);
+            if constexpr (HELP && !HAM) {               // idle waves can take over part of what is left of a forced walk (se_help.h)
+                if (force_result && this->se_slots != nullptr && this->se_slot < 0) {
+                    if (this->se_tried & 0x80000000u) { this->se_tried = (this->se_tried & 0x7fffffffu) > 1u ? this->se_tried - 1u : 0u; }     // (no slot was free: count down to the next look)
+                    else if (!this->se_tried && se_wanted()) se_publish(wl);
                 }
             }
             uint16_t ei = get_next(sent(wl));
@@ -1175,7 +1150,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
                     int cand_seed_offset = (int)((EW(20 + (idx >> 1)) >> (16 * (idx & 1))) & 0xffffu);
                     CandEval ce;
                     bool have = false;
-                    if constexpr (!EXACT && !HAM) { if (se_slot >= 0) have = se_take(ei, idx, listed0, limit_e, e_lps, loc, cand_seed_offset, ce); }
+                    if constexpr (HELP && !HAM) { if (this->se_slot >= 0) have = se_take(ei, idx, listed0, limit_e, e_lps, loc, cand_seed_offset, ce); }
                     if (!have) ce = eval_candidate<HAM>(loc, e_dir, e_lps, cand_seed_offset, limit_e, (uint32_t)all().best_score);
                     const uint32_t sc = ce.sc; const double mp = ce.mp; loc = ce.loc;
                     const int used_ag = ce.used_ag, clip_before = ce.clip_before, clip_after = ce.clip_after, ag_score = ce.ag_score;
@@ -1356,7 +1331,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
         if (!cfg.alt_aware) non_alt().best_score = SNAPGPU_TooBigScoreValue;    // :325 (never re-initialised without ALT awareness)
         n_seeds_applied[0] = n_seeds_applied[1] = 0;
         popular_seeds_skipped = 0;
-        se_tried = 0;
+        if constexpr (HELP) this->se_tried = 0;
 
         // ONE call site for score(): it is inlined (a call would pin this object in memory), and the reference's three sites -- after a seed's
         // hits, when the seeds have wrapped seedLen times (:466), after the loop (:734) -- were three copies of the whole scoring code in the
@@ -1419,7 +1394,7 @@ struct Aligner : AlignerDirBase<REGDIR>::type {
                 if (score<HAM>(force) || force) break;
             }
         }
-        if constexpr (!EXACT && !HAM) { if (se_slot >= 0) se_close(); }       // (before the candidate table is released: helpers read it)
+        if constexpr (HELP && !HAM) { if (this->se_slot >= 0) se_close(); }       // (before the candidate table is released: helpers read it)
         primary().score_prior_to_clipping = primary().score;                      // finalizeSecondaryResults, :2442
         primary().reserved = (ag_stale & 0x3fffffffu) | (ag_replay ? 0x40000000u : 0u);      // bit 30: the exact pass must redo this read
         release_candidates();

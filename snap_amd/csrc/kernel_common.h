@@ -67,13 +67,20 @@ void snapgpu_launch_single_exact_planes_0(const AlignArgs *a, uint32_t blocks, s
 
 static __device__ __forceinline__ uint32_t align_up(uint32_t v, uint32_t a) { return (v + a - 1) & ~(a - 1); }
 
-// LDS carve-out per wave; must match lds_bytes_per_wave() on the host.
+// SE_FRAME_BYTES: the single-end wave's FRAME -- k_align_single constructs its Aligner there (single_kernel.h: wave-uniform state, one read at a
+// time, so one copy per wave instead of one per lane in registers, where its hundred-odd words did not fit next to the Landau-Vishkin and
+// affine-gap calls and were spilled around each of them).  A fixed size, not sizeof: the host sizes LDS from the same function and does not
+// instantiate the device class; the kernel checks that every instantiation fits.
+#define SE_FRAME_BYTES 768u
+
+// LDS carve-out per wave: the host sizes the launch (AlignCfg::lds_per_wave) and the kernel finds its blocks from the same function.
 struct LdsLayout {
-    uint32_t rd0, rd1, ql0, ql1, gw, seed_used, wl_next, wl_prev, lv, ag, shared, rp, tp, lvp, total;
+    uint32_t rd0, rd1, ql0, ql1, gw, seed_used, wl_next, wl_prev, lv, ag, shared, rp, tp, lvp, frame, total;
 };
 
 // ag_lds: bytes of LDS the affine-gap code of the kernel variant needs (AlignCfg::ag_lds; 0 = no affine-gap buffers)
-static __host__ __device__ __forceinline__ LdsLayout lds_layout(uint32_t RL, uint32_t num_weight_lists, uint32_t kmax, uint32_t ag_lds) {
+// frame_bytes: SE_FRAME_BYTES for the single-end kernels; 0 for the paired-end ones, whose frame is laid out by paired_lds_layout
+static __host__ __device__ __forceinline__ LdsLayout lds_layout(uint32_t RL, uint32_t num_weight_lists, uint32_t kmax, uint32_t ag_lds, uint32_t frame_bytes = 0) {
     LdsLayout L; uint32_t o = 0;
     L.rd0 = o; o += RL; L.rd1 = o; o += RL; L.ql0 = o; o += RL; L.ql1 = o; o += RL;
     L.gw = o; o += (RL + 2 * WIN_PAD + 15) & ~15u;
@@ -86,6 +93,7 @@ static __host__ __device__ __forceinline__ LdsLayout lds_layout(uint32_t RL, uin
     L.rp = o; o += (2 * 4 * read_plane_words(RL) * 8 + 15) & ~15u;          // read planes: [direction][code bit 0, code bit 1, N, other][word]
     L.tp = o; o += (3 * text_plane_blocks(RL, WIN_PAD) * 8 + 15) & ~15u;    // text planes of the candidate window: [plane][block]
     L.lvp = o; o += (lv_plane_work_words(RL) * 8 + 15) & ~15u;              // Landau-Vishkin's prepared plane words (planes.h)
+    L.frame = o; o += (frame_bytes + 15) & ~15u;
     L.total = o;
     return L;
 }

@@ -1,11 +1,13 @@
 // single_kernel.h -- the single-end kernel: one wavefront per read, persistent grid, atomic work counter.
 // SEC = with secondary results (-om); a separate instantiation so that the default kernel carries none of it.
 #pragma once
+#include <new>
 #include "kernel_common.h"
 
-// Latency-bound kernel.  The 192-position affine-gap variant (reads up to ~170 bp) asks for 6 waves per SIMD (80 VGPRs, ~75 dwords
-// of cold state spilled): measured 3.96 M reads/s against 3.74-3.80 M at 4 and 3.79 M at 5 waves (profiles/r01g).  The variants
-// with more affine-gap state in registers stay at 4 (128 VGPRs); their LDS footprint caps occupancy first anyway.
+// Latency-bound kernel.  The 192-position affine-gap variant (reads up to ~170 bp) asks for 6 waves per SIMD (80 VGPRs): measured
+// 3.96 M reads/s against 3.74-3.80 M at 4 and 3.79 M at 5 waves (profiles/r01g) with the Aligner in registers and its cold state spilled;
+// with the Aligner in the wave's LDS frame (61 spilled VGPRs instead of 116) the pair has not been measured again (profiles/r07a).  The
+// variants with more affine-gap state in registers stay at 4 (128 VGPRs); their LDS footprint caps occupancy first anyway.
 #ifndef SNAPGPU_WAVES_PER_SIMD
 #define SNAPGPU_WAVES_PER_SIMD(AGC) ((AGC) == 3 ? 6 : 4)            // (AGC 4 / 6 -- which since round 6 keep three chunks in registers like AGC 3 -- at 6: 250 bp / -d 20 reads 5.10 against 5.29 M reads/s at 4, profiles/r06g)
 #endif
@@ -16,18 +18,15 @@ __global__ __launch_bounds__(256, SNAPGPU_WAVES_PER_SIMD(AGC)) void k_align_sing
     const int lane = lane_id();
     const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // uniform: keeps the LDS/scratch pointers in SGPRs
     const uint32_t wave_slot = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave_in_block;
-    const LdsLayout L = lds_layout(a.cfg.RL, a.cfg.num_weight_lists, a.cfg.kmax, a.cfg.ag_lds);
+    const LdsLayout L = lds_layout(a.cfg.RL, a.cfg.num_weight_lists, a.cfg.kmax, a.cfg.ag_lds, SE_FRAME_BYTES);
     uint8_t *my = lds + (size_t)wave_in_block * L.total;
 
     WaveShared *ws = (WaveShared *)(my + L.shared);
-#if !defined(SNAPGPU_REGDIR)
-    Aligner<AGC, SEC, EXACT, TIMED, PLANES> al(a.ix, a.tab, a.cfg, ws);
-#else
-    // (measurement builds: the candidate table's directory in a vector register -- align_single.h: REGDIR.  It takes findElement's two dependent HBM loads
-    //  away and was 1.5 % SLOWER on the bench batch, 15.0 against 15.3 M reads/s, profiles/r06f: five more spilled VGPRs, and the loads it removes are not what
-    //  the hit phase waits for)
-    Aligner<AGC, SEC, EXACT, TIMED, PLANES, true> al(a.ix, a.tab, a.cfg, ws);
-#endif
+    // the wave's frame (kernel_common.h: SE_FRAME_BYTES): the object is constructed in LDS, as k_align_paired does.  The help for heavy reads
+    // (se_help.h) is compiled into the fast forms only.
+    typedef Aligner<AGC, SEC, EXACT, TIMED, PLANES, !EXACT> AL_T;
+    static_assert(sizeof(AL_T) <= SE_FRAME_BYTES, "the wave's frame does not fit SE_FRAME_BYTES");
+    AL_T &al = *new (my + L.frame) AL_T(a.ix, a.tab, a.cfg, ws);
     al.rd[0] = my + L.rd0; al.rd[1] = my + L.rd1;
     al.ql[0] = my + L.ql0; al.ql[1] = my + L.ql1;
     al.gw = my + L.gw;
@@ -59,10 +58,12 @@ __global__ __launch_bounds__(256, SNAPGPU_WAVES_PER_SIMD(AGC)) void k_align_sing
     uint64_t n_done = 0;
     // help for heavy reads (se_help.h): not in the exact replay, not without the context's arrays
     const bool se_on = !EXACT && a.se_slots != nullptr && a.cfg.se_items_cap != 0;
-    al.se_slots = se_on ? a.se_slots : nullptr; al.se_n_slots = a.se_n_slots; al.se_spec = a.se_spec; al.se_spec_cap = a.se_spec_cap;
-    al.se_ctl = a.se_ctl; al.se_eager = a.se_eager; al.se_diag = a.counters + 14;
-    al.se_items = (uint32_t *)(sc + a.cfg.se_off); al.se_first = al.se_items + a.cfg.se_items_cap;
-    al.se_slot = -1; al.se_n = 0; al.se_tried = 0; al.cur_read = 0; al.se_mine = nullptr;
+    if constexpr (!EXACT) {
+        al.se_slots = se_on ? a.se_slots : nullptr; al.se_n_slots = a.se_n_slots; al.se_spec = a.se_spec; al.se_spec_cap = a.se_spec_cap;
+        al.se_ctl = a.se_ctl; al.se_eager = a.se_eager; al.se_diag = a.counters + 14;
+        al.se_items = (uint32_t *)(sc + a.cfg.se_off); al.se_first = al.se_items + a.cfg.se_items_cap;
+        al.se_slot = -1; al.se_n = 0; al.se_tried = 0; al.cur_read = 0; al.se_mine = nullptr;
+    }
 
     // EXACT kernels run either over a list of flagged reads (remap: the replay pass behind the register variants for long reads) or, as
     // the main pass of the 192-position variant, over the whole batch
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256, SNAPGPU_WAVES_PER_SIMD(AGC)) void k_align_sing
         if (a.remap) i = first_u32(a.remap[i]);
         else if (a.order) i = first_u32(a.order[i]);
         al.new_read_images();           // EXACT: a newly constructed reference aligner: both traceback arrays read as zero
-        al.cur_read = i;
+        if constexpr (!EXACT) al.cur_read = i;
         uint64_t b = first_u64(a.offsets[i]), e = first_u64(a.offsets[i + 1]);
         if (a.front_clip) {
             b += (uint64_t)first_u32((uint32_t)a.front_clip[i]); e = b + (uint64_t)first_u32((uint32_t)a.data_len[i]);

@@ -796,7 +796,7 @@ extern "C" int snapgpu_create(const snapgpu_index_view *idx, const snapgpu_param
     c.se_off = ((size_t)c.ht_size * 2 + (size_t)c.pool_size * sizeof(Elem) + ag_bytes + 255) & ~(size_t)255;
     c.scratch_stride = (c.se_off + ((size_t)c.se_items_cap + (c.se_items_cap ? c.pool_size : 0u)) * 4 + 255) & ~(size_t)255;
     c.ag_lds = !c.ag_buffers ? 0u : (ctx->ag_variant == 3 ? ag_lds_bytes_reg(c.RL, 3) : ag_lds_bytes(c.RL));
-    LdsLayout L = lds_layout(c.RL, c.num_weight_lists, c.kmax, c.ag_lds);
+    LdsLayout L = lds_layout(c.RL, c.num_weight_lists, c.kmax, c.ag_lds, SE_FRAME_BYTES);
     c.lds_per_wave = L.total;
 
     // waves in flight: a fixed number per CU, each with its own scratch slab
@@ -808,6 +808,8 @@ extern "C" int snapgpu_create(const snapgpu_index_view *idx, const snapgpu_param
     if ((size_t)4 * L.total > 160 * 1024) { snapgpu_destroy(ctx); return fail(nullptr, SNAPGPU_E_UNSUPPORTED, "per-read LDS state exceeds 40 KiB per wave (max_read_len / num_seeds / max_k too large)"); }
     ctx->n_wave_slots = (uint32_t)ctx->num_cus * (uint32_t)waves_per_cu;
     ctx->n_wave_slots = (ctx->n_wave_slots + 3) & ~3u;
+    if (getenv("SNAPGPU_VERBOSE")) fprintf(stderr, "snapgpu: single-end context: AGC %d RL %u weight_lists %u kmax %u ag_lds %u: lds_per_wave %u (%u without the wave's frame), %d waves per CU, %u wave slots\n",
+                                           ctx->ag_variant, c.RL, c.num_weight_lists, c.kmax, c.ag_lds, (unsigned)c.lds_per_wave, (unsigned)L.frame, waves_per_cu, ctx->n_wave_slots);
     size_t scratch_total = (size_t)ctx->n_wave_slots * c.scratch_stride;
     CRCHK(hipMalloc((void **)&ctx->d_scratch, scratch_total), SNAPGPU_E_NOMEM);
     // the head tables must start zeroed (one fill of the whole slab is cheaper than a fill per wave)
