@@ -31,6 +31,8 @@
  *       useful-read test :680-682), followed by SimpleReadWriter::writePairs  SNAPLib/ReadWriter.cpp:345-520
  *   snapgpu_align_sam_single_records
  *       AlignRead with secondary results, finalizeSecondaryResults, writeReads per result  SNAPLib/SingleAligner.cpp:250-325, BaseAligner.cpp:2423-2553
+ *   snapgpu_sam_text_single / _device, snapgpu_align_sam_single_text
+ *       SAMFormat::createSAMLine / writeRead, the printed line of a single-end record  SNAPLib/SAM.cpp:1424-1572 / 1898-2352
  *   snapgpu_sam_fields_single
  *       SimpleReadWriter::writeReads            SNAPLib/ReadWriter.cpp:170-330
  *       SAMFormat::writeRead / createSAMLine / computeCigarString  SNAPLib/SAM.cpp:1898-2352 / 1424-1572 / 2595-2766
@@ -70,6 +72,7 @@ extern "C" {
 #define SNAPGPU_E_LAUNCH       -5   /* kernel launch or execution failed                 */
 #define SNAPGPU_W_SECONDARY_TRUNCATED 1 /* some read has more secondary results than the caller's stride: see snapgpu_align_single_secondary */
 #define SNAPGPU_W_RECORDS_TRUNCATED 2   /* the batch has more SAM records than the caller's record capacity: see snapgpu_align_sam_single_records */
+#define SNAPGPU_W_TEXT_TRUNCATED 3      /* the SAM lines need more bytes than the caller's text capacity: see snapgpu_sam_text_single_device */
 
 /* mirrors enum AlignmentResult, SNAPLib/AlignmentResult.h:33 */
 enum { SNAPGPU_NotFound = 0, SNAPGPU_SingleHit = 1, SNAPGPU_MultipleHits = 2 };
@@ -519,6 +522,75 @@ int  snapgpu_align_sam_single_records_device(snapgpu_ctx *ctx, uint32_t n, uint3
                                              void *d_n_secondary, uint64_t record_capacity, uint64_t *n_records, void *d_rec_begin, void *d_rec_read,
                                              void *d_rec_kind, void *d_flag, void *d_contig, void *d_pos, void *d_mapq, void *d_ops, uint32_t ops_stride,
                                              void *d_n_ops, void *d_nm, void *d_reference_history_dependent, void *stream);
+
+/*
+ * The names the SAM-line calls below print as RNAME: names[c] (NUL-terminated) is the name of contig c of the index, in the index's order
+ * (what `contig` of the SAM-field calls indexes).  The names go to HBM once, as a blob and its offsets; calling again replaces them.
+ * n_contigs must be the index's contig count (SNAPGPU_E_INVALID otherwise).  Per context: a replica has no names until it is given them.
+ */
+int  snapgpu_set_contig_names(snapgpu_ctx *ctx, uint32_t n_contigs, const char *const *names);
+
+/*
+ * Records to the bytes of their SAM lines, on the device: the last step of the single-end SAM side.  For each record the line that
+ * SAMFormat::writeRead and createSAMLine print into a SAM (not BAM) file (SNAPLib/SAM.cpp:1898-2352 / 1424-1572), byte for byte:
+ *   QNAME \t FLAG \t RNAME \t POS \t MAPQ \t CIGAR \t * \t 0 \t 0 \t SEQ \t QUAL \t PG:Z:SNAP \t NM:i:<nm> \t RG:Z:FASTQ \t PL:Z:Illumina \t PU:Z:pu \t LB:Z:lb \t SM:Z:sm \n
+ * QNAME is the read's name cut at its first space (SAM.cpp:2001-2004); RNAME the contig's name (snapgpu_set_contig_names) or "*" for
+ * contig -1; CIGAR "*" for n_ops < 0, nothing for n_ops == 0, otherwise <op >> 4><"MIDNSHP=X"[op & 15]> per operation; SEQ / QUAL the whole
+ * (unclipped) read, under flag 0x10 its reverse complement (A<->T, C<->G, anything else N) and the qualities reversed.
+ * This is the pure formatter, every array in HBM: the reads (d_bases, d_quals, d_offsets as everywhere), their names (d_names, a blob;
+ * d_name_off uint64[n_reads + 1]), and per record the fields as the SAM-field calls leave them (d_flag .. d_nm; d_ops: ops_stride per
+ * record).  d_rec_read NULL: record i belongs to read i (the layout of snapgpu_align_sam_single and snapgpu_sam_fields_single);
+ * otherwise the list snapgpu_align_sam_single_records_device left behind.
+ *   text_capacity   bytes d_text has room for
+ *   d_text          out: the lines, one after the other
+ *   d_line_begin    out, uint64[n_records + 1]: record i's line is d_text[line_begin[i] .. line_begin[i + 1])
+ *   text_bytes      out (a host word): bytes the lines need, = line_begin[n_records]
+ * Returns SNAPGPU_OK, or SNAPGPU_W_TEXT_TRUNCATED (> 0) when *text_bytes > text_capacity: d_line_begin is complete all the same, every
+ * line that lies wholly below text_capacity is written exactly as a large enough call writes it, nothing at or beyond text_capacity is
+ * touched, and the caller enlarges and calls again.  A record with n_ops > ops_stride or a contig the index does not have: SNAPGPU_E_INVALID.
+ * SNAPGPU_E_INVALID too when the context has no contig names.  Synchronous on `stream` (NULL: the context's): *text_bytes is read back
+ * inside the call.  n_records == 0 writes d_line_begin[0] = 0 and *text_bytes = 0.
+ */
+int  snapgpu_sam_text_single_device(snapgpu_ctx *ctx, uint64_t n_records,
+                                    const void *d_bases, const void *d_quals, const void *d_offsets,
+                                    const void *d_names, const void *d_name_off,
+                                    const void *d_rec_read,
+                                    const void *d_flag, const void *d_contig, const void *d_pos, const void *d_mapq,
+                                    const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                    uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream);
+
+/* Host-pointer form of snapgpu_sam_text_single_device: n_reads sizes the uploads of the reads and their names (rec_read NULL: n_records ==
+ * n_reads); the inputs go up, the lines that were written and line_begin come down.  (SAMFormat::createSAMLine / writeRead, SAM.cpp:1424-1572,
+ * 1898-2352, as above.) */
+int  snapgpu_sam_text_single(snapgpu_ctx *ctx, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
+                             const char *names, const uint64_t *name_off, const uint32_t *rec_read,
+                             const int32_t *flag, const int32_t *contig, const int64_t *pos, const int32_t *mapq,
+                             const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes);
+
+/*
+ * Single-end reads to the TEXT of all their SAM records in ONE call: snapgpu_align_sam_single_records followed by the lines of its
+ * records (SAMFormat::createSAMLine / writeRead, SAM.cpp:1424-1572, 1898-2352), with one upload -- the batch as for that call, plus the
+ * reads' names -- and one download.  In between the library runs snapgpu_align_sam_single_records_device on device arrays of its own and
+ * the SAM-line kernels over the records it left there.  Host pointers.
+ *   ctx, n .. adjust_primary   as snapgpu_align_sam_single_records (every single-end option set: plain, -om / -omax / -mpc, -ea, -ae)
+ *   names, name_off            the reads' names: a blob and uint64[n + 1] offsets
+ *   ops_stride                 room per record for its cigar operations, in the library's own array
+ *   record_capacity, n_records, rec_begin[n + 1]   as snapgpu_align_sam_single_records
+ *   flag                       [record_capacity] out: the records' flags (a caller counts its mapped records from them)
+ *   text_capacity, text, text_bytes                as snapgpu_sam_text_single
+ *   line_begin                 [record_capacity + 1] out
+ * Returns SNAPGPU_OK, SNAPGPU_W_RECORDS_TRUNCATED (the lines of the first record_capacity records are then what was attempted) or
+ * SNAPGPU_W_TEXT_TRUNCATED; when both capacities are too small the records warning comes first.  The caller enlarges and calls again.
+ * A record whose cigar does not fit ops_stride (nm -2) would print a wrong line: the call fails with SNAPGPU_E_INVALID and a message that
+ * names ops_stride, and the caller calls again with a larger one.  -ae's refusal of a reader-clipped read at a contig's end passes through
+ * unchanged (SNAPGPU_E_UNSUPPORTED, "-ae: ...").
+ */
+int  snapgpu_align_sam_single_text(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                   const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                   const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                   uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                   uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes);
 
 /*
  * The paired-end writer: for the primary PairedAlignmentResult of each pair, the computed fields of BOTH SAM records -- what

@@ -62,6 +62,7 @@ NOT_FOUND, SINGLE_HIT, MULTIPLE_HITS = 0, 1, 2
 SCORE_ABOVE_LIMIT = -1
 INVALID_GENOME_LOCATION_32 = 0xFFFFFFFF
 MAX_K = 127
+W_TEXT_TRUNCATED = 3             # SNAPGPU_W_TEXT_TRUNCATED (include/snapgpu.h)
 
 
 class IndexView(C.Structure):

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from .abi import (Counters, IndexView, Params, RESULT_DTYPE, default_params, ptr)
+from .abi import (Counters, IndexView, Params, RESULT_DTYPE, W_TEXT_TRUNCATED, default_params, ptr)
 from .index import GENOME_PAD, GenomeIndex
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,7 +53,7 @@ EXPORTED_SYMBOLS = [
     "snapgpu_align_single_device", "snapgpu_get_counters", "snapgpu_kernel_time",
     "snapgpu_enable_secondary", "snapgpu_align_single_secondary", "snapgpu_align_single_secondary_device",
     "snapgpu_align_paired_secondary", "snapgpu_align_paired_secondary_device",
-    "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_single_records", "snapgpu_align_sam_single_records_device", "snapgpu_align_sam_paired", "snapgpu_create_replica_with_params",
+    "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_single_records", "snapgpu_align_sam_single_records_device", "snapgpu_set_contig_names", "snapgpu_sam_text_single", "snapgpu_sam_text_single_device", "snapgpu_align_sam_single_text", "snapgpu_align_sam_paired", "snapgpu_create_replica_with_params",
     "snapgpu_default_index_build_params", "snapgpu_index_build", "snapgpu_index_build_from_fasta", "snapgpu_index_build_shaped",
     "snapgpu_index_build_from_fasta_shaped", "snapgpu_built_index_view",
     "snapgpu_built_index_save", "snapgpu_built_index_stats", "snapgpu_built_index_destroy",
@@ -418,6 +418,100 @@ class BaseAligner:
         if rc != W_RECORDS_TRUNCATED:
             self._check(rc, "snapgpu_align_sam_single_records_device")
         return int(n_rec.value), rc == W_RECORDS_TRUNCATED
+
+    # ---- records -> the bytes of their SAM lines (SAMFormat::createSAMLine / writeRead) ----
+    def setContigNames(self, names):
+        """snapgpu_set_contig_names: the RNAME of contig c is names[c] (str or bytes), one name per contig of the index."""
+        enc = [n if isinstance(n, bytes) else str(n).encode() for n in names]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        self.lib.snapgpu_set_contig_names.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        self._check(self.lib.snapgpu_set_contig_names(self.handle, C.c_uint32(len(enc)), C.cast(arr, C.c_void_p)), "snapgpu_set_contig_names")
+
+    def samText(self, bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rec_read=None, capacity: int | None = None,
+                grow: bool = True, text=None):
+        """The SAM lines of a batch's records (snapgpu_sam_text_single): bases / quals / offsets the unclipped reads, names / name_off
+        (uint64[n_reads + 1]) their names, flag .. nm the records' fields as samFields / alignSamRecords return them (ops: [n_records,
+        ops_stride]); rec_read: the read of each record (None: record i is read i).  capacity: bytes of text to make room for (default:
+        an estimate); grow: call again with the size the library asks for when that was too few.  text: a uint8 array to write into
+        (its size is the capacity).  Returns dict(text uint8[capacity], line_begin uint64[n_records + 1], text_bytes, truncated)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1); quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        names = np.ascontiguousarray(names, dtype=np.uint8).reshape(-1); name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        flag = np.ascontiguousarray(flag, dtype=np.int32); contig = np.ascontiguousarray(contig, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int64); mapq = np.ascontiguousarray(mapq, dtype=np.int32)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32); n_ops = np.ascontiguousarray(n_ops, dtype=np.int32); nm = np.ascontiguousarray(nm, dtype=np.int32)
+        n_rec = flag.size
+        ops_stride = ops.shape[1] if ops.ndim == 2 else (ops.size // n_rec if n_rec else 1)
+        if rec_read is not None:
+            rec_read = np.ascontiguousarray(rec_read, dtype=np.uint32)
+        n_reads = offsets.size - 1
+        cap = text.size if text is not None else (int(capacity) if capacity is not None else 2 * int(bases.size) + 256 * n_rec + 64)
+        line_begin = np.zeros(n_rec + 1, np.uint64)
+        f = self.lib.snapgpu_sam_text_single
+        f.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3
+        while True:
+            if text is None or text.size != cap:
+                text = np.zeros(cap, np.uint8)
+            tb = C.c_uint64(0)
+            rc = f(self.handle, n_rec, n_reads, ptr(bases), ptr(quals), ptr(offsets), ptr(names), ptr(name_off), ptr(rec_read) if rec_read is not None else None,
+                   ptr(flag), ptr(contig), ptr(pos), ptr(mapq), ptr(ops), ops_stride, ptr(n_ops), ptr(nm), cap, ptr(text), ptr(line_begin), C.addressof(tb))
+            if rc == W_TEXT_TRUNCATED and grow:
+                cap = int(tb.value)
+                continue
+            if rc != W_TEXT_TRUNCATED:
+                self._check(rc, "snapgpu_sam_text_single")
+            return dict(text=text, line_begin=line_begin, text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED)
+
+    def samText_device(self, n_records: int, d_bases: int, d_quals: int, d_offsets: int, d_names: int, d_name_off: int, d_rec_read: int, d_flag: int,
+                       d_contig: int, d_pos: int, d_mapq: int, d_ops: int, ops_stride: int, d_n_ops: int, d_nm: int, capacity: int, d_text: int,
+                       d_line_begin: int, stream: int = 0):
+        """Device-pointer form of samText (snapgpu_sam_text_single_device): every array in HBM (d_rec_read 0: record i is read i), the text
+        and line_begin left there.  Synchronous on `stream` (0: the context's).  Returns (text_bytes, truncated)."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        f = self.lib.snapgpu_sam_text_single_device
+        f.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11 + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4
+        tb = C.c_uint64(0)
+        rc = f(self.handle, n_records, vp(d_bases), vp(d_quals), vp(d_offsets), vp(d_names), vp(d_name_off), vp(d_rec_read), vp(d_flag), vp(d_contig), vp(d_pos),
+               vp(d_mapq), vp(d_ops), ops_stride, vp(d_n_ops), vp(d_nm), capacity, vp(d_text), vp(d_line_begin), C.addressof(tb), vp(stream))
+        if rc != W_TEXT_TRUNCATED:
+            self._check(rc, "snapgpu_sam_text_single_device")
+        return int(tb.value), rc == W_TEXT_TRUNCATED
+
+    def alignSamText(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
+                     adjust_primary: bool = False, capacity: int | None = None, text_capacity: int | None = None, grow: bool = True):
+        """Single-end reads to the text of all their SAM records in one call (snapgpu_align_sam_single_text): alignSamRecords' inputs plus the
+        reads' names; capacity / text_capacity: records / bytes to make room for (defaults: estimates); grow: call again with what the
+        library asks for when one was too small.  Returns dict(text, line_begin, text_bytes, truncated, n_records, records_truncated,
+        rec_begin, flag); line_begin and flag are cut to the records that were formatted."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1); quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        front_clip = np.ascontiguousarray(front_clip, dtype=np.int32); data_len = np.ascontiguousarray(data_len, dtype=np.int32)
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        names = np.ascontiguousarray(names, dtype=np.uint8).reshape(-1); name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        n = offsets.size - 1
+        cap = int(capacity) if capacity is not None else n + n // 2 + 16
+        tcap = int(text_capacity) if text_capacity is not None else 3 * int(bases.size) + 256 * cap + 64
+        rec_begin = np.zeros(n + 1, np.uint64)
+        f = self.lib.snapgpu_align_sam_single_text
+        f.argtypes = ([C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 3 +
+                      [C.c_uint64] + [C.c_void_p] * 3)
+        while True:
+            flag = np.zeros(cap, np.int32); line_begin = np.zeros(cap + 1, np.uint64); text = np.zeros(tcap, np.uint8)
+            n_rec = C.c_uint64(0); tb = C.c_uint64(0)
+            rc = f(self.handle, n, ptr(bases), ptr(quals), ptr(offsets), ptr(front_clip), ptr(data_len), ptr(skip), 1 if use_m else 0, 1 if adjust_primary else 0,
+                   ptr(names), ptr(name_off), ops_stride, cap, C.addressof(n_rec), ptr(rec_begin), ptr(flag), tcap, ptr(text), ptr(line_begin), C.addressof(tb))
+            if rc == W_RECORDS_TRUNCATED and grow:
+                cap = int(n_rec.value)
+                continue
+            if rc == W_TEXT_TRUNCATED and grow:
+                tcap = int(tb.value)
+                continue
+            if rc not in (W_RECORDS_TRUNCATED, W_TEXT_TRUNCATED):
+                self._check(rc, "snapgpu_align_sam_single_text")
+            break
+        m = min(int(n_rec.value), cap)
+        return dict(text=text, line_begin=line_begin[:m + 1], text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED, n_records=int(n_rec.value),
+                    records_truncated=rc == W_RECORDS_TRUNCATED, rec_begin=rec_begin, flag=flag[:m])
 
     def samFieldsPaired(self, bases, quals, offsets, front_clip, data_len, results, use_m: bool = False, ops_stride: int = 64):
         """SAMFormat::writePairs + fillMateInfo up to the point of printing (see snapgpu_sam_fields_paired).  offsets has 2 n + 1

@@ -101,6 +101,27 @@ struct SamRecArgs {
     const uint32_t *ovf_n_secondary;                                             // [n_overflow] what the rerun counted
     uint64_t *clip_off;                                                          // [n] offsets[i] + front_clip[i]: where the adjuster's read starts
 };
+// snapgpu_sam_text_single*: records -> the bytes of their SAM lines (sam_text.h).  Record r belongs to read rec_read[r] (NULL: read r).
+#define SAMTEXT_NM_OVERFLOW 1u      // a record whose cigar did not fit ops_stride (nm == -2: sam_fields.h)
+#define SAMTEXT_BAD_RECORD 2u       // n_ops > ops_stride or a contig the index does not have: printed as "*", the call is refused
+struct SamTextSummary {
+    unsigned long long total;         // bytes the lines of the batch need
+    unsigned long long written;       // end of the last line that lies wholly below the capacity
+    uint32_t flags, pad;
+};
+struct SamTextArgs {
+    uint32_t n, n_chunks, ops_stride, n_contigs;                                 // n records, in tiles of SAMREC_CHUNK
+    const uint8_t *bases; const uint8_t *quals; const uint64_t *offsets;         // the reads (unclipped: SEQ and QUAL are the whole read)
+    const uint8_t *names; const uint64_t *name_off;                              // read i's name: names[name_off[i] .. name_off[i + 1])
+    const uint32_t *rec_read;                                                    // [n] or NULL
+    const int32_t *flag; const int32_t *contig; const int64_t *pos; const int32_t *mapq; const uint32_t *ops; const int32_t *n_ops; const int32_t *nm;
+    const uint8_t *contig_names; const uint32_t *contig_name_off;                // snapgpu_set_contig_names: a blob and n_contigs + 1 offsets
+    uint64_t cap;                                                                // bytes `text` has room for
+    uint8_t *text; uint64_t *line_begin;                                         // [cap], [n + 1]
+    uint32_t *len; uint64_t *partial;                                            // [n] line lengths, [n_chunks] tile sums -> their exclusive scan
+    SamTextSummary *summary;
+};
+extern "C" void snapgpu_launch_sam_text(const SamTextArgs *a, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_count(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_list(const SamRecArgs *a, uint32_t blocks, hipStream_t s);

@@ -1,7 +1,7 @@
 // cigar_k.hip -- the SAM writer's kernels, one wavefront per item on a persistent grid: SAMFormat::computeCigar for a batch of written reads
 // (k_cigar_lv, k_cigar_ag), result -> SAM fields (k_sam_fields*: one body, sam_fields_run, over the reads of a batch, the records of a record
 // list or the mates of a paired batch, with the pre-pass k_samf_dp8* ahead of it), AlignmentAdjuster (k_adjust_alignments) and the launches
-// of the record-list kernels (sam_records.h).
+// of the record-list kernels (sam_records.h) and of the SAM-line kernels (sam_text.h).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -c cigar_k.hip
 #include <hip/hip_runtime.h>
 #include "cigar_lv.h"
@@ -10,6 +10,7 @@
 #include "adjust.h"
 #include "cigar_args.h"
 #include "sam_records.h"
+#include "sam_text.h"
 
 __global__ __launch_bounds__(256) void k_cigar_lv(CigarArgs a)
 {
@@ -522,4 +523,13 @@ extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hi
 extern "C" void snapgpu_launch_samrec_clip_off(const SamRecArgs *a, uint32_t blocks, hipStream_t s)
 {
     hipLaunchKernelGGL(k_samrec_clip_off, dim3(blocks), dim3(256), 0, s, *a);
+}
+
+// ---- records -> the bytes of their SAM lines (sam_text.h): lengths, their scan, the lines that fit the capacity -----------------------------
+extern "C" void snapgpu_launch_sam_text(const SamTextArgs *a, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_samtext_len, dim3(scan_blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samtext_partials, dim3(1), dim3(64), 0, s, *a);
+    hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samtext_write, dim3(write_blocks), dim3(256), 0, s, *a);
 }

@@ -291,6 +291,7 @@ struct Work {                                // a batch on its way through the p
     std::vector<uint8_t> skip;               // single end: read i is not given to the aligner (the fused call's argument)
     uint32_t max_len = 0;                    // the longest read of the batch (unclipped): picks the context's read-length class
     std::string text;                        // the formatted records (BAM: BGZF blocks)
+    bool text_done = false;                  // the feeder left the SAM lines in `text` (SNAPGPU_SAM_DEVICE_TEXT): nothing for the formatter to do
     bool bam = false;
     unsigned long long mapped = 0;
     // as newly constructed, but every vector keeps its capacity (WorkPool)
@@ -301,7 +302,7 @@ struct Work {                                // a batch on its way through the p
         emit.clear(); pu_pair.clear(); pu_secondary.clear(); su_read.clear();
         s_flag.clear(); s_contig.clear(); s_mapq.clear(); s_n_ops.clear(); s_nm.clear(); s_pos.clear(); s_ops.clear(); s_ops_stride = 64;
         prepared = false; front_clip.clear(); data_len.clear(); to_align.clear(); ab.clear(); aq.clear(); ao.clear(); skip.clear();
-        max_len = 0; text.clear(); bam = false; mapped = 0;
+        max_len = 0; text.clear(); text_done = false; bam = false; mapped = 0;
     }
 };
 
@@ -517,6 +518,11 @@ static uint32_t class_len(const Options &o, int k) { return RL_CLASS[k] && RL_CL
 static void configure_ctx(const Options &o, snapgpu_ctx *c)
 {
     snapgpu_set_aligner_flags(c, o.stop_on_first_hit ? 1 : 0, o.explore_popular_seeds ? 1 : 0);      // -f, -x (single-end launches only)
+    {   // RNAME of the SAM-line kernels (snapgpu_align_sam_single_text): the contig table in the index's order
+        std::vector<const char *> names; for (const Contig &ct : *g_contigs) names.push_back(ct.name.c_str());
+        int rc = snapgpu_set_contig_names(c, (uint32_t)names.size(), names.data());
+        if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_set_contig_names failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); }
+    }
     if (o.paired) { int rc = snapgpu_enable_paired(c, &o.pp); if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_enable_paired failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); } }
     if (o.om >= 0) {
         snapgpu_secondary_params sp; memset(&sp, 0, sizeof(sp));
@@ -564,6 +570,15 @@ static bool single_records_path(const Options &o)
     static const bool fused_on = getenv("SNAPGPU_SAM_SINGLE_FUSED") && atoi(getenv("SNAPGPU_SAM_SINGLE_FUSED")) != 0;
     return fused_on && !o.paired && (o.om >= 0 || o.ae || o.p.emit_alt_alignments != 0);
 }
+// SNAPGPU_SAM_DEVICE_TEXT=1: `single` with SAM output takes the LINES of a batch from the device (snapgpu_align_sam_single_text, every option
+// set) and the formatter threads pass the batch through.  Off unless asked for: DESIGN.md section 13 has what to measure before that changes.
+// BAM output and `paired` do not have the path and ignore the switch.  The file is the same bytes either way (tests/test_zz_gpu_sam_text.py).
+static bool device_text_path(const Options &o)
+{
+    static const bool on = getenv("SNAPGPU_SAM_DEVICE_TEXT") && atoi(getenv("SNAPGPU_SAM_DEVICE_TEXT")) != 0;
+    return on && !o.paired && !o.bam;
+}
+static std::atomic<uint32_t> g_text_extra_per_record(128);      // text capacity of the next call: bytes per record beyond its name, SEQ and QUAL; grows to what batches have needed
 static std::atomic<uint32_t> g_records_per_read_x16(24);        // record capacity of the next call, in sixteenths of a record per read: grows to what batches have needed
 
 // Read::clip and the useless-read filter for a batch, and the reads to align gathered into one buffer: host work that does not need the GPU,
@@ -573,7 +588,7 @@ static void prepare_single(const Options &o, Work &w)
     const Batch &b = w.b;
     const size_t n = b.n();
     w.front_clip.assign(n, 0); w.data_len.assign(n, 0); w.skip.assign(n, 1); w.to_align.clear(); w.ab.clear(); w.aq.clear(); w.ao.assign(1, 0);
-    const bool fused = (o.om < 0 && !o.ae) || single_records_path(o);      // gpu_single's one-call paths work on the batch itself: nothing to gather
+    const bool fused = (o.om < 0 && !o.ae) || single_records_path(o) || device_text_path(o);      // gpu_single's one-call paths work on the batch itself: nothing to gather
     if (!fused) { w.ab.reserve(b.bases.size()); w.aq.reserve(b.quals.size()); w.ao.reserve(n + 1); }
     w.to_align.reserve(n);
     w.max_len = 0;
@@ -591,6 +606,49 @@ static void prepare_single(const Options &o, Work &w)
 }
 
 static bool g_index_has_alt = false;        // the index has ALT contigs: only then can a first-ALT result (an extra record) exist
+// SNAPGPU_SAM_DEVICE_TEXT: the batch goes up as it was parsed, with its names, and its SAM lines come down.  Both capacities start from an
+// estimate and follow what the library reports; a cigar that outgrows its row is met with a larger row, as with_growing_stride does.
+static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
+{
+    auto t_stage = std::chrono::steady_clock::now();
+    auto lap = [&](std::atomic<unsigned long long> &acc) { const auto t = std::chrono::steady_clock::now(); acc += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(t - t_stage).count(); t_stage = t; };
+    const Batch &b = w.b;
+    const size_t n = b.n();
+    w.text.clear(); w.text_done = true; w.mapped = 0;
+    if (n == 0) return;
+    if (!w.prepared) prepare_single(o, w);
+    snapgpu_ctx *ctx = ctx_for(o, fc, w.max_len);
+    std::vector<uint64_t> name_off(b.name_off.begin(), b.name_off.end()), rec_begin(n + 1), line_begin;
+    size_t cap = (n * (size_t)g_records_per_read_x16.load() + 15) / 16 + 16;
+    const size_t per_read = (2 * b.bases.size() + b.names.size() + n - 1) / n;             // name, SEQ and QUAL of the average record
+    size_t tcap = cap * (per_read + g_text_extra_per_record.load());
+    uint32_t ops_stride = o.ops_stride;
+    uint64_t n_rec = 0, text_bytes = 0;
+    lap(g_ns_prep);
+    for (;;) {
+        w.flag.resize(cap); line_begin.resize(cap + 1); w.text.resize(tcap);
+        const int rc = snapgpu_align_sam_single_text(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
+                                                     w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
+                                                     (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
+        if (rc == SNAPGPU_E_UNSUPPORTED && o.ae && !strncmp(snapgpu_last_error(ctx), "-ae:", 4))
+            die("-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)");
+        if (rc == SNAPGPU_W_RECORDS_TRUNCATED) { cap = (size_t)n_rec + (size_t)n_rec / 16; tcap = cap * (per_read + g_text_extra_per_record.load()); continue; }
+        if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; continue; }
+        if (rc == SNAPGPU_E_INVALID && strstr(snapgpu_last_error(ctx), "ops_stride")) {
+            if (ops_stride >= 4096) die("a cigar needs more than 4096 operations");
+            ops_stride *= 4; continue;
+        }
+        if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_single_text", rc);
+        break;
+    }
+    const size_t nr = (size_t)n_rec;
+    { const uint32_t need = (uint32_t)((nr * 16 + n - 1) / n) + 2; uint32_t cur = g_records_per_read_x16.load(); while (need > cur && !g_records_per_read_x16.compare_exchange_weak(cur, need)) {} }
+    if (nr) { const size_t per_rec = ((size_t)text_bytes + nr - 1) / nr; const uint32_t need = per_rec > per_read ? (uint32_t)(per_rec - per_read) + 16 : 16;
+              uint32_t cur = g_text_extra_per_record.load(); while (need > cur && !g_text_extra_per_record.compare_exchange_weak(cur, need)) {} }
+    w.text.resize((size_t)text_bytes);
+    for (size_t r = 0; r < nr; r++) w.mapped += (w.flag[r] & 0x4) == 0;
+    lap(g_ns_align);
+}
 static void gpu_single(const Options &o, FeederCtx &fc, Work &w)
 {
     auto t_stage = std::chrono::steady_clock::now();
@@ -805,6 +863,7 @@ struct GroupBuf {
 };
 static void gpu_single_group(const Options &o, FeederCtx &fc, std::vector<Work *> &ws, GroupBuf &g)
 {
+    if (device_text_path(o)) { for (Work *w : ws) gpu_single_text(o, fc, *w); return; }
     const bool fusable = o.om < 0 && !o.ae && !single_records_path(o);
     if (ws.size() == 1 || !fusable) { for (Work *w : ws) gpu_single(o, fc, *w); return; }
     auto t_stage = std::chrono::steady_clock::now();
@@ -1589,7 +1648,7 @@ int main(int argc, char **argv)
         formatters.emplace_back([&] {
             Work *w;
             while (q_aligned.pop(w)) {
-                { StageTimer st(g_ns_format); if (o.paired) format_paired(contigs, *w); else format_single(contigs, *w); }
+                if (!w->text_done) { StageTimer st(g_ns_format); if (o.paired) format_paired(contigs, *w); else format_single(contigs, *w); }
                 if (o.bam) { std::string z; z.reserve(w->text.size() / 3 + 64); bgzf_append(z, w->text.data(), w->text.size()); w->text.swap(z); }
                 std::lock_guard<std::mutex> l(done_m); done[w->b.seq] = w; done_cv.notify_all();
             }

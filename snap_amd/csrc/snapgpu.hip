@@ -397,6 +397,7 @@ struct snapgpu_ctx {
     snapgpu_index_view view_meta{};
     std::vector<uint64_t> h_table_offset, h_table_size, h_contig_begin, h_proj_begin;
     std::vector<uint8_t> h_proj_rc; std::vector<uint32_t> h_cigar_start, h_cigar_ops;
+    uint8_t *d_contig_names = nullptr; uint32_t *d_contig_name_off = nullptr;      // snapgpu_set_contig_names: RNAME of the SAM-line kernels (sam_text.h)
     std::string err;
 };
 
@@ -551,6 +552,8 @@ extern "C" void snapgpu_destroy(snapgpu_ctx *ctx) {
     if (ctx->d_order) (void)hipFree(ctx->d_order);
     if (ctx->d_wbucket) (void)hipFree(ctx->d_wbucket);
     if (ctx->d_whist) (void)hipFree(ctx->d_whist);
+    if (ctx->d_contig_names) (void)hipFree(ctx->d_contig_names);
+    if (ctx->d_contig_name_off) (void)hipFree(ctx->d_contig_name_off);
     ctx->pool.free_all();
     if (ctx->d_work) (void)hipFree(ctx->d_work);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
@@ -2657,6 +2660,206 @@ extern "C" int snapgpu_align_sam_single_records_device(snapgpu_ctx *ctx, uint32_
     return sam_records_call(ctx, "snapgpu_align_sam_single_records_device", false, n, max_read_len, d_bases, d_quals, d_offsets, d_front_clip, d_data_len, d_skip,
                             use_m, adjust_primary, d_results, d_first_alt, d_secondary, secondary_stride, d_n_secondary, record_capacity, n_records,
                             d_rec_begin, d_rec_read, d_rec_kind, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_reference_history_dependent, stream);
+}
+
+// ---- records -> the bytes of their SAM lines (sam_text.h) ------------------------------------------------------------------------------------
+extern "C" int snapgpu_set_contig_names(snapgpu_ctx *ctx, uint32_t n_contigs, const char *const *names)
+{
+    if (!ctx || (n_contigs && !names)) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_set_contig_names: null argument");
+    if (n_contigs != ctx->ix.n_contigs)
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_set_contig_names: " + std::to_string(n_contigs) + " names for an index of " + std::to_string(ctx->ix.n_contigs) + " contigs");
+    std::vector<uint32_t> off((size_t)n_contigs + 1, 0);
+    std::string blob;
+    for (uint32_t i = 0; i < n_contigs; i++) {
+        if (!names[i]) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_set_contig_names: null name");
+        blob += names[i];
+        if (blob.size() > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_set_contig_names: the names are longer than 2 GB together");
+        off[(size_t)i + 1] = (uint32_t)blob.size();
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), SNAPGPU_E_LAUNCH);
+    if (ctx->d_contig_names) { (void)hipFree(ctx->d_contig_names); ctx->d_contig_names = nullptr; }
+    if (ctx->d_contig_name_off) { (void)hipFree(ctx->d_contig_name_off); ctx->d_contig_name_off = nullptr; }
+    void *d_blob = nullptr, *d_off = nullptr;
+    HIPCHK(ctx, hipMalloc(&d_blob, blob.size() + 16), SNAPGPU_E_NOMEM);
+    if (hipMalloc(&d_off, off.size() * 4) != hipSuccess) { (void)hipFree(d_blob); return fail(ctx, SNAPGPU_E_NOMEM, "snapgpu_set_contig_names: hipMalloc"); }
+    if ((blob.size() && hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d_blob); (void)hipFree(d_off);
+        return fail(ctx, SNAPGPU_E_LAUNCH, "snapgpu_set_contig_names: hipMemcpy");
+    }
+    ctx->d_contig_names = (uint8_t *)d_blob; ctx->d_contig_name_off = (uint32_t *)d_off;
+    return SNAPGPU_OK;
+}
+
+// What the three text calls share once every array is in HBM: the length pass, the scan, the write pass (sam_text.h), all on the call's
+// stream, and the summary read back -- the stream is synchronised when this returns.  n_records > 0.
+struct SamTextIO {
+    const void *bases, *quals, *offsets, *names, *name_off, *rec_read;
+    const void *flag, *contig, *pos, *mapq, *ops; uint32_t ops_stride; const void *n_ops, *nm;
+    uint64_t cap; void *text, *line_begin;
+};
+static int sam_text_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_records, uint32_t ops_stride)
+{
+    if (!ctx->d_contig_names) return fail(ctx, SNAPGPU_E_INVALID, w + ": no contig names (call snapgpu_set_contig_names first)");
+    if (ops_stride == 0) return fail(ctx, SNAPGPU_E_INVALID, w + ": ops_stride must not be 0");
+    if (n_records > 0xFFFFFFFFull - SAMREC_CHUNK) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^32 - 1 records in one call");
+    return SNAPGPU_OK;
+}
+static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, const SamTextIO &io, SamTextSummary *sum)
+{
+    SamTextArgs a; memset(&a, 0, sizeof(a));
+    a.n = (uint32_t)n_records; a.n_chunks = (uint32_t)((n_records + SAMREC_CHUNK - 1) / SAMREC_CHUNK); a.ops_stride = io.ops_stride; a.n_contigs = ctx->ix.n_contigs;
+    a.bases = (const uint8_t *)io.bases; a.quals = (const uint8_t *)io.quals; a.offsets = (const uint64_t *)io.offsets;
+    a.names = (const uint8_t *)io.names; a.name_off = (const uint64_t *)io.name_off; a.rec_read = (const uint32_t *)io.rec_read;
+    a.flag = (const int32_t *)io.flag; a.contig = (const int32_t *)io.contig; a.pos = (const int64_t *)io.pos; a.mapq = (const int32_t *)io.mapq;
+    a.ops = (const uint32_t *)io.ops; a.n_ops = (const int32_t *)io.n_ops; a.nm = (const int32_t *)io.nm;
+    a.contig_names = ctx->d_contig_names; a.contig_name_off = ctx->d_contig_name_off;
+    a.cap = io.cap; a.text = (uint8_t *)io.text; a.line_begin = (uint64_t *)io.line_begin;
+    a.len = st.scratch((size_t)a.n * 4 + 4); a.partial = st.scratch((size_t)a.n_chunks * 8); a.summary = st.scratch(sizeof(SamTextSummary));
+    if (st.rc) return st.rc;
+    uint32_t scan_blocks = (uint32_t)ctx->num_cus * 8, write_blocks = scan_blocks;
+    { const uint32_t need = (a.n_chunks + 3) / 4; if (scan_blocks > need) scan_blocks = need; }
+    { const uint32_t need = (a.n + 3) / 4; if (write_blocks > need) write_blocks = need; }
+    HIPCHK(ctx, hipMemsetAsync(a.summary, 0, sizeof(SamTextSummary), st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
+    snapgpu_launch_sam_text(&a, scan_blocks, write_blocks, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemcpyAsync(sum, a.summary, sizeof(SamTextSummary), hipMemcpyDeviceToHost, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    int rc = finish_timing(ctx);
+    if (rc) return rc;
+    if (sum->flags & SAMTEXT_BAD_RECORD) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record has more cigar operations than ops_stride, or a contig the index does not have");
+    return SNAPGPU_OK;
+}
+// no records: line_begin[0] = 0 and no text (the device form writes the word in HBM)
+static int sam_text_empty(snapgpu_ctx *ctx, bool host, void *line_begin, uint64_t *text_bytes, void *stream)
+{
+    *text_bytes = 0;
+    if (host) { *(uint64_t *)line_begin = 0; return SNAPGPU_OK; }
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    HIPCHK(ctx, hipMemsetAsync(line_begin, 0, 8, s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipStreamSynchronize(s), SNAPGPU_E_LAUNCH);
+    return SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_sam_text_single_device(snapgpu_ctx *ctx, uint64_t n_records, const void *d_bases, const void *d_quals, const void *d_offsets,
+                                              const void *d_names, const void *d_name_off, const void *d_rec_read, const void *d_flag, const void *d_contig,
+                                              const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                              uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
+{
+    const std::string w = "snapgpu_sam_text_single_device";
+    if (!ctx || !text_bytes || !d_line_begin || (text_capacity && !d_text) ||
+        (n_records && (!d_bases || !d_quals || !d_offsets || !d_names || !d_name_off || !d_flag || !d_contig || !d_pos || !d_mapq || !d_ops || !d_n_ops || !d_nm)))
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    int rc = sam_text_check(ctx, w, n_records, ops_stride);
+    if (rc) return rc;
+    if (n_records == 0) return sam_text_empty(ctx, false, d_line_begin, text_bytes, stream);
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
+                       text_capacity, d_text, d_line_begin};
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = sam_text_core(ctx, w, st, n_records, io, &sum))) return rc;
+    *text_bytes = sum.total;
+    return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_sam_text_single(snapgpu_ctx *ctx, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
+                                       const char *names, const uint64_t *name_off, const uint32_t *rec_read, const int32_t *flag, const int32_t *contig,
+                                       const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                                       uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    const std::string w = "snapgpu_sam_text_single";
+    if (!ctx || !text_bytes || !line_begin || (text_capacity && !text) ||
+        (n_records && (!bases || !quals || !offsets || !names || !name_off || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm)))
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    int rc = sam_text_check(ctx, w, n_records, ops_stride);
+    if (rc) return rc;
+    if (n_records == 0) return sam_text_empty(ctx, true, line_begin, text_bytes, nullptr);
+    if (!rec_read && n_records != n_reads) return fail(ctx, SNAPGPU_E_INVALID, w + ": without rec_read there is one record per read (n_records == n_reads)");
+    for (uint32_t i = 0; i < n_reads; i++)
+        if (offsets[i + 1] < offsets[i] || name_off[i + 1] < name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": offsets and name_off must be non-decreasing");
+    for (uint64_t r = 0; rec_read && r < n_records; r++)
+        if (rec_read[r] >= n_reads) return fail(ctx, SNAPGPU_E_INVALID, w + ": rec_read names a read the batch does not have");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, ctx->stream);
+    const size_t nb = (size_t)offsets[n_reads], r4 = (size_t)n_records * 4;
+    SamTextIO io;
+    io.bases = st.in(bases, nb); io.quals = st.in(quals, nb); io.offsets = st.in(offsets, ((size_t)n_reads + 1) * 8);
+    io.names = st.in(names, (size_t)name_off[n_reads]); io.name_off = st.in(name_off, ((size_t)n_reads + 1) * 8);
+    io.rec_read = rec_read ? (const void *)st.in(rec_read, r4) : nullptr;
+    io.flag = st.in(flag, r4); io.contig = st.in(contig, r4); io.pos = st.in(pos, (size_t)n_records * 8); io.mapq = st.in(mapq, r4);
+    io.ops = st.in(ops, r4 * ops_stride); io.ops_stride = ops_stride; io.n_ops = st.in(n_ops, r4); io.nm = st.in(nm, r4);
+    io.cap = text_capacity; io.text = st.out(text, (size_t)text_capacity); io.line_begin = st.out(line_begin, ((size_t)n_records + 1) * 8);
+    if (st.rc) return st.rc;
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = sam_text_core(ctx, w, st, n_records, io, &sum))) return rc;
+    st.limit(io.text, (size_t)sum.written);                              // only the lines that were written come down
+    if ((rc = st.download())) return rc;
+    *text_bytes = sum.total;
+    return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_align_sam_single_text(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                             uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    const char *who = "snapgpu_align_sam_single_text";
+    const std::string w(who);
+    if (!ctx || !n_records || !rec_begin || !line_begin || !text_bytes || (text_capacity && !text) || (record_capacity && !flag) ||
+        (n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off)))
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    int rc = sam_text_check(ctx, w, record_capacity, ops_stride);
+    if (rc) return rc;
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, w + ": ops_stride must be at least 3");
+    if (ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, w + ": a single-end context is needed (no snapgpu_enable_paired)");
+    *n_records = 0; *rec_begin = 0; *line_begin = 0; *text_bytes = 0;
+    if (n == 0) return SNAPGPU_OK;
+    uint32_t RL = 64;
+    if ((rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
+        if (!skip[i] && (uint32_t)data_len[i] > ctx->params.max_read_len)
+            return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (BaseAligner.cpp:354-358)");
+        return (int)SNAPGPU_OK;
+    }))) return rc;
+    for (uint32_t i = 0; i < n; i++) if (name_off[i + 1] < name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": name_off must be non-decreasing");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    // ---- one upload: the batch and its names; the record arrays are the library's own
+    Stage st(ctx, ctx->stream);
+    const size_t n4 = (size_t)n * 4, c4 = (size_t)record_capacity * 4;
+    const void *d_bases = bases, *d_quals = quals, *d_offsets = offsets;
+    stage_reads(st, d_bases, d_quals, d_offsets, n);
+    const void *d_fc = st.in(front_clip, n4), *d_dl = st.in(data_len, n4), *d_skip = st.in(skip, n);
+    const void *d_names = st.in(names, (size_t)name_off[n]), *d_name_off = st.in(name_off, ((size_t)n + 1) * 8);
+    void *d_rec_begin = st.out(rec_begin, ((size_t)n + 1) * 8), *d_rec_read = st.scratch(c4), *d_rec_kind = st.scratch((size_t)record_capacity);
+    void *d_flag = st.out(flag, c4), *d_contig = st.scratch(c4), *d_pos = st.scratch((size_t)record_capacity * 8), *d_mapq = st.scratch(c4);
+    void *d_ops = st.scratch(c4 * ops_stride), *d_n_ops = st.scratch(c4), *d_nm = st.scratch(c4), *d_stale = st.scratch(c4);
+    void *d_text = st.out(text, (size_t)text_capacity), *d_line_begin = st.out(line_begin, ((size_t)record_capacity + 1) * 8);
+    if (st.rc) return st.rc;
+    // ---- the records, where snapgpu_align_sam_single_records_device leaves them (RL: the longest unclipped read, as check_sam_reads found it)
+    uint64_t total = 0;
+    rc = sam_records_call(ctx, who, false, n, RL, d_bases, d_quals, d_offsets, d_fc, d_dl, d_skip, use_m, adjust_primary, nullptr, nullptr, nullptr, 0, nullptr,
+                          record_capacity, &total, d_rec_begin, d_rec_read, d_rec_kind, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_stale, st.s);
+    if (rc != SNAPGPU_OK && rc != SNAPGPU_W_RECORDS_TRUNCATED) return rc;
+    const bool rec_truncated = rc == SNAPGPU_W_RECORDS_TRUNCATED;
+    const uint64_t f = total < record_capacity ? total : record_capacity;                            // the records that were formatted
+    // ---- their lines
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if (f) {
+        const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
+                           text_capacity, d_text, d_line_begin};
+        if ((rc = sam_text_core(ctx, w, st, f, io, &sum))) return rc;
+        if (sum.flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
+    } else HIPCHK(ctx, hipMemsetAsync(d_line_begin, 0, 8, st.s), SNAPGPU_E_LAUNCH);
+    // ---- one download: rec_begin, the flags and line offsets of the formatted records, the lines that were written
+    st.limit(d_flag, (size_t)f * 4); st.limit(d_line_begin, ((size_t)f + 1) * 8); st.limit(d_text, (size_t)sum.written);
+    if ((rc = st.download())) return rc;
+    *n_records = total; *text_bytes = sum.total;
+    return rec_truncated ? SNAPGPU_W_RECORDS_TRUNCATED : (sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK);
 }
 
 // paired-end writer: results -> the computed fields of both SAM records of each pair (sam_fields.h, cigar_k.hip); host / max_read_len / stream as
