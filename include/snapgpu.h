@@ -33,6 +33,9 @@
  *       AlignRead with secondary results, finalizeSecondaryResults, writeReads per result  SNAPLib/SingleAligner.cpp:250-325, BaseAligner.cpp:2423-2553
  *   snapgpu_sam_text_single / _device, snapgpu_align_sam_single_text
  *       SAMFormat::createSAMLine / writeRead, the printed line of a single-end record  SNAPLib/SAM.cpp:1424-1572 / 1898-2352
+ *   snapgpu_sam_text_paired / _device, snapgpu_align_sam_paired_text
+ *       SAMFormat::writePairs, the printed lines of a pair's result  SNAPLib/SAM.cpp:1575-1895 (snprintf :1854-1875, QS :1826-1834); the
+ *       "/1" "/2" rule and the print order of SimpleReadWriter::writePairs  SNAPLib/ReadWriter.cpp:405-420 / 453-461
  *   snapgpu_sam_fields_single
  *       SimpleReadWriter::writeReads            SNAPLib/ReadWriter.cpp:170-330
  *       SAMFormat::writeRead / createSAMLine / computeCigarString  SNAPLib/SAM.cpp:1898-2352 / 1424-1572 / 2595-2766
@@ -638,6 +641,67 @@ int  snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *ba
                               int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
                               int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
                               int32_t *reference_history_dependent);
+
+/*
+ * Pair units to the bytes of their SAM lines, on the device: the last step of the paired-end SAM side.  A pair unit is one
+ * PairedAlignmentResult of a pair; for each unit the TWO lines that SAMFormat::writePairs prints into a SAM (not BAM) file
+ * (SNAPLib/SAM.cpp:1575-1895, its snprintf at :1854-1875), byte for byte, in the order SimpleReadWriter::writePairs prints them
+ * (ReadWriter.cpp:453-461: mate first_written first):
+ *   QNAME \t FLAG \t RNAME \t POS \t MAPQ \t CIGAR \t RNEXT \t PNEXT \t TLEN \t SEQ \t QUAL \t PG:Z:SNAP \t NM:i:<nm> \t RG:Z:FASTQ \t PL:Z:Illumina \t PU:Z:pu \t LB:Z:lb \t SM:Z:sm \t QS:i:<qs> \n
+ * QNAME: when both names of the pair have the same length L > 2, "/" at L - 2 and last bytes that are "1" and "2" either way round, two
+ * bytes come off BOTH (ReadWriter.cpp:405-420); the name is then cut at its first space.  RNEXT "=" for rnext -2, "*" for -1, else the
+ * contig's name; PNEXT a 64-bit decimal; TLEN the 64-bit value cast to int32; QS the sum over the MATE's whole quality string, bytes
+ * unsigned, of b - 33 wherever b - 33 >= 15 (SAM.cpp:1826-1834).  The other fields as snapgpu_sam_text_single_device prints them.
+ * This is the pure formatter, every array in HBM.  Reads 2 k and 2 k + 1 (d_bases, d_quals, d_offsets, d_names, d_name_off) are the mates
+ * of pair k; unit u belongs to pair d_unit_pair[u] (uint32[n_units]; NULL: unit u is pair u, the layout snapgpu_align_sam_paired and
+ * snapgpu_sam_fields_paired leave).  d_flag .. d_nm, d_rnext, d_pnext, d_tlen: per mate of a unit, [2 * n_units], mate v of unit u at
+ * 2 u + v; d_first_written [n_units].  Line j is d_text[line_begin[j] .. line_begin[j + 1]): lines 2 u and 2 u + 1 are unit u's.
+ *   d_line_begin    out, uint64[2 * n_units + 1]
+ * text_capacity, d_text, text_bytes, the return values (SNAPGPU_W_TEXT_TRUNCATED: line_begin complete, the lines wholly below the capacity
+ * written as a large enough call writes them, nothing at or beyond it touched) and `stream` exactly as snapgpu_sam_text_single_device.
+ * SNAPGPU_E_INVALID for a record with n_ops > ops_stride, a contig or an rnext the index does not have (rnext < -2 too), a first_written
+ * outside {0, 1}, and for a context without contig names.  n_units == 0 writes d_line_begin[0] = 0 and *text_bytes = 0.
+ */
+int  snapgpu_sam_text_paired_device(snapgpu_ctx *ctx, uint64_t n_units,
+                                    const void *d_bases, const void *d_quals, const void *d_offsets,
+                                    const void *d_names, const void *d_name_off,
+                                    const void *d_unit_pair,
+                                    const void *d_flag, const void *d_contig, const void *d_pos, const void *d_mapq,
+                                    const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                    const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
+                                    uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream);
+
+/* Host-pointer form of snapgpu_sam_text_paired_device (SAMFormat::writePairs, SAM.cpp:1575-1895; ReadWriter.cpp:405-420, 453-461): n_pairs
+ * sizes the uploads of the 2 * n_pairs mates and their names; one upload, and the lines that were written and line_begin come down.
+ * Checked on the host (SNAPGPU_E_INVALID): offsets and name_off non-decreasing, unit_pair[u] < n_pairs, n_units == n_pairs when unit_pair
+ * is NULL. */
+int  snapgpu_sam_text_paired(snapgpu_ctx *ctx, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                             const char *names, const uint64_t *name_off, const uint32_t *unit_pair,
+                             const int32_t *flag, const int32_t *contig, const int64_t *pos, const int32_t *mapq,
+                             const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                             const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
+                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes);
+
+/*
+ * Paired-end reads to the TEXT of their SAM records in ONE call: snapgpu_align_sam_paired on device arrays of the library's own, followed
+ * by the lines of its pairs (SAMFormat::writePairs, SAM.cpp:1575-1895; ReadWriter.cpp:405-420, 453-461) -- one upload, the batch as for
+ * that call plus the mates' names, and one download.  One result per pair (unit u is pair u).  Host pointers.
+ *   ctx, n_pairs .. use_m      as snapgpu_align_sam_paired
+ *   names, name_off            the 2 * n_pairs mates' names: a blob and uint64[2 * n_pairs + 1] offsets
+ *   ops_stride                 room per record for its cigar operations, in the library's own array (at least 3)
+ *   results / first_alt        [n_pairs] out, each may be NULL, as snapgpu_align_sam_paired
+ *   flag [2 * n_pairs], first_written [n_pairs]   out: a caller counts its mapped records from the one and orders the lines by the other
+ *   text_capacity, text, text_bytes               as snapgpu_sam_text_paired;  line_begin [2 * n_pairs + 1] out
+ * Returns SNAPGPU_OK or SNAPGPU_W_TEXT_TRUNCATED.  The context requirements, the max_read_len check and the pool-overflow report
+ * (SNAPGPU_E_UNSUPPORTED, outputs written) are snapgpu_align_sam_paired's; contig names are needed as well.  A record whose cigar does
+ * not fit ops_stride (nm -2) would print a wrong line: the call fails with SNAPGPU_E_INVALID and a message that names ops_stride, and the
+ * caller calls again with a larger one.
+ */
+int  snapgpu_align_sam_paired_text(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                   const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                   const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                   snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                   uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes);
 
 /*
  * Batched AffineGapVectorized<dir>::computeScore (banded[i] == 0) / computeScoreBanded

@@ -53,7 +53,7 @@ EXPORTED_SYMBOLS = [
     "snapgpu_align_single_device", "snapgpu_get_counters", "snapgpu_kernel_time",
     "snapgpu_enable_secondary", "snapgpu_align_single_secondary", "snapgpu_align_single_secondary_device",
     "snapgpu_align_paired_secondary", "snapgpu_align_paired_secondary_device",
-    "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_single_records", "snapgpu_align_sam_single_records_device", "snapgpu_set_contig_names", "snapgpu_sam_text_single", "snapgpu_sam_text_single_device", "snapgpu_align_sam_single_text", "snapgpu_align_sam_paired", "snapgpu_create_replica_with_params",
+    "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_single_records", "snapgpu_align_sam_single_records_device", "snapgpu_set_contig_names", "snapgpu_sam_text_single", "snapgpu_sam_text_single_device", "snapgpu_align_sam_single_text", "snapgpu_align_sam_paired", "snapgpu_sam_text_paired", "snapgpu_sam_text_paired_device", "snapgpu_align_sam_paired_text","snapgpu_create_replica_with_params",
     "snapgpu_default_index_build_params", "snapgpu_index_build", "snapgpu_index_build_from_fasta", "snapgpu_index_build_shaped",
     "snapgpu_index_build_from_fasta_shaped", "snapgpu_built_index_view",
     "snapgpu_built_index_save", "snapgpu_built_index_stats", "snapgpu_built_index_destroy",
@@ -729,6 +729,98 @@ class ChimericPairedEndAligner(BaseAligner):
             ptr(rnext), ptr(pnext), ptr(tlen), ptr(first), ptr(stale)), "snapgpu_align_sam_paired")
         return results, first_alt, dict(flag=flag, contig=contig, pos=pos, mapq=mapq, ops=ops, n_ops=n_ops, nm=nm, rnext=rnext, pnext=pnext,
                                         tlen=tlen, first_written=first, stale=stale)
+
+    # ---- pair units -> the bytes of their SAM lines (SAMFormat::writePairs' printed lines) ----
+    def samTextPaired(self, bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rnext, pnext, tlen, first_written,
+                      unit_pair=None, capacity: int | None = None, grow: bool = True, text=None):
+        """The SAM lines of a batch's pair units (snapgpu_sam_text_paired): bases / quals / offsets (2 n_pairs + 1 entries) the unclipped
+        mates, names / name_off (uint64[2 n_pairs + 1]) their names, flag .. tlen the fields of both mates of every unit as samFieldsPaired /
+        alignSamPaired return them ([2 n_units]; ops: [2 n_units, ops_stride]), first_written [n_units]; unit_pair: the pair of each unit
+        (None: unit i is pair i).  capacity / grow / text: as samText.  Returns dict(text uint8[capacity], line_begin uint64[2 n_units + 1],
+        text_bytes, truncated); lines 2 u and 2 u + 1 are unit u's, in the order they are printed."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1); quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        names = np.ascontiguousarray(names, dtype=np.uint8).reshape(-1); name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        flag = np.ascontiguousarray(flag, dtype=np.int32); contig = np.ascontiguousarray(contig, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int64); mapq = np.ascontiguousarray(mapq, dtype=np.int32)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32); n_ops = np.ascontiguousarray(n_ops, dtype=np.int32); nm = np.ascontiguousarray(nm, dtype=np.int32)
+        rnext = np.ascontiguousarray(rnext, dtype=np.int32); pnext = np.ascontiguousarray(pnext, dtype=np.int64); tlen = np.ascontiguousarray(tlen, dtype=np.int64)
+        first_written = np.ascontiguousarray(first_written, dtype=np.int32)
+        n_units = first_written.size
+        if flag.size != 2 * n_units or (offsets.size - 1) % 2:
+            raise ValueError("two records per unit and two mates per pair are needed")
+        ops_stride = ops.shape[1] if ops.ndim == 2 else (ops.size // flag.size if flag.size else 1)
+        if unit_pair is not None:
+            unit_pair = np.ascontiguousarray(unit_pair, dtype=np.uint32)
+        n_pairs = (offsets.size - 1) // 2
+        cap = text.size if text is not None else (int(capacity) if capacity is not None else 4 * int(bases.size) + 600 * n_units + 64)
+        line_begin = np.zeros(2 * n_units + 1, np.uint64)
+        f = self.lib.snapgpu_sam_text_paired
+        f.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 3
+        while True:
+            if text is None or text.size != cap:
+                text = np.zeros(cap, np.uint8)
+            tb = C.c_uint64(0)
+            rc = f(self.handle, n_units, n_pairs, ptr(bases), ptr(quals), ptr(offsets), ptr(names), ptr(name_off), ptr(unit_pair) if unit_pair is not None else None,
+                   ptr(flag), ptr(contig), ptr(pos), ptr(mapq), ptr(ops), ops_stride, ptr(n_ops), ptr(nm), ptr(rnext), ptr(pnext), ptr(tlen), ptr(first_written),
+                   cap, ptr(text), ptr(line_begin), C.addressof(tb))
+            if rc == W_TEXT_TRUNCATED and grow:
+                cap = int(tb.value)
+                continue
+            if rc != W_TEXT_TRUNCATED:
+                self._check(rc, "snapgpu_sam_text_paired")
+            return dict(text=text, line_begin=line_begin, text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED)
+
+    def samTextPaired_device(self, n_units: int, d_bases: int, d_quals: int, d_offsets: int, d_names: int, d_name_off: int, d_unit_pair: int, d_flag: int,
+                             d_contig: int, d_pos: int, d_mapq: int, d_ops: int, ops_stride: int, d_n_ops: int, d_nm: int, d_rnext: int, d_pnext: int,
+                             d_tlen: int, d_first_written: int, capacity: int, d_text: int, d_line_begin: int, stream: int = 0):
+        """Device-pointer form of samTextPaired (snapgpu_sam_text_paired_device): every array in HBM (d_unit_pair 0: unit i is pair i), the
+        text and line_begin left there.  Synchronous on `stream` (0: the context's).  Returns (text_bytes, truncated)."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        f = self.lib.snapgpu_sam_text_paired_device
+        f.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11 + [C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 4
+        tb = C.c_uint64(0)
+        rc = f(self.handle, n_units, vp(d_bases), vp(d_quals), vp(d_offsets), vp(d_names), vp(d_name_off), vp(d_unit_pair), vp(d_flag), vp(d_contig), vp(d_pos),
+               vp(d_mapq), vp(d_ops), ops_stride, vp(d_n_ops), vp(d_nm), vp(d_rnext), vp(d_pnext), vp(d_tlen), vp(d_first_written), capacity, vp(d_text),
+               vp(d_line_begin), C.addressof(tb), vp(stream))
+        if rc != W_TEXT_TRUNCATED:
+            self._check(rc, "snapgpu_sam_text_paired_device")
+        return int(tb.value), rc == W_TEXT_TRUNCATED
+
+    def alignSamTextPaired(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
+                           text_capacity: int | None = None, grow: bool = True, want_results: bool = False):
+        """Paired-end reads to the text of their SAM records in one call (snapgpu_align_sam_paired_text): alignSamPaired's inputs plus the
+        mates' names; text_capacity: bytes to make room for (default: an estimate); grow: call again with what the library asks for when
+        that was too few.  Returns dict(text, line_begin uint64[2 n_pairs + 1], text_bytes, truncated, flag [2 n_pairs], first_written
+        [n_pairs], results, first_alt); the last two None unless want_results."""
+        from .abi import PAIRED_RESULT_DTYPE
+        bases = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1); quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        front_clip = np.ascontiguousarray(front_clip, dtype=np.int32); data_len = np.ascontiguousarray(data_len, dtype=np.int32)
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        names = np.ascontiguousarray(names, dtype=np.uint8).reshape(-1); name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        if (offsets.size - 1) % 2:
+            raise ValueError("offsets must have 2*n_pairs + 1 entries")
+        n = offsets.size - 1; npairs = n // 2
+        tcap = int(text_capacity) if text_capacity is not None else 3 * int(bases.size) + 300 * n + 64
+        results = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
+        first_alt = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
+        f = self.lib.snapgpu_align_sam_paired_text
+        f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 3
+        while True:
+            flag = np.zeros(n, np.int32); first = np.zeros(npairs, np.int32); line_begin = np.zeros(n + 1, np.uint64); text = np.zeros(tcap, np.uint8)
+            tb = C.c_uint64(0)
+            rc = f(self.handle, npairs, ptr(bases), ptr(quals), ptr(offsets), ptr(front_clip), ptr(data_len), ptr(skip), 1 if use_m else 0, ptr(names), ptr(name_off),
+                   ops_stride, ptr(results) if want_results else None, ptr(first_alt) if want_results else None, ptr(flag), ptr(first), tcap, ptr(text),
+                   ptr(line_begin), C.addressof(tb))
+            if rc == W_TEXT_TRUNCATED and grow:
+                tcap = int(tb.value)
+                continue
+            if rc != W_TEXT_TRUNCATED:
+                self._check(rc, "snapgpu_align_sam_paired_text")
+            break
+        return dict(text=text, line_begin=line_begin, text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED, flag=flag, first_written=first,
+                    results=results, first_alt=first_alt)
 
     def align_secondary(self, bases: np.ndarray, quals: np.ndarray, offsets: np.ndarray, stride: int = 8, single_stride: int = 16):
         """ChimericPairedEndAligner::align with secondary results (after enable_secondary(...)): returns

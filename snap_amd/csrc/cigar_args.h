@@ -104,6 +104,7 @@ struct SamRecArgs {
 // snapgpu_sam_text_single*: records -> the bytes of their SAM lines (sam_text.h).  Record r belongs to read rec_read[r] (NULL: read r).
 #define SAMTEXT_NM_OVERFLOW 1u      // a record whose cigar did not fit ops_stride (nm == -2: sam_fields.h)
 #define SAMTEXT_BAD_RECORD 2u       // n_ops > ops_stride or a contig the index does not have: printed as "*", the call is refused
+                                    // (pair lines: also rnext < -2 or not a contig, first_written outside {0, 1})
 struct SamTextSummary {
     unsigned long long total;         // bytes the lines of the batch need
     unsigned long long written;       // end of the last line that lies wholly below the capacity
@@ -122,6 +123,15 @@ struct SamTextArgs {
     SamTextSummary *summary;
 };
 extern "C" void snapgpu_launch_sam_text(const SamTextArgs *a, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s);
+// snapgpu_sam_text_paired*: the two lines of each pair unit (one PairedAlignmentResult of a pair).  Line j of a call is position j & 1 of unit
+// u = j >> 1: mate v = first_written[u] first, then the other; its fields are at 2 u + v, its read is 2 k + v of pair k = rec_read[u] (here
+// the unit's pair; NULL: unit u is pair u).  n is the number of LINES, 2 * n_units, so the scan kernels run over it as they are.
+struct SamTextPairedArgs : SamTextArgs {
+    const int32_t *rnext; const int64_t *pnext; const int64_t *tlen;             // [n]
+    const int32_t *first_written;                                                // [n / 2]
+    int32_t *qs;                                                                 // [n] k_samtext_qs: qs[2 u + v] = QS of mate v of unit u's pair, which the OTHER mate's line prints
+};
+extern "C" void snapgpu_launch_sam_text_paired(const SamTextPairedArgs *a, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_count(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_list(const SamRecArgs *a, uint32_t blocks, hipStream_t s);

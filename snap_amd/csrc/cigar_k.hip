@@ -533,3 +533,13 @@ extern "C" void snapgpu_launch_sam_text(const SamTextArgs *a, uint32_t scan_bloc
     hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, *a);
     hipLaunchKernelGGL(k_samtext_write, dim3(write_blocks), dim3(256), 0, s, *a);
 }
+// the two lines of each pair unit: QS of every mate first (a line's length has its digits), then the same passes; the scan kernels as they are
+extern "C" void snapgpu_launch_sam_text_paired(const SamTextPairedArgs *a, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s)
+{
+    const SamTextArgs &base = *a;
+    hipLaunchKernelGGL(k_samtext_qs, dim3(write_blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samtext_pair_len, dim3(scan_blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samtext_partials, dim3(1), dim3(64), 0, s, base);
+    hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, base);
+    hipLaunchKernelGGL(k_samtext_pair_write, dim3(write_blocks), dim3(256), 0, s, *a);
+}

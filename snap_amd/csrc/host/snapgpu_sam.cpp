@@ -572,11 +572,19 @@ static bool single_records_path(const Options &o)
 }
 // SNAPGPU_SAM_DEVICE_TEXT=1: `single` with SAM output takes the LINES of a batch from the device (snapgpu_align_sam_single_text, every option
 // set) and the formatter threads pass the batch through.  Off unless asked for: DESIGN.md section 13 has what to measure before that changes.
-// BAM output and `paired` do not have the path and ignore the switch.  The file is the same bytes either way (tests/test_zz_gpu_sam_text.py).
+// BAM output does not have the path and ignores the switch.  The file is the same bytes either way (tests/test_zz_gpu_sam_text.py).
 static bool device_text_path(const Options &o)
 {
     static const bool on = getenv("SNAPGPU_SAM_DEVICE_TEXT") && atoi(getenv("SNAPGPU_SAM_DEVICE_TEXT")) != 0;
     return on && !o.paired && !o.bam;
+}
+// The same switch for `paired` with SAM output: the batches of the one-call path (no -om) take their lines from snapgpu_align_sam_paired_text;
+// a batch in which -ea finds a first-ALT pair goes through the host path as it does without the switch.  -om ignores the switch.  Same file
+// (tests/test_zz_gpu_sam_text_paired.py).
+static bool device_text_paired_path(const Options &o)
+{
+    static const bool on = getenv("SNAPGPU_SAM_DEVICE_TEXT") && atoi(getenv("SNAPGPU_SAM_DEVICE_TEXT")) != 0;
+    return on && o.paired && !o.bam && o.om < 0;
 }
 static std::atomic<uint32_t> g_text_extra_per_record(128);      // text capacity of the next call: bytes per record beyond its name, SEQ and QUAL; grows to what batches have needed
 static std::atomic<uint32_t> g_records_per_read_x16(24);        // record capacity of the next call, in sixteenths of a record per read: grows to what batches have needed
@@ -939,23 +947,58 @@ static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
         std::vector<snapgpu_paired_result> fres, falt;
         if (want_alt) { fres.resize(np); falt.resize(np); }
         const size_t nrec = 2 * np;
-        w.emit.clear(); w.pu_pair.resize(np); w.pu_secondary.assign(np, 0); w.su_read.clear();
-        for (size_t k = 0; k < np; k++) { w.emit.push_back(Work::Emit{(uint32_t)k, 0}); w.pu_pair[k] = (uint32_t)k; }
-        w.flag.assign(nrec, 0); w.contig.assign(nrec, 0); w.mapq.assign(nrec, 0); w.n_ops.assign(nrec, 0); w.nm.assign(nrec, 0); w.rnext.assign(nrec, 0);
-        w.first_written.assign(np, 0); w.pos.assign(nrec, 0); w.pnext.assign(nrec, 0); w.tlen.assign(nrec, 0);
-        w.s_flag.clear(); w.s_contig.clear(); w.s_mapq.clear(); w.s_n_ops.clear(); w.s_nm.clear(); w.s_pos.clear();
-        w.ops_stride = w.s_ops_stride = o.ops_stride;
-        std::vector<int32_t> stale(nrec);
-        with_growing_stride(w, nrec, [&] {
-            int rc = snapgpu_align_sam_paired(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(), skip.data(),
-                                              o.use_m ? 1 : 0, want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL,
-                                              w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(), w.ops.data(), w.ops_stride, w.n_ops.data(),
-                                              w.nm.data(), w.rnext.data(), w.pnext.data(), w.tlen.data(), w.first_written.data(), stale.data());
-            if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_paired", rc);
-        });
-        bool any_alt = false;
-        if (want_alt) for (size_t k = 0; k < np && !any_alt; k++) any_alt = !skip[k] && (falt[k].status[0] != SNAPGPU_NotFound || falt[k].status[1] != SNAPGPU_NotFound);
-        if (!any_alt) return;                                           // (rare: a first-ALT pair to write -- the batch goes through the calls below)
+        auto first_alt_pair = [&] {
+            if (want_alt) for (size_t k = 0; k < np; k++) if (!skip[k] && (falt[k].status[0] != SNAPGPU_NotFound || falt[k].status[1] != SNAPGPU_NotFound)) return true;
+            return false;
+        };
+        // SNAPGPU_SAM_DEVICE_TEXT: the batch goes up as it was parsed, with its names, and the lines of its pairs come down (as gpu_single_text: the
+        // capacity follows what the library reports, a cigar that outgrows its row is met with a larger row)
+        if (device_text_paired_path(o)) {
+            std::vector<uint64_t> name_off(b.name_off.begin(), b.name_off.end()), line_begin(nrec + 1);
+            const size_t per_read = (2 * b.bases.size() + b.names.size() + nrec - 1) / nrec;       // name, SEQ and QUAL of the average record
+            size_t tcap = nrec * (per_read + g_text_extra_per_record.load());
+            uint32_t ops_stride = o.ops_stride;
+            uint64_t text_bytes = 0;
+            w.flag.assign(nrec, 0); w.first_written.assign(np, 0);
+            for (;;) {
+                w.text.resize(tcap);
+                const int rc = snapgpu_align_sam_paired_text(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
+                                                             skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
+                                                             want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
+                                                             (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
+                if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; continue; }
+                if (rc == SNAPGPU_E_INVALID && strstr(snapgpu_last_error(ctx), "ops_stride")) {
+                    if (ops_stride >= 4096) die("a cigar needs more than 4096 operations");
+                    ops_stride *= 4; continue;
+                }
+                if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_paired_text", rc);
+                break;
+            }
+            if (!first_alt_pair()) {
+                { const size_t per_rec = ((size_t)text_bytes + nrec - 1) / nrec; const uint32_t need = per_rec > per_read ? (uint32_t)(per_rec - per_read) + 16 : 16;
+                  uint32_t cur = g_text_extra_per_record.load(); while (need > cur && !g_text_extra_per_record.compare_exchange_weak(cur, need)) {} }
+                w.text.resize((size_t)text_bytes); w.text_done = true; w.mapped = 0;
+                for (size_t r = 0; r < nrec; r++) w.mapped += (w.flag[r] & 0x4) == 0;
+                return;
+            }
+            w.text.clear();                                             // (rare: a first-ALT pair to write -- the batch goes through the calls below)
+        } else {
+            w.emit.clear(); w.pu_pair.resize(np); w.pu_secondary.assign(np, 0); w.su_read.clear();
+            for (size_t k = 0; k < np; k++) { w.emit.push_back(Work::Emit{(uint32_t)k, 0}); w.pu_pair[k] = (uint32_t)k; }
+            w.flag.assign(nrec, 0); w.contig.assign(nrec, 0); w.mapq.assign(nrec, 0); w.n_ops.assign(nrec, 0); w.nm.assign(nrec, 0); w.rnext.assign(nrec, 0);
+            w.first_written.assign(np, 0); w.pos.assign(nrec, 0); w.pnext.assign(nrec, 0); w.tlen.assign(nrec, 0);
+            w.s_flag.clear(); w.s_contig.clear(); w.s_mapq.clear(); w.s_n_ops.clear(); w.s_nm.clear(); w.s_pos.clear();
+            w.ops_stride = w.s_ops_stride = o.ops_stride;
+            std::vector<int32_t> stale(nrec);
+            with_growing_stride(w, nrec, [&] {
+                int rc = snapgpu_align_sam_paired(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(), skip.data(),
+                                                  o.use_m ? 1 : 0, want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL,
+                                                  w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(), w.ops.data(), w.ops_stride, w.n_ops.data(),
+                                                  w.nm.data(), w.rnext.data(), w.pnext.data(), w.tlen.data(), w.first_written.data(), stale.data());
+                if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_paired", rc);
+            });
+            if (!first_alt_pair()) return;                                         // (rare: a first-ALT pair to write -- the batch goes through the calls below)
+        }
     }
     std::vector<uint32_t> to_align;                                     // pairs with at least one useful mate (PairedAligner.cpp:680-682)
     std::vector<char> ab, aq; std::vector<uint64_t> ao(1, 0);

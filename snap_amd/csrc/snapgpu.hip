@@ -2706,9 +2706,11 @@ static int sam_text_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_rec
     if (n_records > 0xFFFFFFFFull - SAMREC_CHUNK) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^32 - 1 records in one call");
     return SNAPGPU_OK;
 }
-static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, const SamTextIO &io, SamTextSummary *sum)
+// the arrays only pair lines have (snapgpu_sam_text_paired*): with them n_records counts LINES, two per pair unit, and io.rec_read is unit_pair
+struct SamTextPairIO { const void *rnext, *pnext, *tlen, *first_written; };
+static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, const SamTextIO &io, SamTextSummary *sum, const SamTextPairIO *pair = nullptr)
 {
-    SamTextArgs a; memset(&a, 0, sizeof(a));
+    SamTextPairedArgs a; memset(&a, 0, sizeof(a));
     a.n = (uint32_t)n_records; a.n_chunks = (uint32_t)((n_records + SAMREC_CHUNK - 1) / SAMREC_CHUNK); a.ops_stride = io.ops_stride; a.n_contigs = ctx->ix.n_contigs;
     a.bases = (const uint8_t *)io.bases; a.quals = (const uint8_t *)io.quals; a.offsets = (const uint64_t *)io.offsets;
     a.names = (const uint8_t *)io.names; a.name_off = (const uint64_t *)io.name_off; a.rec_read = (const uint32_t *)io.rec_read;
@@ -2717,20 +2719,27 @@ static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint
     a.contig_names = ctx->d_contig_names; a.contig_name_off = ctx->d_contig_name_off;
     a.cap = io.cap; a.text = (uint8_t *)io.text; a.line_begin = (uint64_t *)io.line_begin;
     a.len = st.scratch((size_t)a.n * 4 + 4); a.partial = st.scratch((size_t)a.n_chunks * 8); a.summary = st.scratch(sizeof(SamTextSummary));
+    if (pair) {
+        a.rnext = (const int32_t *)pair->rnext; a.pnext = (const int64_t *)pair->pnext; a.tlen = (const int64_t *)pair->tlen;
+        a.first_written = (const int32_t *)pair->first_written; a.qs = st.scratch((size_t)a.n * 4);
+    }
     if (st.rc) return st.rc;
     uint32_t scan_blocks = (uint32_t)ctx->num_cus * 8, write_blocks = scan_blocks;
     { const uint32_t need = (a.n_chunks + 3) / 4; if (scan_blocks > need) scan_blocks = need; }
     { const uint32_t need = (a.n + 3) / 4; if (write_blocks > need) write_blocks = need; }
     HIPCHK(ctx, hipMemsetAsync(a.summary, 0, sizeof(SamTextSummary), st.s), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
-    snapgpu_launch_sam_text(&a, scan_blocks, write_blocks, st.s);
+    if (pair) snapgpu_launch_sam_text_paired(&a, scan_blocks, write_blocks, st.s);
+    else snapgpu_launch_sam_text(&a, scan_blocks, write_blocks, st.s);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipMemcpyAsync(sum, a.summary, sizeof(SamTextSummary), hipMemcpyDeviceToHost, st.s), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
     int rc = finish_timing(ctx);
     if (rc) return rc;
-    if (sum->flags & SAMTEXT_BAD_RECORD) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record has more cigar operations than ops_stride, or a contig the index does not have");
+    if (sum->flags & SAMTEXT_BAD_RECORD)
+        return fail(ctx, SNAPGPU_E_INVALID, w + (pair ? ": a record has more cigar operations than ops_stride, a contig or an rnext the index does not have, or a first_written that is neither 0 nor 1"
+                                                      : ": a record has more cigar operations than ops_stride, or a contig the index does not have"));
     return SNAPGPU_OK;
 }
 // no records: line_begin[0] = 0 and no text (the device form writes the word in HBM)
@@ -2934,23 +2943,28 @@ extern "C" int snapgpu_sam_fields_paired_device(snapgpu_ctx *ctx, uint32_t n_pai
 // launches, the SAM fields of both mates of every pair from the results where the align kernels left them, one download.  What
 // snapgpu_align_paired on a clipped copy of the reads, a host scatter and snapgpu_sam_fields_paired do with two uploads of the reads and a
 // round trip of the results.
-extern "C" int snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
-                                        const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
-                                        snapgpu_paired_result *results, snapgpu_paired_result *first_alt,
-                                        int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
-                                        int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
-                                        int32_t *reference_history_dependent)
+// (`text`, snapgpu_align_sam_paired_text: the fields but flag and first_written stay in HBM -- a NULL output is a device-only buffer -- and the
+// lines of the batch's pairs follow them, with the names uploaded beside the batch and the lines that were written in the one download)
+struct PairedTextOut { const char *names; const uint64_t *name_off; uint64_t cap; char *text; uint64_t *line_begin; uint64_t *text_bytes; };
+static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                 const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                 snapgpu_paired_result *results, snapgpu_paired_result *first_alt,
+                                 int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                                 int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
+                                 int32_t *reference_history_dependent, const PairedTextOut *text)
 {
-    const char *who = "snapgpu_align_sam_paired";
-    if (!ctx || (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !flag || !contig || !pos || !mapq || !ops || !n_ops ||
-                             !nm || !rnext || !pnext || !tlen || !first_written || !reference_history_dependent)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: null argument");
-    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: ops_stride must be at least 3");
+    const std::string w(who);
+    if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, w + ": ops_stride must be at least 3");
     if (!ctx->paired || ctx->secondary)
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: a paired-end context without secondary results is needed (snapgpu_enable_paired, no snapgpu_enable_secondary)");
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": a paired-end context without secondary results is needed (snapgpu_enable_paired, no snapgpu_enable_secondary)");
+    if (text) {
+        if (const int rc = sam_text_check(ctx, w, 2 * (uint64_t)n_pairs, ops_stride)) return rc;
+        *text->line_begin = 0; *text->text_bytes = 0;
+    }
     if (n_pairs == 0) return SNAPGPU_OK;
-    if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: too many pairs");
+    if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, w + ": too many pairs");
     const uint32_t n = 2 * n_pairs;
+    for (uint32_t i = 0; text && i < n; i++) if (text->name_off[i + 1] < text->name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": name_off must be non-decreasing");
     SamfGeom g; uint32_t RL;
     int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
         if (!skip[i >> 1] && (uint32_t)data_len[i] > ctx->params.max_read_len)
@@ -2976,15 +2990,134 @@ extern "C" int snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, cons
     a.n_ops = st.out(n_ops, n4); a.nm = st.out(nm, n4);
     a.rnext = st.out(rnext, n4); a.pnext = st.out(pnext, n8); a.tlen = st.out(tlen, n8); a.first_written = st.out(first_written, (size_t)n_pairs * 4);
     a.stale = st.out(reference_history_dependent, n4);
+    const void *d_names = nullptr, *d_name_off = nullptr; void *d_text = nullptr, *d_line_begin = nullptr;
+    if (text) {
+        d_names = st.in(text->names, (size_t)text->name_off[n]); d_name_off = st.in(text->name_off, ((size_t)n + 1) * 8);
+        d_text = st.out(text->text, (size_t)text->cap); d_line_begin = st.out(text->line_begin, ((size_t)n + 1) * 8);
+    }
     if (st.rc) return st.rc;
     if ((rc = launch_paired(ctx, n_pairs, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s, &clip)) || (rc = finish_timing(ctx))) return rc;      // (the align launches' own hipEvent time, before the events are reused)
     // what snapgpu_align_paired reports for a pool overflow, without the results on the host: the pairs still flagged after the second pass, counted
     HIPCHK(ctx, hipMemsetAsync(d_overflowed, 0, 4, st.s), SNAPGPU_E_LAUNCH);
     snapgpu_launch_collect_flagged((snapgpu_paired_result *)d_results, n_pairs, ctx->d_flag_list, d_overflowed, 0, st.s);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    if ((rc = launch_sam_fields(ctx, a, g, n, ops_stride, use_m, st)) || (rc = st.download())) return rc;
+    if ((rc = launch_sam_fields(ctx, a, g, n, ops_stride, use_m, st))) return rc;
+    if (!text) {
+        if ((rc = st.download()) || (rc = finish_timing(ctx))) return rc;
+        return h_overflowed ? fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG) : SNAPGPU_OK;
+    }
+    // ---- the lines of the pairs, from the fields where the SAM-field kernel left them (pair unit u is pair u)
     if ((rc = finish_timing(ctx))) return rc;
-    return h_overflowed ? fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG) : SNAPGPU_OK;
+    const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, nullptr, a.flag, a.contig, a.pos, a.mapq, a.ops, ops_stride, a.n_ops, a.nm,
+                       text->cap, d_text, d_line_begin};
+    const SamTextPairIO pio{a.rnext, a.pnext, a.tlen, a.first_written};
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = sam_text_core(ctx, w, st, n, io, &sum, &pio))) return rc;
+    if (sum.flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
+    st.limit(d_text, (size_t)sum.written);                               // only the lines that were written come down
+    if ((rc = st.download())) return rc;
+    *text->text_bytes = sum.total;
+    if (h_overflowed) return fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG);
+    return sum.total > text->cap ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+}
+
+extern "C" int snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                        const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                        snapgpu_paired_result *results, snapgpu_paired_result *first_alt,
+                                        int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
+                                        int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
+                                        int32_t *reference_history_dependent)
+{
+    if (!ctx || (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !flag || !contig || !pos || !mapq || !ops || !n_ops ||
+                             !nm || !rnext || !pnext || !tlen || !first_written || !reference_history_dependent)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: null argument");
+    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
+                                 flag, contig, pos, mapq, ops, ops_stride, n_ops, nm, rnext, pnext, tlen, first_written, reference_history_dependent, nullptr);
+}
+
+// Paired-end reads to the TEXT of their SAM records in one call (SAMFormat::writePairs, SAM.cpp:1575-1895, after what snapgpu_align_sam_paired replaces)
+extern "C" int snapgpu_align_sam_paired_text(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                             snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    if (!ctx || !line_begin || !text_bytes || (text_capacity && !text) ||
+        (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off || !flag || !first_written)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired_text: null argument");
+    const PairedTextOut t{names, name_off, text_capacity, text, line_begin, text_bytes};
+    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_text", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
+                                 flag, nullptr, nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, &t);
+}
+
+// The two lines of each pair unit from fields in HBM (SAMFormat::writePairs' snprintf, SAM.cpp:1854-1875; QNAME: ReadWriter.cpp:405-420; QS: SAM.cpp:1826-1834)
+extern "C" int snapgpu_sam_text_paired_device(snapgpu_ctx *ctx, uint64_t n_units, const void *d_bases, const void *d_quals, const void *d_offsets,
+                                              const void *d_names, const void *d_name_off, const void *d_unit_pair, const void *d_flag, const void *d_contig,
+                                              const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                              const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
+                                              uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
+{
+    const std::string w = "snapgpu_sam_text_paired_device";
+    if (!ctx || !text_bytes || !d_line_begin || (text_capacity && !d_text) ||
+        (n_units && (!d_bases || !d_quals || !d_offsets || !d_names || !d_name_off || !d_flag || !d_contig || !d_pos || !d_mapq || !d_ops || !d_n_ops || !d_nm ||
+                     !d_rnext || !d_pnext || !d_tlen || !d_first_written)))
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    if (n_units > 0x7fffffffull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^31 - 1 pair units in one call");
+    int rc = sam_text_check(ctx, w, 2 * n_units, ops_stride);
+    if (rc) return rc;
+    if (n_units == 0) return sam_text_empty(ctx, false, d_line_begin, text_bytes, stream);
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_unit_pair, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
+                       text_capacity, d_text, d_line_begin};
+    const SamTextPairIO pio{d_rnext, d_pnext, d_tlen, d_first_written};
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = sam_text_core(ctx, w, st, 2 * n_units, io, &sum, &pio))) return rc;
+    *text_bytes = sum.total;
+    return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+}
+
+// Host-pointer form: one upload, and only the lines that were written and line_begin come down
+extern "C" int snapgpu_sam_text_paired(snapgpu_ctx *ctx, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                       const char *names, const uint64_t *name_off, const uint32_t *unit_pair, const int32_t *flag, const int32_t *contig,
+                                       const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                                       const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
+                                       uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    const std::string w = "snapgpu_sam_text_paired";
+    if (!ctx || !text_bytes || !line_begin || (text_capacity && !text) ||
+        (n_units && (!bases || !quals || !offsets || !names || !name_off || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm || !rnext || !pnext || !tlen ||
+                     !first_written)))
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    if (n_units > 0x7fffffffull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^31 - 1 pair units in one call");
+    if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, w + ": too many pairs");
+    int rc = sam_text_check(ctx, w, 2 * n_units, ops_stride);
+    if (rc) return rc;
+    if (n_units == 0) return sam_text_empty(ctx, true, line_begin, text_bytes, nullptr);
+    if (!unit_pair && n_units != n_pairs) return fail(ctx, SNAPGPU_E_INVALID, w + ": without unit_pair there is one unit per pair (n_units == n_pairs)");
+    const uint32_t n_reads = 2 * n_pairs;
+    for (uint32_t i = 0; i < n_reads; i++)
+        if (offsets[i + 1] < offsets[i] || name_off[i + 1] < name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": offsets and name_off must be non-decreasing");
+    for (uint64_t u = 0; unit_pair && u < n_units; u++)
+        if (unit_pair[u] >= n_pairs) return fail(ctx, SNAPGPU_E_INVALID, w + ": unit_pair names a pair the batch does not have");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, ctx->stream);
+    const size_t nb = (size_t)offsets[n_reads], nl = 2 * (size_t)n_units, r4 = nl * 4, r8 = nl * 8;
+    SamTextIO io; SamTextPairIO pio;
+    io.bases = st.in(bases, nb); io.quals = st.in(quals, nb); io.offsets = st.in(offsets, ((size_t)n_reads + 1) * 8);
+    io.names = st.in(names, (size_t)name_off[n_reads]); io.name_off = st.in(name_off, ((size_t)n_reads + 1) * 8);
+    io.rec_read = unit_pair ? (const void *)st.in(unit_pair, (size_t)n_units * 4) : nullptr;
+    io.flag = st.in(flag, r4); io.contig = st.in(contig, r4); io.pos = st.in(pos, r8); io.mapq = st.in(mapq, r4);
+    io.ops = st.in(ops, r4 * ops_stride); io.ops_stride = ops_stride; io.n_ops = st.in(n_ops, r4); io.nm = st.in(nm, r4);
+    pio.rnext = st.in(rnext, r4); pio.pnext = st.in(pnext, r8); pio.tlen = st.in(tlen, r8); pio.first_written = st.in(first_written, (size_t)n_units * 4);
+    io.cap = text_capacity; io.text = st.out(text, (size_t)text_capacity); io.line_begin = st.out(line_begin, (nl + 1) * 8);
+    if (st.rc) return st.rc;
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = sam_text_core(ctx, w, st, nl, io, &sum, &pio))) return rc;
+    st.limit(io.text, (size_t)sum.written);                              // only the lines that were written come down
+    if ((rc = st.download())) return rc;
+    *text_bytes = sum.total;
+    return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
 // Diagnostics (not part of the drop-in surface): how many SamfPre records the row-loop pre-pass (k_samf_dp8 / k_samf_dp8_paired) of the context's
