@@ -139,12 +139,12 @@ def main():
     read_len = int(opt.get("read-len", 150)); max_k = int(opt.get("max-k", 8))
 
     unit, asm_flags, src = "single_sec_k3", ["-DSINGLE_AGC=3"], "single_sec_k.hip"
-    kern = ["k_align_singleILi3ELb0ELb1ELb0ELb0EE", "lv_compute_fn", "ag_dispatch_fnILi3ELb1E"]
+    kern = ["k_align_singleILi3ELb0ELb1ELb0ELb0EE", "lv_compute_fn", "ag_hot_fnILb1E", "ag_cold_fnILi3ELb1E"]
     gfn = None
     if mode.endswith("paired"):          # the paired-end kernel of the read length's class (2 x 150: AGC 3; 2 x 250: AGC 4), fast form
         agc = 3 if read_len <= 170 else 6
         unit, asm_flags, src = "paired_k%d" % agc, ["-DPAIRED_AGC=%d" % agc], "paired_k.hip"
-        kern = ["k_align_pairedILi%dELb0ELb0E" % agc, "lv_compute_fn", "ag_dispatch_fnILi%dELb0E" % agc]
+        kern = ["k_align_pairedILi%dELb0ELb0E" % agc, "lv_compute_fn", "ag_hot_fnILb0E", "ag_cold_fnILi%dELb0E" % agc]
     if mode.startswith("run-"):          # the child: run the workload on the coverage build; the counters are written when the process exits
         import tests.emu.build as eb
         os.makedirs(COV, exist_ok=True)

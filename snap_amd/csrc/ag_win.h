@@ -753,18 +753,8 @@ static __device__ __forceinline__ AGResult ag_banded_win(
                     int u_next = 0;
                     if constexpr (r < 6) u_next = __builtin_amdgcn_ds_bpermute(c_prev, u_cur);
                     const unsigned long long go = BALLOT(u_cur > Tr);                // (an offer <= 0 is never above Tr >= 0; lanes outside the segment's band: masked by kgs)
-#if defined(SNAPGPU_AG_FOLD_SCALAR)
-                    typename std::conditional<FULL, unsigned long long, uint32_t>::type cm = s == 0 ? go : (go >> seg_len);      // (a banded segment's lanes fit 32 bits)
-#else
                     const auto cm = (decltype(kgs))go;                               // (first segment of a banded call: its lanes fit 32 bits; second: tested where they are)
-#endif
-#if defined(SNAPGPU_AG_FOLD_SCALAR)                                                    // (measurement builds: the fold of rounds 4 - 5)
-                    cm &= (decltype(cm))(s == 0 ? ins_mask : (ins_mask >> seg_len));
-                    cm |= cm >> num_vec; cm |= cm >> (2 * num_vec); cm |= cm >> (4 * num_vec);
-                    const uint32_t low = (uint32_t)cm & full;
-#else
                     const uint32_t low = (uint32_t)BALLOT((cm & kgs) != 0);          // bit k: vector k goes on (kgs: lane k < nk holds the band's valid lanes of vector k; every other lane 0)
-#endif
                     if (__builtin_expect(low != full, 0)) {                          // the round stops at vector jlim: the walk ends
                         const int jlim = (int)__builtin_ctz(~low);
                         const int fm = (k <= jlim && lane_in(ins_mask)) ? u_cur : 0;   // (vectors 0 .. jlim of the segment: a vector compare against the lane's k, not a mask built on the scalar unit)
@@ -1338,52 +1328,84 @@ static __device__ __forceinline__ AGResult ag_banded_win2(
     return res;
 }
 
+// Which form takes a call.  The two forms of ag_banded_win -- every affine-gap call of a 150-bp read at -d 8 -- are the HOT ones: they get an
+// out-of-line function of their own (ag_hot_fn), so that their row loops have a register allocation and a stretch of the instruction cache that no
+// other form shapes; everything else is COLD (ag_cold_fn).
+enum { AG_FORM_NONE = 0, AG_FORM_WIN = 1, AG_FORM_FULL = 2, AG_FORM_COLD = 3 };
+
+// The selection, once per call (AGC > 0): the striped layout's dimensions, the host-sizing traps, and the form.  *ww: the band half-width the forms use.
+template <int AGC, bool EXACT>
+static __device__ __forceinline__ int ag_select(bool banded, const AGParams &prm, int pattern_len, int text_len, int w, uint32_t RL,
+                                                int *ww_out, int *num_vec_out, int *seg_len_out, int *num_seg_out)
+{
+    const int ww = w > 126 ? 126 : w;
+    *ww_out = ww; *num_vec_out = 0; *seg_len_out = 0; *num_seg_out = 0;
+    if (ww < 0) return AG_FORM_NONE;                                  // :325 / :890
+    int num_vec, seg_len, num_seg;
+    ag_dims(banded, pattern_len, ww, &num_vec, &seg_len, &num_seg);
+    *num_vec_out = num_vec; *seg_len_out = seg_len; *num_seg_out = num_seg;
+    if (num_vec > 1023 || num_seg > 255 ||
+        (size_t)text_len * (size_t)(((num_seg * seg_len + 63) >> 6) * 64) > ag_scratch_bytes(RL) ||
+        (EXACT && (size_t)text_len * (size_t)(num_seg * seg_len) > ag_scratch_bytes(RL))) {
+        __builtin_trap();                                             // host sizing bug: fail loudly
+    }
+#if defined(SNAPGPU_WAVE_EMU) && defined(SNAPGPU_AG_WIN_STATS)
+    {   // which form takes the call (scripts/emu_stats.py, emu_paired_stats.py): calls / rows / positions per form, and the unbanded register calls by chunk count
+        extern unsigned long long g_agform_stats[64];
+        const int tot_ = num_seg * seg_len;
+        const int f = banded ? (2 * seg_len <= 64 ? 1 : (seg_len <= 64 ? 2 : 3)) : (tot_ <= 64 ? 4 : 6);
+        if (lane_id() == 0) {
+            __atomic_fetch_add(&g_agform_stats[f], 1, __ATOMIC_RELAXED); __atomic_fetch_add(&g_agform_stats[8 + f], (unsigned long long)text_len, __ATOMIC_RELAXED);
+            __atomic_fetch_add(&g_agform_stats[16 + f], (unsigned long long)tot_, __ATOMIC_RELAXED);
+            if (f == 6) { __atomic_fetch_add(&g_agform_stats[24 + ((tot_ + 63) >> 6)], 1, __ATOMIC_RELAXED); __atomic_fetch_add(&g_agform_stats[32 + ((tot_ + 63) >> 6)], (unsigned long long)text_len, __ATOMIC_RELAXED); }
+            __atomic_fetch_add(&g_agform_stats[40 + (ww > 15 ? 15 : ww)], 1, __ATOMIC_RELAXED);
+            __atomic_fetch_add(&g_agform_stats[56 + (ww >= 32 ? 1 : 0) + (tot_ > 192 ? 2 : 0) + (tot_ > 256 ? 2 : 0)], 1, __ATOMIC_RELAXED);     // [56] w < 32 && tot <= 192 ... [61] w >= 32 && tot > 256
+        }
+    }
+#endif
+    if (prm.gap_open > 0) {                 // (the rewritten row loop assumes a positive gap-open penalty: see its lazy-F notes)
+        if (banded && 2 * seg_len <= 64) return AG_FORM_WIN;          // the band's two segments fit one wavefront: sliding-window form
+        if (!banded && num_seg * seg_len <= 64) return AG_FORM_FULL;  // short pattern (e.g. the read's head before an early seed): the window form's row, band = everything
+    }
+    return AG_FORM_COLD;
+}
+
+// The hot forms (form: AG_FORM_WIN or AG_FORM_FULL, as ag_select decided).
+template <bool EXACT, typename PSeq, typename TSeq, typename QSeq>
+static __device__ __forceinline__ AGResult ag_hot_inl(
+    int form, int dir, const AGParams &prm, const PSeq &P, const QSeq &Q, int pattern_len,
+    const TSeq &T, int text_len, int ww, int score_init, bool is_rc, int use_clipping,
+    int16_t *lds_rows, uint8_t *bt_scratch, uint32_t RL, const DevTables *tab,
+    int num_vec, int seg_len, int num_seg, uint32_t bt_tag)
+{
+    if (form == AG_FORM_FULL)
+        return ag_banded_win<EXACT, true>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
+                                          lds_rows, bt_scratch, tab, num_vec, seg_len, num_seg, (uint32_t)ag_scratch_bytes(RL), bt_tag);
+    return ag_banded_win<EXACT>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
+                                lds_rows, bt_scratch, tab, num_vec, seg_len, num_seg, (uint32_t)ag_scratch_bytes(RL), bt_tag);
+}
+
+// Every other form, in the order the dispatcher has always tried them (the hot forms' places are marked).
 // AGC > 0: register formulation with AGC chunks of 64 positions (the host guarantees it fits);
-// AGC == 0: the LDS formulation of ag.h (any pattern length up to RL).
+// AGC == 0: the LDS formulation of ag.h (any pattern length up to RL): no selection, the dimensions are not used.
 template <int AGC, bool EXACT, typename PSeq, typename TSeq, typename QSeq>
-static __device__ __forceinline__ AGResult ag_dispatch_inl(
+static __device__ __forceinline__ AGResult ag_cold_inl(
     bool banded, int dir, const AGParams &prm, const PSeq &P, const QSeq &Q, int pattern_len,
     const TSeq &T, int text_len, int w, int score_init, bool is_rc, int use_clipping,
-    int16_t *lds_rows, uint8_t *bt_scratch, uint32_t RL, const DevTables *tab, uint32_t bt_tag = 0)
+    int16_t *lds_rows, uint8_t *bt_scratch, uint32_t RL, const DevTables *tab,
+    int num_vec, int seg_len, int num_seg, uint32_t bt_tag)
 {
     if constexpr (AGC > 0) {
-        AGResult res; res.ag_score = -1; res.text_offset = -1; res.pattern_offset = -1; res.n_edits = -1;
-        res.match_probability = 0.0; res.stale_reads = 0;
-        int ww = w > 126 ? 126 : w;
-        if (ww < 0) return res;                                           // :325 / :890
-        int num_vec, seg_len, num_seg;
-        ag_dims(banded, pattern_len, ww, &num_vec, &seg_len, &num_seg);
+        const int ww = w > 126 ? 126 : w;
         // AGC 4 and 6 (reads beyond ~170 bp): since round 6 these kernels keep THREE chunks of 64 positions in registers like AGC 3 -- every banded call with a
-        // band half-width up to 31 goes through the window forms below, whatever the pattern length, and what is left for the chunked register form are the
+        // band half-width up to 31 goes through the window forms, whatever the pattern length, and what is left for the chunked register form are the
         // unbanded calls (pattern shorter than 3 * (2w + 1)): at most 134 positions at -d 20; BASELINE configs[4] has none beyond 128 (scripts/emu_paired_stats.py) --
         // and a call that needs more than 192 positions takes the LDS form of ag.h, which these contexts have the LDS for (ag_lds_bytes(RL)).  The kernels
         // that used to carry 256 / 384 positions of H, H-1, E in VGPRs (128 / 256 VGPRs, 4 / 2 waves per SIMD) run at AGC 3's occupancy.
         constexpr int CH = AGC > 3 ? 3 : AGC;
-        if (num_vec > 1023 || num_seg > 255 ||
-            (size_t)text_len * (size_t)(((num_seg * seg_len + 63) >> 6) * 64) > ag_scratch_bytes(RL) ||
-            (EXACT && (size_t)text_len * (size_t)(num_seg * seg_len) > ag_scratch_bytes(RL))) {
-            __builtin_trap();                                             // host sizing bug: fail loudly
-        }
-#if defined(SNAPGPU_WAVE_EMU) && defined(SNAPGPU_AG_WIN_STATS)
-        {   // which form takes the call (scripts/emu_stats.py, emu_paired_stats.py): calls / rows / positions per form, and the unbanded register calls by chunk count
-            extern unsigned long long g_agform_stats[64];
-            const int tot_ = num_seg * seg_len;
-            const int f = banded ? (2 * seg_len <= 64 ? 1 : (seg_len <= 64 ? 2 : 3)) : (tot_ <= 64 ? 4 : 6);
-            if (lane_id() == 0) {
-                __atomic_fetch_add(&g_agform_stats[f], 1, __ATOMIC_RELAXED); __atomic_fetch_add(&g_agform_stats[8 + f], (unsigned long long)text_len, __ATOMIC_RELAXED);
-                __atomic_fetch_add(&g_agform_stats[16 + f], (unsigned long long)tot_, __ATOMIC_RELAXED);
-                if (f == 6) { __atomic_fetch_add(&g_agform_stats[24 + ((tot_ + 63) >> 6)], 1, __ATOMIC_RELAXED); __atomic_fetch_add(&g_agform_stats[32 + ((tot_ + 63) >> 6)], (unsigned long long)text_len, __ATOMIC_RELAXED); }
-                __atomic_fetch_add(&g_agform_stats[40 + (ww > 15 ? 15 : ww)], 1, __ATOMIC_RELAXED);
-                __atomic_fetch_add(&g_agform_stats[56 + (ww >= 32 ? 1 : 0) + (tot_ > 192 ? 2 : 0) + (tot_ > 256 ? 2 : 0)], 1, __ATOMIC_RELAXED);     // [56] w < 32 && tot <= 192 ... [61] w >= 32 && tot > 256
-            }
-        }
-#endif
-        if (banded && 2 * seg_len <= 64 && prm.gap_open <= 0)        // (the rewritten row loop assumes a positive gap-open penalty: see its lazy-F notes)
+        if (banded && 2 * seg_len <= 64)        // a ZERO gap-open penalty (a positive one: AG_FORM_WIN)
             return ag_banded_win_v1<EXACT>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
                                            lds_rows, bt_scratch, tab, num_vec, seg_len, num_seg, (uint32_t)ag_scratch_bytes(RL), bt_tag);
-        if (banded && 2 * seg_len <= 64)        // the band's two segments fit one wavefront: sliding-window form
-            return ag_banded_win<EXACT>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
-                                        lds_rows, bt_scratch, tab, num_vec, seg_len, num_seg, (uint32_t)ag_scratch_bytes(RL), bt_tag);
 #if !defined(SNAPGPU_NO_AG_WIN2)
         if (banded && seg_len <= 64 && (size_t)text_len * 128u <= ag_scratch_bytes(RL))        // wide bands (limits 13 .. 31): one segment per register set
             return ag_banded_win2<EXACT>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
@@ -1398,10 +1420,7 @@ static __device__ __forceinline__ AGResult ag_dispatch_inl(
         if (banded)
             return ag_compute_reg<CH, true, EXACT>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
                                                    lds_rows, bt_scratch, tab, num_vec, seg_len, num_seg, (uint32_t)ag_scratch_bytes(RL), bt_tag);
-        if (num_seg * seg_len <= 64 && prm.gap_open > 0)        // short pattern (e.g. the read's head before an early seed): the window form's row, band = everything
-            return ag_banded_win<EXACT, true>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
-                                              lds_rows, bt_scratch, tab, num_vec, seg_len, num_seg, (uint32_t)ag_scratch_bytes(RL), bt_tag);
-        if (num_seg * seg_len <= 64)            // ... with a zero gap-open penalty: the chunked form with one chunk
+        if (num_seg * seg_len <= 64)            // short pattern with a zero gap-open penalty (a positive one: AG_FORM_FULL): the chunked form with one chunk
             return ag_compute_reg<1, false, EXACT>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
                                                    lds_rows, bt_scratch, tab, num_vec, seg_len, num_seg, (uint32_t)ag_scratch_bytes(RL), bt_tag);
         return ag_compute_reg<CH, false, EXACT>(dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping,
@@ -1412,26 +1431,66 @@ static __device__ __forceinline__ AGResult ag_dispatch_inl(
     }
 }
 
-// The affine-gap code as ONE function per kernel instead of one inlined copy per call site.  k_align_paired reaches ag_dispatch from 24
+// The affine-gap code as functions of the kernel instead of one inlined copy per call site.  k_align_paired reaches ag_dispatch from 24
 // places (Phases 3 and 4, the speculative Phase-4 scoring, the single-end aligner of the chimeric fallback ...), each copy ~40 KB of code:
 // 1.3 MB of kernel against a 64 KB instruction cache shared by two CUs, every copy allocated out of the caller's 256 VGPRs (1 600 bytes of
 // scratch per lane, 4 500 SGPR spills).  A call costs a few hundred cycles against the ~10^5 of the work it starts.  Arguments arrive in
 // VGPRs under the device calling convention, so everything wave-uniform is made scalar again on entry.
+// Two functions: ag_hot_fn holds the two forms of ag_banded_win and nothing else, ag_cold_fn every other form (see AG_FORM_*).  The caller's
+// inlined stub (ag_dispatch) selects; the layout's dimensions travel in one word: num_vec | num_seg << 16 (seg_len = 8 * num_vec; ag_select
+// has trapped on anything that does not fit).
 
-template <int AGC, bool EXACT, typename PSeq, typename TSeq, typename QSeq>
-static __device__ __attribute__((noinline)) AGResult ag_dispatch_fn(
-    uint32_t flags, AGParams prm_in, PSeq P_in, QSeq Q_in, int pattern_len,
-    TSeq T_in, int text_len, int w, int score_init, int use_clipping,
-    int16_t *lds_rows, uint8_t *bt_scratch, uint32_t RL, const DevTables *tab)
+struct AGCallArgs {            // what both functions make wave-uniform on entry
+    bool banded, is_rc; int dir; uint32_t bt_tag; int form;
+    int num_vec, seg_len, num_seg;
+};
+static __device__ __forceinline__ AGCallArgs ag_call_args(uint32_t flags, uint32_t dims)
 {
-    flags = first_u32(flags);
-    const bool banded = (flags & 1u) != 0, is_rc = (flags & 2u) != 0;
-    const uint32_t bt_tag = (flags >> 8) & 0xFFu;               // EXACT: the tag of the read whose image cells count (dev_common.h: bt_cell)
-    const int dir = (flags & 4u) ? -1 : 1;
+    flags = first_u32(flags); dims = first_u32(dims);
+    AGCallArgs c;
+    c.banded = (flags & 1u) != 0; c.is_rc = (flags & 2u) != 0;
+    c.dir = (flags & 4u) ? -1 : 1;
+    c.form = (flags & 8u) ? AG_FORM_FULL : AG_FORM_WIN;         // (read by ag_hot_fn only)
+    c.bt_tag = (flags >> 8) & 0xFFu;                            // EXACT: the tag of the read whose image cells count (dev_common.h: bt_cell)
+    c.num_vec = (int)(dims & 0xFFFFu); c.seg_len = c.num_vec * 8; c.num_seg = (int)(dims >> 16);
+    return c;
+}
+static __device__ __forceinline__ AGParams ag_params_uniform(const AGParams &prm_in)
+{
     AGParams prm;
     prm.match_reward = (int)first_u32((uint32_t)prm_in.match_reward); prm.sub_penalty = (int)first_u32((uint32_t)prm_in.sub_penalty);
     prm.gap_open = (int)first_u32((uint32_t)prm_in.gap_open); prm.gap_extend = (int)first_u32((uint32_t)prm_in.gap_extend);
     prm.five_bonus = (int)first_u32((uint32_t)prm_in.five_bonus); prm.three_bonus = (int)first_u32((uint32_t)prm_in.three_bonus);
+    return prm;
+}
+
+template <bool EXACT, typename PSeq, typename TSeq, typename QSeq>
+static __device__ __attribute__((noinline)) AGResult ag_hot_fn(
+    uint32_t flags, uint32_t dims, AGParams prm_in, PSeq P_in, QSeq Q_in, int pattern_len,
+    TSeq T_in, int text_len, int ww, int score_init, int use_clipping,
+    int16_t *lds_rows, uint8_t *bt_scratch, uint32_t RL, const DevTables *tab)
+{
+    const AGCallArgs c = ag_call_args(flags, dims);
+    const AGParams prm = ag_params_uniform(prm_in);
+    const PSeq P = seq_uniform(P_in); const QSeq Q = seq_uniform(Q_in); const TSeq T = seq_uniform(T_in);
+    pattern_len = (int)first_u32((uint32_t)pattern_len); text_len = (int)first_u32((uint32_t)text_len);
+    ww = (int)first_u32((uint32_t)ww); score_init = (int)first_u32((uint32_t)score_init); use_clipping = (int)first_u32((uint32_t)use_clipping);
+    lds_rows = (int16_t *)(uintptr_t)first_u64((uint64_t)(uintptr_t)lds_rows);
+    bt_scratch = (uint8_t *)(uintptr_t)first_u64((uint64_t)(uintptr_t)bt_scratch);
+    RL = first_u32(RL);
+    tab = (const DevTables *)(uintptr_t)first_u64((uint64_t)(uintptr_t)tab);
+    return ag_hot_inl<EXACT>(c.form, c.dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, c.is_rc, use_clipping,
+                             lds_rows, bt_scratch, RL, tab, c.num_vec, c.seg_len, c.num_seg, c.bt_tag);
+}
+
+template <int AGC, bool EXACT, typename PSeq, typename TSeq, typename QSeq>
+static __device__ __attribute__((noinline)) AGResult ag_cold_fn(
+    uint32_t flags, uint32_t dims, AGParams prm_in, PSeq P_in, QSeq Q_in, int pattern_len,
+    TSeq T_in, int text_len, int w, int score_init, int use_clipping,
+    int16_t *lds_rows, uint8_t *bt_scratch, uint32_t RL, const DevTables *tab)
+{
+    const AGCallArgs c = ag_call_args(flags, dims);
+    const AGParams prm = ag_params_uniform(prm_in);
     const PSeq P = seq_uniform(P_in); const QSeq Q = seq_uniform(Q_in); const TSeq T = seq_uniform(T_in);
     pattern_len = (int)first_u32((uint32_t)pattern_len); text_len = (int)first_u32((uint32_t)text_len);
     w = (int)first_u32((uint32_t)w); score_init = (int)first_u32((uint32_t)score_init); use_clipping = (int)first_u32((uint32_t)use_clipping);
@@ -1439,8 +1498,8 @@ static __device__ __attribute__((noinline)) AGResult ag_dispatch_fn(
     bt_scratch = (uint8_t *)(uintptr_t)first_u64((uint64_t)(uintptr_t)bt_scratch);
     RL = first_u32(RL);
     tab = (const DevTables *)(uintptr_t)first_u64((uint64_t)(uintptr_t)tab);
-    return ag_dispatch_inl<AGC, EXACT>(banded, dir, prm, P, Q, pattern_len, T, text_len, w, score_init, is_rc, use_clipping,
-                                       lds_rows, bt_scratch, RL, tab, bt_tag);
+    return ag_cold_inl<AGC, EXACT>(c.banded, c.dir, prm, P, Q, pattern_len, T, text_len, w, score_init, c.is_rc, use_clipping,
+                                   lds_rows, bt_scratch, RL, tab, c.num_vec, c.seg_len, c.num_seg, c.bt_tag);
 }
 
 template <int AGC, bool EXACT = false, typename PSeq, typename TSeq, typename QSeq>
@@ -1449,10 +1508,26 @@ static __device__ __forceinline__ AGResult ag_dispatch(
     const TSeq &T, int text_len, int w, int score_init, bool is_rc, int use_clipping,
     int16_t *lds_rows, uint8_t *bt_scratch, uint32_t RL, const DevTables *tab, uint32_t bt_tag = 0)
 {
+    int form = AG_FORM_COLD, ww = w, num_vec = 0, seg_len = 0, num_seg = 0;
+    if constexpr (AGC > 0) {
+        form = ag_select<AGC, EXACT>(banded, prm, pattern_len, text_len, w, RL, &ww, &num_vec, &seg_len, &num_seg);
+        if (form == AG_FORM_NONE) {
+            AGResult res; res.ag_score = -1; res.text_offset = -1; res.pattern_offset = -1; res.n_edits = -1;
+            res.match_probability = 0.0; res.stale_reads = 0;
+            return res;
+        }
+    }
 #if !defined(SNAPGPU_AG_LV_FUNCTIONS)
-    return ag_dispatch_inl<AGC, EXACT>(banded, dir, prm, P, Q, pattern_len, T, text_len, w, score_init, is_rc, use_clipping, lds_rows, bt_scratch, RL, tab, bt_tag);
+    if (form != AG_FORM_COLD)
+        return ag_hot_inl<EXACT>(form, dir, prm, P, Q, pattern_len, T, text_len, ww, score_init, is_rc, use_clipping, lds_rows, bt_scratch, RL, tab,
+                                 num_vec, seg_len, num_seg, bt_tag);
+    return ag_cold_inl<AGC, EXACT>(banded, dir, prm, P, Q, pattern_len, T, text_len, w, score_init, is_rc, use_clipping, lds_rows, bt_scratch, RL, tab,
+                                   num_vec, seg_len, num_seg, bt_tag);
 #else
-    const uint32_t flags = (banded ? 1u : 0u) | (is_rc ? 2u : 0u) | (dir == -1 ? 4u : 0u) | (bt_tag << 8);
-    return ag_dispatch_fn<AGC, EXACT, PSeq, TSeq, QSeq>(flags, prm, P, Q, pattern_len, T, text_len, w, score_init, use_clipping, lds_rows, bt_scratch, RL, tab);
+    const uint32_t flags = (banded ? 1u : 0u) | (is_rc ? 2u : 0u) | (dir == -1 ? 4u : 0u) | (form == AG_FORM_FULL ? 8u : 0u) | (bt_tag << 8);
+    const uint32_t dims = (uint32_t)num_vec | ((uint32_t)num_seg << 16);
+    if (form != AG_FORM_COLD)
+        return ag_hot_fn<EXACT, PSeq, TSeq, QSeq>(flags, dims, prm, P, Q, pattern_len, T, text_len, ww, score_init, use_clipping, lds_rows, bt_scratch, RL, tab);
+    return ag_cold_fn<AGC, EXACT, PSeq, TSeq, QSeq>(flags, dims, prm, P, Q, pattern_len, T, text_len, w, score_init, use_clipping, lds_rows, bt_scratch, RL, tab);
 #endif
 }
