@@ -346,6 +346,10 @@ int  snapgpu_lookup_seeds_device(snapgpu_ctx *ctx, uint32_t n, const void *d_see
  *   k[i]    = edit distance limit
  * Outputs (each [n]): score (ScoreAboveLimit if > k), match_probability, net_indel,
  * total_indels, text_span.
+ * SNAPGPU_LV_FORM (environment, read by every call; for tests) selects the form of the device code that answers: unset, the entry's own
+ * (sequences read from HBM); "lds", the aligners' (sequences staged into LDS); "hbm", the paired-end kernel's for limits above its LDS
+ * triangle (level triangle and bitmaps in HBM).  Same answers.  "lds" returns SNAPGPU_E_UNSUPPORTED, before anything is launched, for a
+ * batch whose staged sequences and triangle exceed 64 KB of LDS (k = 126 on 1000 bases); any other value is SNAPGPU_E_INVALID.
  */
 int  snapgpu_landau_vishkin(snapgpu_ctx *ctx, int dir, uint32_t n,
                             const char *texts, uint64_t texts_bytes, const uint32_t *text_off, const int32_t *text_len,

@@ -145,24 +145,48 @@ struct LVBatchArgs {
     const uint8_t *patterns; const uint8_t *quals; const uint32_t *pat_off; const int32_t *pat_len; const int32_t *k;
     int32_t *score; double *prob; int32_t *net_indel; int32_t *total_indels; int32_t *text_span;
     const DevTables *tab;
+    uint32_t tcap; uint8_t *tri_hbm;       // forms LV_FORM_LDS / LV_FORM_HBM: bytes of one staged text; LV_FORM_HBM: the waves' triangles
 };
 
+// The forms of the test entry (SNAPGPU_LV_FORM): the instantiations of lv_compute that the kernels run.
+#define LV_FORM_BYTES 0      // sequences read from HBM (ByteSeq), triangle in LDS: no kernel's form, the entry's own
+#define LV_FORM_LDS   1      // sequences staged into LDS (LdsSeq), triangle in LDS: every call of the aligners
+#define LV_FORM_HBM   2      // sequences staged into LDS (LdsSeq), triangle, backtrace words and bitmaps in HBM: paired_dev.h, limits above AlignCfg::kmax
+// the text bytes a problem can look at: text[d + i] with i < pattern_len and d <= 126
+static __host__ __device__ __forceinline__ int lv_staged_text_len(int plen, int tlen) { const int m = plen + 127; return tlen < 0 ? 0 : (tlen < m ? tlen : m); }
+
 // One wave per problem: LandauVishkin<dir>::computeEditDistance.
+template <int FORM>
 __global__ __launch_bounds__(256) void k_lv_batch(LVBatchArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = lane_id();
     const int wave_in_block = (int)(threadIdx.x >> 6);
-    const uint32_t per_wave = (lv_lds_bytes(a.kmax, a.pcap) + 15) & ~15u;
+    const uint32_t per_tri = FORM == LV_FORM_HBM ? 0u : (lv_lds_bytes(a.kmax, a.pcap) + 15) & ~15u;
+    const uint32_t per_wave = per_tri + (FORM == LV_FORM_BYTES ? 0u : 2 * a.pcap + a.tcap);
     uint16_t *tri = (uint16_t *)(lds + (size_t)wave_in_block * per_wave);
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    if (FORM == LV_FORM_HBM) tri = (uint16_t *)(a.tri_hbm + (size_t)wave * ((lv_lds_bytes(a.kmax, a.pcap) + 15) & ~15u));
     for (uint32_t i = wave; i < a.n; i += n_waves) {
         int plen = a.pat_len[i], tlen = a.text_len[i], k = a.k[i];
         const uint8_t *p = a.patterns + a.pat_off[i];
         const uint8_t *q = a.quals + a.pat_off[i];
         const uint8_t *t = a.texts + a.text_off[i];
         LVResult r;
+        if (FORM != LV_FORM_BYTES) {
+            // as the aligners hold them: the read and its qualities once, the backward direction walking them (and the text) with stride -1
+            LDS_AS uint8_t *sp = (LDS_AS uint8_t *)(lds + (size_t)wave_in_block * per_wave + per_tri), *sq = sp + a.pcap, *stx = sq + a.pcap;
+            const int ts = lv_staged_text_len(plen, tlen);
+            for (int j = lane; j < plen; j += WAVE) { const int at = a.dir == 1 ? j : plen - 1 - j; sp[at] = p[j]; sq[at] = q[j]; }
+            for (int j = lane; j < ts; j += WAVE) stx[a.dir == 1 ? j : ts - 1 - j] = a.dir == 1 ? t[j] : t[-1 - j];
+            WAVE_SYNC();
+            const int org_p = a.dir == 1 ? 0 : plen - 1, org_t = a.dir == 1 ? 0 : ts - 1;
+            LdsSeq P{sp + org_p, a.dir}, Q{sq + org_p, a.dir}, T{stx + org_t, a.dir};
+            if (FORM == LV_FORM_LDS) r = lv_compute(P, Q, plen, T, tlen, k, tri, a.kmax, a.tab, a.pcap);
+            else                     r = lv_compute<false>(P, Q, plen, T, tlen, k, tri, a.kmax, a.tab, a.pcap);
+            WAVE_SYNC();
+        } else
         if (a.dir == 1) {
             ByteSeq P{p, 1}, Q{q, 1}, T{t, 1};
             r = lv_compute(P, Q, plen, T, tlen, k, tri, a.kmax, a.tab, a.pcap);
@@ -2127,29 +2151,48 @@ extern "C" int snapgpu_landau_vishkin(snapgpu_ctx *ctx, int dir, uint32_t n,
     if (!ctx || (dir != 1 && dir != -1)) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_landau_vishkin: bad argument");
     if (n == 0) return SNAPGPU_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    uint32_t kmax = 0, pcap = 64;
+    // SNAPGPU_LV_FORM, read per call: which instantiation of lv_compute answers (k_lv_batch).  Unset: the entry's own.
+    int form = LV_FORM_BYTES;
+    if (const char *f = getenv("SNAPGPU_LV_FORM")) {
+        if (!strcmp(f, "lds")) form = LV_FORM_LDS;
+        else if (!strcmp(f, "hbm")) form = LV_FORM_HBM;
+        else if (*f) return fail(ctx, SNAPGPU_E_INVALID, "SNAPGPU_LV_FORM: lds or hbm");
+    }
+    uint32_t kmax = 0, pcap = 64, tcap = 16;
     for (uint32_t i = 0; i < n; i++) {
         if (pat_len[i] < 0 || pat_len[i] > 1000) return fail(ctx, SNAPGPU_E_INVALID, "pattern length out of range");
         int kk = k[i] > 126 ? 126 : k[i];
         if (kk > (int)kmax) kmax = (uint32_t)kk;
         if ((uint32_t)pat_len[i] > pcap) pcap = (uint32_t)pat_len[i];
+        const uint32_t ts = (uint32_t)lv_staged_text_len(pat_len[i], text_len[i]);
+        if (ts > tcap) tcap = ts;
     }
+    pcap = (pcap + 63) & ~63u; tcap = (tcap + 15) & ~15u;
+    const uint32_t per_tri = (lv_lds_bytes(kmax, pcap) + 15) & ~15u;
+    uint32_t per_wave = (form == LV_FORM_HBM ? 0u : per_tri) + (form == LV_FORM_BYTES ? 0u : 2 * pcap + tcap);
+    uint32_t waves_per_block = 4;
+    while (waves_per_block > 1 && (size_t)waves_per_block * per_wave > 64 * 1024) waves_per_block >>= 1;
+    if (form != LV_FORM_BYTES && (size_t)waves_per_block * per_wave > 64 * 1024)
+        return fail(ctx, SNAPGPU_E_UNSUPPORTED, "SNAPGPU_LV_FORM=lds: the staged sequences and the triangle of this k do not fit 64 KB of LDS (the hbm form takes the problem)");
     Stage st(ctx, ctx->stream);
     const size_t n4 = (size_t)n * 4;
     LVBatchArgs a;
-    a.dir = dir; a.n = n; a.kmax = kmax; a.pcap = (pcap + 63) & ~63u; a.tab = ctx->d_tab;
+    a.dir = dir; a.n = n; a.kmax = kmax; a.pcap = pcap; a.tab = ctx->d_tab; a.tcap = tcap; a.tri_hbm = nullptr;
     a.texts = st.in(texts, texts_bytes); a.text_off = st.in(text_off, n4); a.text_len = st.in(text_len, n4);
     a.patterns = st.in(patterns, patterns_bytes); a.quals = st.in(quals, patterns_bytes); a.pat_off = st.in(pat_off, n4);
     a.pat_len = st.in(pat_len, n4); a.k = st.in(k, n4);
     a.score = st.out(score, n4); a.prob = st.out(match_probability, (size_t)n * 8); a.net_indel = st.out(net_indel, n4);
     a.total_indels = st.out(total_indels, n4); a.text_span = st.out(text_span, n4);
     if (st.rc) return st.rc;
-    uint32_t per_wave = (lv_lds_bytes(kmax, a.pcap) + 15) & ~15u;
-    uint32_t waves_per_block = 4;
-    while (waves_per_block > 1 && (size_t)waves_per_block * per_wave > 64 * 1024) waves_per_block >>= 1;
     if ((size_t)waves_per_block * per_wave > 64 * 1024) return fail(ctx, SNAPGPU_E_UNSUPPORTED, "k too large for the LDS triangle");
-    uint32_t blocks = (n + waves_per_block - 1) / waves_per_block; uint32_t maxb = (uint32_t)ctx->num_cus * 8; if (blocks > maxb) blocks = maxb;
-    hipLaunchKernelGGL(k_lv_batch, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * per_wave, st.s, a);
+    uint32_t blocks = (n + waves_per_block - 1) / waves_per_block; uint32_t maxb = (uint32_t)ctx->num_cus * (form == LV_FORM_HBM ? 2 : 8); if (blocks > maxb) blocks = maxb;
+    if (form == LV_FORM_HBM) {                      // one triangle per wave of the grid, as the paired-end kernel's waves have theirs
+        a.tri_hbm = st.scratch((size_t)blocks * waves_per_block * per_tri);
+        if (st.rc) return st.rc;
+    }
+    if (form == LV_FORM_LDS)      hipLaunchKernelGGL(k_lv_batch<LV_FORM_LDS>, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * per_wave, st.s, a);
+    else if (form == LV_FORM_HBM) hipLaunchKernelGGL(k_lv_batch<LV_FORM_HBM>, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * per_wave, st.s, a);
+    else                          hipLaunchKernelGGL(k_lv_batch<LV_FORM_BYTES>, dim3(blocks), dim3(64 * waves_per_block), waves_per_block * per_wave, st.s, a);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
     return st.download();
 }
