@@ -36,6 +36,11 @@
  *   snapgpu_sam_text_paired / _device, snapgpu_align_sam_paired_text
  *       SAMFormat::writePairs, the printed lines of a pair's result  SNAPLib/SAM.cpp:1575-1895 (snprintf :1854-1875, QS :1826-1834); the
  *       "/1" "/2" rule and the print order of SimpleReadWriter::writePairs  SNAPLib/ReadWriter.cpp:405-420 / 453-461
+ *   snapgpu_bam_records_single / _device, snapgpu_align_sam_single_bam
+ *       BAMFormat::writeRead, the bytes of a single-end record before BGZF compression  SNAPLib/Bam.cpp:1312-1508 (reg2bin :523-535, the
+ *       sequence codes :505-510, the aux fields :1510-1650)
+ *   snapgpu_bam_records_paired / _device, snapgpu_align_sam_paired_bam
+ *       BAMFormat::writePairs, the bytes of the two records of a pair's result  SNAPLib/Bam.cpp:1033-1309
  *   snapgpu_sam_fields_single
  *       SimpleReadWriter::writeReads            SNAPLib/ReadWriter.cpp:170-330
  *       SAMFormat::writeRead / createSAMLine / computeCigarString  SNAPLib/SAM.cpp:1898-2352 / 1424-1572 / 2595-2766
@@ -75,7 +80,7 @@ extern "C" {
 #define SNAPGPU_E_LAUNCH       -5   /* kernel launch or execution failed                 */
 #define SNAPGPU_W_SECONDARY_TRUNCATED 1 /* some read has more secondary results than the caller's stride: see snapgpu_align_single_secondary */
 #define SNAPGPU_W_RECORDS_TRUNCATED 2   /* the batch has more SAM records than the caller's record capacity: see snapgpu_align_sam_single_records */
-#define SNAPGPU_W_TEXT_TRUNCATED 3      /* the SAM lines need more bytes than the caller's text capacity: see snapgpu_sam_text_single_device */
+#define SNAPGPU_W_TEXT_TRUNCATED 3      /* the SAM lines (or BAM records) need more bytes than the caller's capacity: see snapgpu_sam_text_single_device */
 
 /* mirrors enum AlignmentResult, SNAPLib/AlignmentResult.h:33 */
 enum { SNAPGPU_NotFound = 0, SNAPGPU_SingleHit = 1, SNAPGPU_MultipleHits = 2 };
@@ -706,6 +711,76 @@ int  snapgpu_align_sam_paired_text(snapgpu_ctx *ctx, uint32_t n_pairs, const cha
                                    const char *names, const uint64_t *name_off, uint32_t ops_stride,
                                    snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
                                    uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes);
+
+/*
+ * Records -> the bytes of their BAM records, uncompressed: what BAMFormat::writeRead (Bam.cpp:1312-1508) and writePairs (Bam.cpp:1033-1309)
+ * lay out for a record before the BGZF stage, which stays with the caller.  Per record, little endian:
+ *   block_size | refID | pos - 1 | bin << 16 | (mapq & 0xff) << 8 | l_qname + 1 | flag << 16 | n_cigar | l_seq | next_refID | pnext - 1 | tlen
+ *   | QNAME NUL | cigar | SEQ | QUAL | aux
+ * refID / next_refID are the contigs' BAM numbers (snapgpu_set_contig_bam_ids) or -1; QNAME as in the text calls (cut at its first space; a
+ * pair's names lose "/1" / "/2" together first); the cigar is the record's row of ops as it stands (n_ops <= 0: none); l_seq, SEQ and QUAL
+ * are the whole, unclipped read in the record's orientation: SEQ two bases a byte, high nibble first, coded by "=ACMGRSVTWYHKDBN" with every
+ * other byte (and '=') 15 (Bam.cpp:505-510), QUAL byte - 33.  bin = reg2bin(pos - 1, pos - 1 + ref_len) (Bam.cpp:523-535), ref_len the
+ * lengths of the operations CigarCodeToRefBase counts (Bam.cpp:270) or l_seq without operations; an unmapped mate of a mapped one takes it
+ * from pnext, any other unmapped record gets reg2bin(-1, 0) (Bam.cpp:1473-1477).  tlen is tlen >= 0 ? tlen & 0x7fffffff :
+ * -((-tlen) & 0x7fffffff).  aux: RG:Z:FASTQ PL:Z:Illumina PU:Z:pu LB:Z:lb SM:Z:sm PG:Z:SNAP NM:C (one byte: -1 reads as 255) and, for mates,
+ * QS:i (Bam.cpp:1510-1650).  Single-end records: next_refID -1, next position -1, tlen 0.
+ *
+ * snapgpu_set_contig_bam_ids: ref_id[c] is the BAM reference number of index contig c -- its place in the header's reference table, which
+ * a writer orders by the contigs' original (FASTA) numbers (Bam.cpp:1003-1021).  NULL: contig c is number c.  n_contigs must be the index's
+ * count.  Per context, like the names; replaces an earlier call.
+ */
+int  snapgpu_set_contig_bam_ids(snapgpu_ctx *ctx, uint32_t n_contigs, const int32_t *ref_id);
+
+/*
+ * The three forms of snapgpu_sam_text_single_device, snapgpu_sam_text_single and snapgpu_align_sam_single_text over BAM records (replacing
+ * BAMFormat::writeRead, Bam.cpp:1312-1508): every argument, check, warning and error as there, except that
+ *   byte_capacity, d_bytes / bytes, d_block_begin / block_begin (uint64 [n_records + 1]; fused form: [record_capacity + 1]), bam_bytes
+ *       stand where text_capacity, text, line_begin and text_bytes stand: record r is bytes [block_begin[r], block_begin[r + 1]), its
+ *       block_size word included, and *bam_bytes what all records need;
+ *   the contigs' BAM numbers (snapgpu_set_contig_bam_ids) are needed instead of their names;
+ *   a QNAME longer than 254 bytes after the cut fails with SNAPGPU_E_INVALID and a message that names the record (Bam.cpp:1394-1397).
+ * SNAPGPU_W_TEXT_TRUNCATED (*bam_bytes > byte_capacity) means what it means for text: block_begin is complete, every record that lies
+ * wholly below the capacity is written exactly as a large enough call writes it, nothing at or beyond the capacity is touched.  In the fused
+ * call SNAPGPU_W_RECORDS_TRUNCATED comes first.  A record never assumes an alignment: d_bytes may be any byte address.
+ */
+int  snapgpu_bam_records_single_device(snapgpu_ctx *ctx, uint64_t n_records,
+                                       const void *d_bases, const void *d_quals, const void *d_offsets, const void *d_names, const void *d_name_off,
+                                       const void *d_rec_read, const void *d_flag, const void *d_contig, const void *d_pos, const void *d_mapq,
+                                       const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                       uint64_t byte_capacity, void *d_bytes, void *d_block_begin, uint64_t *bam_bytes, void *stream);
+int  snapgpu_bam_records_single(snapgpu_ctx *ctx, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
+                                const char *names, const uint64_t *name_off, const uint32_t *rec_read, const int32_t *flag, const int32_t *contig,
+                                const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                                uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes);
+int  snapgpu_align_sam_single_bam(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                  const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                  const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                  uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                  uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes);
+
+/*
+ * The three forms of snapgpu_sam_text_paired_device, snapgpu_sam_text_paired and snapgpu_align_sam_paired_text over BAM records (replacing
+ * BAMFormat::writePairs, Bam.cpp:1033-1309): pair units, unit_pair, first_written, rnext / pnext / tlen and two records per unit in print
+ * order as there (block_begin: uint64 [2 * n_units + 1]); next_refID is the record's own refID for rnext -2; QS:i carries the value the
+ * text calls print.  What differs from the text calls is what differs for the single-end forms above.
+ */
+int  snapgpu_bam_records_paired_device(snapgpu_ctx *ctx, uint64_t n_units,
+                                       const void *d_bases, const void *d_quals, const void *d_offsets, const void *d_names, const void *d_name_off,
+                                       const void *d_unit_pair, const void *d_flag, const void *d_contig, const void *d_pos, const void *d_mapq,
+                                       const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                       const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
+                                       uint64_t byte_capacity, void *d_bytes, void *d_block_begin, uint64_t *bam_bytes, void *stream);
+int  snapgpu_bam_records_paired(snapgpu_ctx *ctx, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                const char *names, const uint64_t *name_off, const uint32_t *unit_pair, const int32_t *flag, const int32_t *contig,
+                                const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                                const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
+                                uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes);
+int  snapgpu_align_sam_paired_bam(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                  const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                  const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                  snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                  uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes);
 
 /*
  * Batched AffineGapVectorized<dir>::computeScore (banded[i] == 0) / computeScoreBanded

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = [
     "snapgpu_enable_secondary", "snapgpu_align_single_secondary", "snapgpu_align_single_secondary_device",
     "snapgpu_align_paired_secondary", "snapgpu_align_paired_secondary_device",
     "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_single_records", "snapgpu_align_sam_single_records_device", "snapgpu_set_contig_names", "snapgpu_sam_text_single", "snapgpu_sam_text_single_device", "snapgpu_align_sam_single_text", "snapgpu_align_sam_paired", "snapgpu_sam_text_paired", "snapgpu_sam_text_paired_device", "snapgpu_align_sam_paired_text","snapgpu_create_replica_with_params",
+    "snapgpu_set_contig_bam_ids", "snapgpu_bam_records_single", "snapgpu_bam_records_single_device", "snapgpu_align_sam_single_bam",
+    "snapgpu_bam_records_paired", "snapgpu_bam_records_paired_device", "snapgpu_align_sam_paired_bam",
     "snapgpu_default_index_build_params", "snapgpu_index_build", "snapgpu_index_build_from_fasta", "snapgpu_index_build_shaped",
     "snapgpu_index_build_from_fasta_shaped", "snapgpu_built_index_view",
     "snapgpu_built_index_save", "snapgpu_built_index_stats", "snapgpu_built_index_destroy",
@@ -428,7 +430,7 @@ class BaseAligner:
         self._check(self.lib.snapgpu_set_contig_names(self.handle, C.c_uint32(len(enc)), C.cast(arr, C.c_void_p)), "snapgpu_set_contig_names")
 
     def samText(self, bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rec_read=None, capacity: int | None = None,
-                grow: bool = True, text=None):
+                grow: bool = True, text=None, _fn: str = "snapgpu_sam_text_single"):
         """The SAM lines of a batch's records (snapgpu_sam_text_single): bases / quals / offsets the unclipped reads, names / name_off
         (uint64[n_reads + 1]) their names, flag .. nm the records' fields as samFields / alignSamRecords return them (ops: [n_records,
         ops_stride]); rec_read: the read of each record (None: record i is read i).  capacity: bytes of text to make room for (default:
@@ -447,7 +449,7 @@ class BaseAligner:
         n_reads = offsets.size - 1
         cap = text.size if text is not None else (int(capacity) if capacity is not None else 2 * int(bases.size) + 256 * n_rec + 64)
         line_begin = np.zeros(n_rec + 1, np.uint64)
-        f = self.lib.snapgpu_sam_text_single
+        f = getattr(self.lib, _fn)
         f.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3
         while True:
             if text is None or text.size != cap:
@@ -459,26 +461,27 @@ class BaseAligner:
                 cap = int(tb.value)
                 continue
             if rc != W_TEXT_TRUNCATED:
-                self._check(rc, "snapgpu_sam_text_single")
+                self._check(rc, _fn)
             return dict(text=text, line_begin=line_begin, text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED)
 
     def samText_device(self, n_records: int, d_bases: int, d_quals: int, d_offsets: int, d_names: int, d_name_off: int, d_rec_read: int, d_flag: int,
                        d_contig: int, d_pos: int, d_mapq: int, d_ops: int, ops_stride: int, d_n_ops: int, d_nm: int, capacity: int, d_text: int,
-                       d_line_begin: int, stream: int = 0):
+                       d_line_begin: int, stream: int = 0, _fn: str = "snapgpu_sam_text_single_device"):
         """Device-pointer form of samText (snapgpu_sam_text_single_device): every array in HBM (d_rec_read 0: record i is read i), the text
         and line_begin left there.  Synchronous on `stream` (0: the context's).  Returns (text_bytes, truncated)."""
         vp = lambda x: C.c_void_p(x) if x else None
-        f = self.lib.snapgpu_sam_text_single_device
+        f = getattr(self.lib, _fn)
         f.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11 + [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4
         tb = C.c_uint64(0)
         rc = f(self.handle, n_records, vp(d_bases), vp(d_quals), vp(d_offsets), vp(d_names), vp(d_name_off), vp(d_rec_read), vp(d_flag), vp(d_contig), vp(d_pos),
                vp(d_mapq), vp(d_ops), ops_stride, vp(d_n_ops), vp(d_nm), capacity, vp(d_text), vp(d_line_begin), C.addressof(tb), vp(stream))
         if rc != W_TEXT_TRUNCATED:
-            self._check(rc, "snapgpu_sam_text_single_device")
+            self._check(rc, _fn)
         return int(tb.value), rc == W_TEXT_TRUNCATED
 
     def alignSamText(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
-                     adjust_primary: bool = False, capacity: int | None = None, text_capacity: int | None = None, grow: bool = True):
+                     adjust_primary: bool = False, capacity: int | None = None, text_capacity: int | None = None, grow: bool = True,
+                     _fn: str = "snapgpu_align_sam_single_text"):
         """Single-end reads to the text of all their SAM records in one call (snapgpu_align_sam_single_text): alignSamRecords' inputs plus the
         reads' names; capacity / text_capacity: records / bytes to make room for (defaults: estimates); grow: call again with what the
         library asks for when one was too small.  Returns dict(text, line_begin, text_bytes, truncated, n_records, records_truncated,
@@ -492,7 +495,7 @@ class BaseAligner:
         cap = int(capacity) if capacity is not None else n + n // 2 + 16
         tcap = int(text_capacity) if text_capacity is not None else 3 * int(bases.size) + 256 * cap + 64
         rec_begin = np.zeros(n + 1, np.uint64)
-        f = self.lib.snapgpu_align_sam_single_text
+        f = getattr(self.lib, _fn)
         f.argtypes = ([C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 3 +
                       [C.c_uint64] + [C.c_void_p] * 3)
         while True:
@@ -507,11 +510,51 @@ class BaseAligner:
                 tcap = int(tb.value)
                 continue
             if rc not in (W_RECORDS_TRUNCATED, W_TEXT_TRUNCATED):
-                self._check(rc, "snapgpu_align_sam_single_text")
+                self._check(rc, _fn)
             break
         m = min(int(n_rec.value), cap)
         return dict(text=text, line_begin=line_begin[:m + 1], text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED, n_records=int(n_rec.value),
                     records_truncated=rc == W_RECORDS_TRUNCATED, rec_begin=rec_begin, flag=flag[:m])
+
+    # ---- records -> the bytes of their BAM records (BAMFormat::writeRead) ----
+    def setContigBamIds(self, ref_id=None, n_contigs: int | None = None):
+        """snapgpu_set_contig_bam_ids: the BAM reference number of contig c is ref_id[c] (int32, one per contig of the index); None: contig c
+        is number c (n_contigs: the index's count, for an aligner that has no GenomeIndex of its own)."""
+        f = self.lib.snapgpu_set_contig_bam_ids
+        f.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        if ref_id is None:
+            self._check(f(self.handle, len(self.index.contigs) if n_contigs is None else int(n_contigs), None), "snapgpu_set_contig_bam_ids")
+            return
+        ids = np.ascontiguousarray(ref_id, dtype=np.int32)
+        self._check(f(self.handle, ids.size, ptr(ids) if ids.size else None), "snapgpu_set_contig_bam_ids")
+
+    @staticmethod
+    def _as_bam(d):
+        """a text call's dict under the BAM calls' names"""
+        d["bytes"] = d.pop("text"); d["block_begin"] = d.pop("line_begin"); d["bam_bytes"] = d.pop("text_bytes")
+        return d
+
+    def bamRecords(self, bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rec_read=None, capacity: int | None = None,
+                   grow: bool = True, bytes_out=None):
+        """The uncompressed BAM records of a batch's records (snapgpu_bam_records_single): samText's arguments (bytes_out: a uint8 array to
+        write into).  Returns dict(bytes uint8[capacity], block_begin uint64[n_records + 1], bam_bytes, truncated)."""
+        return self._as_bam(self.samText(bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rec_read=rec_read, capacity=capacity,
+                                         grow=grow, text=bytes_out, _fn="snapgpu_bam_records_single"))
+
+    def bamRecords_device(self, n_records: int, d_bases: int, d_quals: int, d_offsets: int, d_names: int, d_name_off: int, d_rec_read: int, d_flag: int,
+                          d_contig: int, d_pos: int, d_mapq: int, d_ops: int, ops_stride: int, d_n_ops: int, d_nm: int, capacity: int, d_bytes: int,
+                          d_block_begin: int, stream: int = 0):
+        """Device-pointer form of bamRecords (snapgpu_bam_records_single_device), as samText_device.  Returns (bam_bytes, truncated)."""
+        return self.samText_device(n_records, d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride,
+                                   d_n_ops, d_nm, capacity, d_bytes, d_block_begin, stream, _fn="snapgpu_bam_records_single_device")
+
+    def alignSamBam(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
+                    adjust_primary: bool = False, capacity: int | None = None, byte_capacity: int | None = None, grow: bool = True):
+        """Single-end reads to the BAM records of all their SAM records in one call (snapgpu_align_sam_single_bam), as alignSamText.  Returns
+        dict(bytes, block_begin, bam_bytes, truncated, n_records, records_truncated, rec_begin, flag)."""
+        return self._as_bam(self.alignSamText(bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m=use_m, ops_stride=ops_stride,
+                                              adjust_primary=adjust_primary, capacity=capacity, text_capacity=byte_capacity, grow=grow,
+                                              _fn="snapgpu_align_sam_single_bam"))
 
     def samFieldsPaired(self, bases, quals, offsets, front_clip, data_len, results, use_m: bool = False, ops_stride: int = 64):
         """SAMFormat::writePairs + fillMateInfo up to the point of printing (see snapgpu_sam_fields_paired).  offsets has 2 n + 1
@@ -732,7 +775,7 @@ class ChimericPairedEndAligner(BaseAligner):
 
     # ---- pair units -> the bytes of their SAM lines (SAMFormat::writePairs' printed lines) ----
     def samTextPaired(self, bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rnext, pnext, tlen, first_written,
-                      unit_pair=None, capacity: int | None = None, grow: bool = True, text=None):
+                      unit_pair=None, capacity: int | None = None, grow: bool = True, text=None, _fn: str = "snapgpu_sam_text_paired"):
         """The SAM lines of a batch's pair units (snapgpu_sam_text_paired): bases / quals / offsets (2 n_pairs + 1 entries) the unclipped
         mates, names / name_off (uint64[2 n_pairs + 1]) their names, flag .. tlen the fields of both mates of every unit as samFieldsPaired /
         alignSamPaired return them ([2 n_units]; ops: [2 n_units, ops_stride]), first_written [n_units]; unit_pair: the pair of each unit
@@ -755,7 +798,7 @@ class ChimericPairedEndAligner(BaseAligner):
         n_pairs = (offsets.size - 1) // 2
         cap = text.size if text is not None else (int(capacity) if capacity is not None else 4 * int(bases.size) + 600 * n_units + 64)
         line_begin = np.zeros(2 * n_units + 1, np.uint64)
-        f = self.lib.snapgpu_sam_text_paired
+        f = getattr(self.lib, _fn)
         f.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 3
         while True:
             if text is None or text.size != cap:
@@ -768,27 +811,28 @@ class ChimericPairedEndAligner(BaseAligner):
                 cap = int(tb.value)
                 continue
             if rc != W_TEXT_TRUNCATED:
-                self._check(rc, "snapgpu_sam_text_paired")
+                self._check(rc, _fn)
             return dict(text=text, line_begin=line_begin, text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED)
 
     def samTextPaired_device(self, n_units: int, d_bases: int, d_quals: int, d_offsets: int, d_names: int, d_name_off: int, d_unit_pair: int, d_flag: int,
                              d_contig: int, d_pos: int, d_mapq: int, d_ops: int, ops_stride: int, d_n_ops: int, d_nm: int, d_rnext: int, d_pnext: int,
-                             d_tlen: int, d_first_written: int, capacity: int, d_text: int, d_line_begin: int, stream: int = 0):
+                             d_tlen: int, d_first_written: int, capacity: int, d_text: int, d_line_begin: int, stream: int = 0,
+                             _fn: str = "snapgpu_sam_text_paired_device"):
         """Device-pointer form of samTextPaired (snapgpu_sam_text_paired_device): every array in HBM (d_unit_pair 0: unit i is pair i), the
         text and line_begin left there.  Synchronous on `stream` (0: the context's).  Returns (text_bytes, truncated)."""
         vp = lambda x: C.c_void_p(x) if x else None
-        f = self.lib.snapgpu_sam_text_paired_device
+        f = getattr(self.lib, _fn)
         f.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11 + [C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 4
         tb = C.c_uint64(0)
         rc = f(self.handle, n_units, vp(d_bases), vp(d_quals), vp(d_offsets), vp(d_names), vp(d_name_off), vp(d_unit_pair), vp(d_flag), vp(d_contig), vp(d_pos),
                vp(d_mapq), vp(d_ops), ops_stride, vp(d_n_ops), vp(d_nm), vp(d_rnext), vp(d_pnext), vp(d_tlen), vp(d_first_written), capacity, vp(d_text),
                vp(d_line_begin), C.addressof(tb), vp(stream))
         if rc != W_TEXT_TRUNCATED:
-            self._check(rc, "snapgpu_sam_text_paired_device")
+            self._check(rc, _fn)
         return int(tb.value), rc == W_TEXT_TRUNCATED
 
     def alignSamTextPaired(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
-                           text_capacity: int | None = None, grow: bool = True, want_results: bool = False):
+                           text_capacity: int | None = None, grow: bool = True, want_results: bool = False, _fn: str = "snapgpu_align_sam_paired_text"):
         """Paired-end reads to the text of their SAM records in one call (snapgpu_align_sam_paired_text): alignSamPaired's inputs plus the
         mates' names; text_capacity: bytes to make room for (default: an estimate); grow: call again with what the library asks for when
         that was too few.  Returns dict(text, line_begin uint64[2 n_pairs + 1], text_bytes, truncated, flag [2 n_pairs], first_written
@@ -805,7 +849,7 @@ class ChimericPairedEndAligner(BaseAligner):
         tcap = int(text_capacity) if text_capacity is not None else 3 * int(bases.size) + 300 * n + 64
         results = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
         first_alt = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
-        f = self.lib.snapgpu_align_sam_paired_text
+        f = getattr(self.lib, _fn)
         f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 3
         while True:
             flag = np.zeros(n, np.int32); first = np.zeros(npairs, np.int32); line_begin = np.zeros(n + 1, np.uint64); text = np.zeros(tcap, np.uint8)
@@ -817,10 +861,33 @@ class ChimericPairedEndAligner(BaseAligner):
                 tcap = int(tb.value)
                 continue
             if rc != W_TEXT_TRUNCATED:
-                self._check(rc, "snapgpu_align_sam_paired_text")
+                self._check(rc, _fn)
             break
         return dict(text=text, line_begin=line_begin, text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED, flag=flag, first_written=first,
                     results=results, first_alt=first_alt)
+
+    # ---- pair units -> the bytes of their BAM records (BAMFormat::writePairs) ----
+    def bamRecordsPaired(self, bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rnext, pnext, tlen, first_written,
+                         unit_pair=None, capacity: int | None = None, grow: bool = True, bytes_out=None):
+        """The uncompressed BAM records of a batch's pair units (snapgpu_bam_records_paired): samTextPaired's arguments.  Returns dict(bytes
+        uint8[capacity], block_begin uint64[2 n_units + 1], bam_bytes, truncated); records 2 u and 2 u + 1 are unit u's, in file order."""
+        return self._as_bam(self.samTextPaired(bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rnext, pnext, tlen, first_written,
+                                               unit_pair=unit_pair, capacity=capacity, grow=grow, text=bytes_out, _fn="snapgpu_bam_records_paired"))
+
+    def bamRecordsPaired_device(self, n_units: int, d_bases: int, d_quals: int, d_offsets: int, d_names: int, d_name_off: int, d_unit_pair: int, d_flag: int,
+                                d_contig: int, d_pos: int, d_mapq: int, d_ops: int, ops_stride: int, d_n_ops: int, d_nm: int, d_rnext: int, d_pnext: int,
+                                d_tlen: int, d_first_written: int, capacity: int, d_bytes: int, d_block_begin: int, stream: int = 0):
+        """Device-pointer form of bamRecordsPaired (snapgpu_bam_records_paired_device), as samTextPaired_device.  Returns (bam_bytes, truncated)."""
+        return self.samTextPaired_device(n_units, d_bases, d_quals, d_offsets, d_names, d_name_off, d_unit_pair, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride,
+                                         d_n_ops, d_nm, d_rnext, d_pnext, d_tlen, d_first_written, capacity, d_bytes, d_block_begin, stream,
+                                         _fn="snapgpu_bam_records_paired_device")
+
+    def alignSamBamPaired(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
+                          byte_capacity: int | None = None, grow: bool = True, want_results: bool = False):
+        """Paired-end reads to the BAM records of their SAM records in one call (snapgpu_align_sam_paired_bam), as alignSamTextPaired.  Returns
+        dict(bytes, block_begin uint64[2 n_pairs + 1], bam_bytes, truncated, flag, first_written, results, first_alt)."""
+        return self._as_bam(self.alignSamTextPaired(bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m=use_m, ops_stride=ops_stride,
+                                                    text_capacity=byte_capacity, grow=grow, want_results=want_results, _fn="snapgpu_align_sam_paired_bam"))
 
     def align_secondary(self, bases: np.ndarray, quals: np.ndarray, offsets: np.ndarray, stride: int = 8, single_stride: int = 16):
         """ChimericPairedEndAligner::align with secondary results (after enable_secondary(...)): returns

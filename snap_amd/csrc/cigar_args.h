@@ -132,6 +132,13 @@ struct SamTextPairedArgs : SamTextArgs {
     int32_t *qs;                                                                 // [n] k_samtext_qs: qs[2 u + v] = QS of mate v of unit u's pair, which the OTHER mate's line prints
 };
 extern "C" void snapgpu_launch_sam_text_paired(const SamTextPairedArgs *a, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s);
+// snapgpu_bam_records_single* / _paired*: records -> the bytes of their BAM records (sam_bam.h).  The arrays of the text calls, single end (the
+// pair members NULL) or pair units; `text` is the record bytes, `line_begin` block_begin, len[r] = 4 + block_size.
+#define SAMBAM_LONG_NAME 4u         // a QNAME longer than 254 after the cut: the call is refused (summary->pad: ~ the first such record)
+struct SamBamArgs : SamTextPairedArgs {
+    const int32_t *ref_id;                                                       // [n_contigs] snapgpu_set_contig_bam_ids: the BAM number of each contig
+};
+extern "C" void snapgpu_launch_sam_bam(const SamBamArgs *a, int paired, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_count(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_list(const SamRecArgs *a, uint32_t blocks, hipStream_t s);

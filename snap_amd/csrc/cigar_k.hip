@@ -1,7 +1,7 @@
 // cigar_k.hip -- the SAM writer's kernels, one wavefront per item on a persistent grid: SAMFormat::computeCigar for a batch of written reads
 // (k_cigar_lv, k_cigar_ag), result -> SAM fields (k_sam_fields*: one body, sam_fields_run, over the reads of a batch, the records of a record
 // list or the mates of a paired batch, with the pre-pass k_samf_dp8* ahead of it), AlignmentAdjuster (k_adjust_alignments) and the launches
-// of the record-list kernels (sam_records.h) and of the SAM-line kernels (sam_text.h).
+// of the record-list kernels (sam_records.h), of the SAM-line kernels (sam_text.h) and of the BAM-record kernels (sam_bam.h).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -c cigar_k.hip
 #include <hip/hip_runtime.h>
 #include "cigar_lv.h"
@@ -11,6 +11,7 @@
 #include "cigar_args.h"
 #include "sam_records.h"
 #include "sam_text.h"
+#include "sam_bam.h"
 
 __global__ __launch_bounds__(256) void k_cigar_lv(CigarArgs a)
 {
@@ -542,4 +543,19 @@ extern "C" void snapgpu_launch_sam_text_paired(const SamTextPairedArgs *a, uint3
     hipLaunchKernelGGL(k_samtext_partials, dim3(1), dim3(64), 0, s, base);
     hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, base);
     hipLaunchKernelGGL(k_samtext_pair_write, dim3(write_blocks), dim3(256), 0, s, *a);
+}
+
+// ---- records -> the bytes of their BAM records (sam_bam.h): lengths, sam_text.h's scan, the records that fit the capacity; pairs: QS first ---
+extern "C" void snapgpu_launch_sam_bam(const SamBamArgs *a, int paired, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s)
+{
+    const SamTextArgs &base = *a;
+    const SamTextPairedArgs &pbase = *a;
+    if (paired) {
+        hipLaunchKernelGGL(k_samtext_qs, dim3(write_blocks), dim3(256), 0, s, pbase);
+        hipLaunchKernelGGL(k_sambam_pair_len, dim3(scan_blocks), dim3(256), 0, s, *a);
+    } else hipLaunchKernelGGL(k_sambam_len, dim3(scan_blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samtext_partials, dim3(1), dim3(64), 0, s, base);
+    hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, base);
+    if (paired) hipLaunchKernelGGL(k_sambam_pair_write, dim3(write_blocks), dim3(256), 0, s, *a);
+    else hipLaunchKernelGGL(k_sambam_write, dim3(write_blocks), dim3(256), 0, s, *a);
 }

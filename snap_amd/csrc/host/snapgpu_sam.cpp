@@ -515,6 +515,7 @@ struct FeederCtx {
     snapgpu_ctx *owner = NULL; int device = 0;                             // whose index blobs they share
 };
 static uint32_t class_len(const Options &o, int k) { return RL_CLASS[k] && RL_CLASS[k] < o.p.max_read_len ? RL_CLASS[k] : o.p.max_read_len; }
+static bool device_bam_switch(const Options &o);
 static void configure_ctx(const Options &o, snapgpu_ctx *c)
 {
     snapgpu_set_aligner_flags(c, o.stop_on_first_hit ? 1 : 0, o.explore_popular_seeds ? 1 : 0);      // -f, -x (single-end launches only)
@@ -522,6 +523,11 @@ static void configure_ctx(const Options &o, snapgpu_ctx *c)
         std::vector<const char *> names; for (const Contig &ct : *g_contigs) names.push_back(ct.name.c_str());
         int rc = snapgpu_set_contig_names(c, (uint32_t)names.size(), names.data());
         if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_set_contig_names failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); }
+    }
+    if (device_bam_switch(o)) {   // refID of the BAM-record kernels: the contigs' original numbers, which order the header's reference table (main checks that they are a permutation)
+        std::vector<int32_t> ids; for (const Contig &ct : *g_contigs) ids.push_back(ct.orig);
+        int rc = snapgpu_set_contig_bam_ids(c, (uint32_t)ids.size(), ids.data());
+        if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_set_contig_bam_ids failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); }
     }
     if (o.paired) { int rc = snapgpu_enable_paired(c, &o.pp); if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_enable_paired failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); } }
     if (o.om >= 0) {
@@ -586,6 +592,18 @@ static bool device_text_paired_path(const Options &o)
     static const bool on = getenv("SNAPGPU_SAM_DEVICE_TEXT") && atoi(getenv("SNAPGPU_SAM_DEVICE_TEXT")) != 0;
     return on && o.paired && !o.bam && o.om < 0;
 }
+// SNAPGPU_SAM_DEVICE_BAM=1: the same two paths for BAM output -- the uncompressed RECORDS of a batch come from the device
+// (snapgpu_align_sam_single_bam, every option set; snapgpu_align_sam_paired_bam, no -om, first-ALT batches through the host path) and the
+// formatter threads only compress them.  A switch of its own: SNAPGPU_SAM_DEVICE_TEXT keeps ignoring BAM.  Off unless asked for (DESIGN.md
+// section 13); SAM output ignores it.  The file is the same bytes either way (tests/test_zz_gpu_sam_bam.py).
+static bool device_bam_switch(const Options &o)
+{
+    static const bool on = getenv("SNAPGPU_SAM_DEVICE_BAM") && atoi(getenv("SNAPGPU_SAM_DEVICE_BAM")) != 0;
+    return on && o.bam;
+}
+static bool device_bam_path(const Options &o) { return device_bam_switch(o) && !o.paired; }
+static bool device_bam_paired_path(const Options &o) { return device_bam_switch(o) && o.paired && o.om < 0; }
+static std::atomic<unsigned long long> g_bam_batches(0), g_bam_records(0);      // what the device-BAM paths produced (the line on stderr at the end)
 static std::atomic<uint32_t> g_text_extra_per_record(128);      // text capacity of the next call: bytes per record beyond its name, SEQ and QUAL; grows to what batches have needed
 static std::atomic<uint32_t> g_records_per_read_x16(24);        // record capacity of the next call, in sixteenths of a record per read: grows to what batches have needed
 
@@ -596,7 +614,7 @@ static void prepare_single(const Options &o, Work &w)
     const Batch &b = w.b;
     const size_t n = b.n();
     w.front_clip.assign(n, 0); w.data_len.assign(n, 0); w.skip.assign(n, 1); w.to_align.clear(); w.ab.clear(); w.aq.clear(); w.ao.assign(1, 0);
-    const bool fused = (o.om < 0 && !o.ae) || single_records_path(o) || device_text_path(o);      // gpu_single's one-call paths work on the batch itself: nothing to gather
+    const bool fused = (o.om < 0 && !o.ae) || single_records_path(o) || device_text_path(o) || device_bam_path(o);      // gpu_single's one-call paths work on the batch itself: nothing to gather
     if (!fused) { w.ab.reserve(b.bases.size()); w.aq.reserve(b.quals.size()); w.ao.reserve(n + 1); }
     w.to_align.reserve(n);
     w.max_len = 0;
@@ -614,7 +632,8 @@ static void prepare_single(const Options &o, Work &w)
 }
 
 static bool g_index_has_alt = false;        // the index has ALT contigs: only then can a first-ALT result (an extra record) exist
-// SNAPGPU_SAM_DEVICE_TEXT: the batch goes up as it was parsed, with its names, and its SAM lines come down.  Both capacities start from an
+// SNAPGPU_SAM_DEVICE_TEXT / SNAPGPU_SAM_DEVICE_BAM: the batch goes up as it was parsed, with its names, and its SAM lines (BAM output: its
+// uncompressed BAM records, which are shorter than the lines, so the same estimate has room for them) come down.  Both capacities start from an
 // estimate and follow what the library reports; a cigar that outgrows its row is met with a larger row, as with_growing_stride does.
 static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
 {
@@ -635,9 +654,13 @@ static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
     lap(g_ns_prep);
     for (;;) {
         w.flag.resize(cap); line_begin.resize(cap + 1); w.text.resize(tcap);
-        const int rc = snapgpu_align_sam_single_text(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
-                                                     w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
-                                                     (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
+        const int rc = o.bam
+            ? snapgpu_align_sam_single_bam(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
+                                           w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
+                                           (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), (uint64_t)tcap, (uint8_t *)&w.text[0], line_begin.data(), &text_bytes)
+            : snapgpu_align_sam_single_text(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
+                                            w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
+                                            (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
         if (rc == SNAPGPU_E_UNSUPPORTED && o.ae && !strncmp(snapgpu_last_error(ctx), "-ae:", 4))
             die("-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)");
         if (rc == SNAPGPU_W_RECORDS_TRUNCATED) { cap = (size_t)n_rec + (size_t)n_rec / 16; tcap = cap * (per_read + g_text_extra_per_record.load()); continue; }
@@ -646,10 +669,11 @@ static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
             if (ops_stride >= 4096) die("a cigar needs more than 4096 operations");
             ops_stride *= 4; continue;
         }
-        if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_single_text", rc);
+        if (rc != SNAPGPU_OK) fail_rc(ctx, o.bam ? "snapgpu_align_sam_single_bam" : "snapgpu_align_sam_single_text", rc);
         break;
     }
     const size_t nr = (size_t)n_rec;
+    if (o.bam) { g_bam_batches++; g_bam_records += nr; }
     { const uint32_t need = (uint32_t)((nr * 16 + n - 1) / n) + 2; uint32_t cur = g_records_per_read_x16.load(); while (need > cur && !g_records_per_read_x16.compare_exchange_weak(cur, need)) {} }
     if (nr) { const size_t per_rec = ((size_t)text_bytes + nr - 1) / nr; const uint32_t need = per_rec > per_read ? (uint32_t)(per_rec - per_read) + 16 : 16;
               uint32_t cur = g_text_extra_per_record.load(); while (need > cur && !g_text_extra_per_record.compare_exchange_weak(cur, need)) {} }
@@ -871,7 +895,7 @@ struct GroupBuf {
 };
 static void gpu_single_group(const Options &o, FeederCtx &fc, std::vector<Work *> &ws, GroupBuf &g)
 {
-    if (device_text_path(o)) { for (Work *w : ws) gpu_single_text(o, fc, *w); return; }
+    if (device_text_path(o) || device_bam_path(o)) { for (Work *w : ws) gpu_single_text(o, fc, *w); return; }
     const bool fusable = o.om < 0 && !o.ae && !single_records_path(o);
     if (ws.size() == 1 || !fusable) { for (Work *w : ws) gpu_single(o, fc, *w); return; }
     auto t_stage = std::chrono::steady_clock::now();
@@ -953,7 +977,7 @@ static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
         };
         // SNAPGPU_SAM_DEVICE_TEXT: the batch goes up as it was parsed, with its names, and the lines of its pairs come down (as gpu_single_text: the
         // capacity follows what the library reports, a cigar that outgrows its row is met with a larger row)
-        if (device_text_paired_path(o)) {
+        if (device_text_paired_path(o) || device_bam_paired_path(o)) {
             std::vector<uint64_t> name_off(b.name_off.begin(), b.name_off.end()), line_begin(nrec + 1);
             const size_t per_read = (2 * b.bases.size() + b.names.size() + nrec - 1) / nrec;       // name, SEQ and QUAL of the average record
             size_t tcap = nrec * (per_read + g_text_extra_per_record.load());
@@ -962,16 +986,21 @@ static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
             w.flag.assign(nrec, 0); w.first_written.assign(np, 0);
             for (;;) {
                 w.text.resize(tcap);
-                const int rc = snapgpu_align_sam_paired_text(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
-                                                             skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
-                                                             want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
-                                                             (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
+                const int rc = o.bam
+                    ? snapgpu_align_sam_paired_bam(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
+                                                   skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
+                                                   want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
+                                                   (uint64_t)tcap, (uint8_t *)&w.text[0], line_begin.data(), &text_bytes)
+                    : snapgpu_align_sam_paired_text(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
+                                                    skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
+                                                    want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
+                                                    (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
                 if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; continue; }
                 if (rc == SNAPGPU_E_INVALID && strstr(snapgpu_last_error(ctx), "ops_stride")) {
                     if (ops_stride >= 4096) die("a cigar needs more than 4096 operations");
                     ops_stride *= 4; continue;
                 }
-                if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_paired_text", rc);
+                if (rc != SNAPGPU_OK) fail_rc(ctx, o.bam ? "snapgpu_align_sam_paired_bam" : "snapgpu_align_sam_paired_text", rc);
                 break;
             }
             if (!first_alt_pair()) {
@@ -979,6 +1008,7 @@ static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
                   uint32_t cur = g_text_extra_per_record.load(); while (need > cur && !g_text_extra_per_record.compare_exchange_weak(cur, need)) {} }
                 w.text.resize((size_t)text_bytes); w.text_done = true; w.mapped = 0;
                 for (size_t r = 0; r < nrec; r++) w.mapped += (w.flag[r] & 0x4) == 0;
+                if (o.bam) { g_bam_batches++; g_bam_records += nrec; }
                 return;
             }
             w.text.clear();                                             // (rare: a first-ALT pair to write -- the batch goes through the calls below)
@@ -1552,6 +1582,7 @@ int main(int argc, char **argv)
     std::vector<double> pass_s;
     WorkPool pool(256);
     for (int pass = 0; pass < o.passes; pass++) {
+        g_bam_batches = 0; g_bam_records = 0;
     total = 0; mapped = 0;
     if (pass > 0) (void)unlink(out_path.c_str());        // (-passes: the previous pass's output goes BEFORE this pass is timed -- replacing a 5.6 GB file at the end of a pass
                                                          //  cost it 1.3 s of page-cache work that streaming a FASTQ file into a new SAM file does not have: profiles/r06j)
@@ -1740,6 +1771,8 @@ int main(int argc, char **argv)
     }
     for (size_t g = primary.size(); g-- > 0;) snapgpu_destroy(primary[g]);
     fprintf(stderr, "snapgpu-sam: %llu reads, %llu mapped records, %d GPU(s) x %d feeder(s), %d formatter thread(s)\n", total, mapped, o.n_gpus, o.ctx_per_gpu, o.n_format);
+    if (device_bam_switch(o) && (!o.paired || o.om < 0))                     // (the last pass's, like the counts above)
+        fprintf(stderr, "snapgpu-sam: BAM records from the device: %llu batches, %llu records\n", g_bam_batches.load(), g_bam_records.load());
     {   // (AlignerContext.cpp:489-543 prints reads/s over the alignment phase, the index load apart: the same split here)
         const double s_stream = pass_s.back();                              // (the last pass; with -passes N each pass printed its own line above)
         fprintf(stderr, "snapgpu-sam: index resident after %.2f s; FASTQ -> %s in %.2f s = %.0f reads/s (%s reader, %d parser thread(s))\n", s_load, o.bam ? "BAM" : "SAM", s_stream,

@@ -422,6 +422,7 @@ struct snapgpu_ctx {
     std::vector<uint64_t> h_table_offset, h_table_size, h_contig_begin, h_proj_begin;
     std::vector<uint8_t> h_proj_rc; std::vector<uint32_t> h_cigar_start, h_cigar_ops;
     uint8_t *d_contig_names = nullptr; uint32_t *d_contig_name_off = nullptr;      // snapgpu_set_contig_names: RNAME of the SAM-line kernels (sam_text.h)
+    int32_t *d_contig_bam_id = nullptr;                                            // snapgpu_set_contig_bam_ids: refID of the BAM-record kernels (sam_bam.h)
     std::string err;
 };
 
@@ -578,6 +579,7 @@ extern "C" void snapgpu_destroy(snapgpu_ctx *ctx) {
     if (ctx->d_whist) (void)hipFree(ctx->d_whist);
     if (ctx->d_contig_names) (void)hipFree(ctx->d_contig_names);
     if (ctx->d_contig_name_off) (void)hipFree(ctx->d_contig_name_off);
+    if (ctx->d_contig_bam_id) (void)hipFree(ctx->d_contig_bam_id);
     ctx->pool.free_all();
     if (ctx->d_work) (void)hipFree(ctx->d_work);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
@@ -2735,6 +2737,27 @@ extern "C" int snapgpu_set_contig_names(snapgpu_ctx *ctx, uint32_t n_contigs, co
     return SNAPGPU_OK;
 }
 
+// the BAM reference number of each contig of the index (Bam.cpp:1003-1021: the header lists the contigs in the FASTA's order); NULL: contig c is number c
+extern "C" int snapgpu_set_contig_bam_ids(snapgpu_ctx *ctx, uint32_t n_contigs, const int32_t *ref_id)
+{
+    if (!ctx) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_set_contig_bam_ids: null argument");
+    if (n_contigs != ctx->ix.n_contigs)
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_set_contig_bam_ids: " + std::to_string(n_contigs) + " numbers for an index of " + std::to_string(ctx->ix.n_contigs) + " contigs");
+    std::vector<int32_t> ids((size_t)n_contigs);
+    for (uint32_t i = 0; i < n_contigs; i++) ids[i] = ref_id ? ref_id[i] : (int32_t)i;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), SNAPGPU_E_LAUNCH);
+    if (ctx->d_contig_bam_id) { (void)hipFree(ctx->d_contig_bam_id); ctx->d_contig_bam_id = nullptr; }
+    void *d_ids = nullptr;
+    HIPCHK(ctx, hipMalloc(&d_ids, ids.size() * 4 + 16), SNAPGPU_E_NOMEM);
+    if (n_contigs && hipMemcpy(d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d_ids);
+        return fail(ctx, SNAPGPU_E_LAUNCH, "snapgpu_set_contig_bam_ids: hipMemcpy");
+    }
+    ctx->d_contig_bam_id = (int32_t *)d_ids;
+    return SNAPGPU_OK;
+}
+
 // What the three text calls share once every array is in HBM: the length pass, the scan, the write pass (sam_text.h), all on the call's
 // stream, and the summary read back -- the stream is synchronised when this returns.  n_records > 0.
 struct SamTextIO {
@@ -2742,18 +2765,23 @@ struct SamTextIO {
     const void *flag, *contig, *pos, *mapq, *ops; uint32_t ops_stride; const void *n_ops, *nm;
     uint64_t cap; void *text, *line_begin;
 };
-static int sam_text_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_records, uint32_t ops_stride)
+// (bam: the same calls over the BAM-record kernels, sam_bam.h -- `text` is then the record bytes, line_begin block_begin, and the contigs'
+// BAM numbers are needed in place of their names)
+static int sam_text_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_records, uint32_t ops_stride, bool bam = false)
 {
-    if (!ctx->d_contig_names) return fail(ctx, SNAPGPU_E_INVALID, w + ": no contig names (call snapgpu_set_contig_names first)");
+    if (bam && !ctx->d_contig_bam_id) return fail(ctx, SNAPGPU_E_INVALID, w + ": no contig BAM numbers (call snapgpu_set_contig_bam_ids first)");
+    if (!bam && !ctx->d_contig_names) return fail(ctx, SNAPGPU_E_INVALID, w + ": no contig names (call snapgpu_set_contig_names first)");
     if (ops_stride == 0) return fail(ctx, SNAPGPU_E_INVALID, w + ": ops_stride must not be 0");
     if (n_records > 0xFFFFFFFFull - SAMREC_CHUNK) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^32 - 1 records in one call");
     return SNAPGPU_OK;
 }
 // the arrays only pair lines have (snapgpu_sam_text_paired*): with them n_records counts LINES, two per pair unit, and io.rec_read is unit_pair
 struct SamTextPairIO { const void *rnext, *pnext, *tlen, *first_written; };
-static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, const SamTextIO &io, SamTextSummary *sum, const SamTextPairIO *pair = nullptr)
+static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, const SamTextIO &io, SamTextSummary *sum, const SamTextPairIO *pair = nullptr,
+                         bool bam = false)
 {
-    SamTextPairedArgs a; memset(&a, 0, sizeof(a));
+    SamBamArgs a; memset(&a, 0, sizeof(a));
+    a.ref_id = ctx->d_contig_bam_id;
     a.n = (uint32_t)n_records; a.n_chunks = (uint32_t)((n_records + SAMREC_CHUNK - 1) / SAMREC_CHUNK); a.ops_stride = io.ops_stride; a.n_contigs = ctx->ix.n_contigs;
     a.bases = (const uint8_t *)io.bases; a.quals = (const uint8_t *)io.quals; a.offsets = (const uint64_t *)io.offsets;
     a.names = (const uint8_t *)io.names; a.name_off = (const uint64_t *)io.name_off; a.rec_read = (const uint32_t *)io.rec_read;
@@ -2772,7 +2800,8 @@ static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint
     { const uint32_t need = (a.n + 3) / 4; if (write_blocks > need) write_blocks = need; }
     HIPCHK(ctx, hipMemsetAsync(a.summary, 0, sizeof(SamTextSummary), st.s), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
-    if (pair) snapgpu_launch_sam_text_paired(&a, scan_blocks, write_blocks, st.s);
+    if (bam) snapgpu_launch_sam_bam(&a, pair ? 1 : 0, scan_blocks, write_blocks, st.s);
+    else if (pair) snapgpu_launch_sam_text_paired(&a, scan_blocks, write_blocks, st.s);
     else snapgpu_launch_sam_text(&a, scan_blocks, write_blocks, st.s);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
     HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
@@ -2783,6 +2812,8 @@ static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint
     if (sum->flags & SAMTEXT_BAD_RECORD)
         return fail(ctx, SNAPGPU_E_INVALID, w + (pair ? ": a record has more cigar operations than ops_stride, a contig or an rnext the index does not have, or a first_written that is neither 0 nor 1"
                                                       : ": a record has more cigar operations than ops_stride, or a contig the index does not have"));
+    if (sum->flags & SAMBAM_LONG_NAME)                                   // (Bam.cpp:1394-1397 / 1127-1130: l_read_name is one byte)
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": record " + std::to_string(~sum->pad) + ": QNAME must be shorter than 255 characters in a BAM record");
     return SNAPGPU_OK;
 }
 // no records: line_begin[0] = 0 and no text (the device form writes the word in HBM)
@@ -2797,16 +2828,16 @@ static int sam_text_empty(snapgpu_ctx *ctx, bool host, void *line_begin, uint64_
     return SNAPGPU_OK;
 }
 
-extern "C" int snapgpu_sam_text_single_device(snapgpu_ctx *ctx, uint64_t n_records, const void *d_bases, const void *d_quals, const void *d_offsets,
+static int sam_text_single_device_call(snapgpu_ctx *ctx, const char *who, bool bam, uint64_t n_records, const void *d_bases, const void *d_quals, const void *d_offsets,
                                               const void *d_names, const void *d_name_off, const void *d_rec_read, const void *d_flag, const void *d_contig,
                                               const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
                                               uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
 {
-    const std::string w = "snapgpu_sam_text_single_device";
+    const std::string w(who);
     if (!ctx || !text_bytes || !d_line_begin || (text_capacity && !d_text) ||
         (n_records && (!d_bases || !d_quals || !d_offsets || !d_names || !d_name_off || !d_flag || !d_contig || !d_pos || !d_mapq || !d_ops || !d_n_ops || !d_nm)))
         return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    int rc = sam_text_check(ctx, w, n_records, ops_stride);
+    int rc = sam_text_check(ctx, w, n_records, ops_stride, bam);
     if (rc) return rc;
     if (n_records == 0) return sam_text_empty(ctx, false, d_line_begin, text_bytes, stream);
     HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
@@ -2814,21 +2845,21 @@ extern "C" int snapgpu_sam_text_single_device(snapgpu_ctx *ctx, uint64_t n_recor
     const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
                        text_capacity, d_text, d_line_begin};
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, n_records, io, &sum))) return rc;
+    if ((rc = sam_text_core(ctx, w, st, n_records, io, &sum, nullptr, bam))) return rc;
     *text_bytes = sum.total;
     return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
-extern "C" int snapgpu_sam_text_single(snapgpu_ctx *ctx, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
+static int sam_text_single_call(snapgpu_ctx *ctx, const char *who, bool bam, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
                                        const char *names, const uint64_t *name_off, const uint32_t *rec_read, const int32_t *flag, const int32_t *contig,
                                        const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
                                        uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
 {
-    const std::string w = "snapgpu_sam_text_single";
+    const std::string w(who);
     if (!ctx || !text_bytes || !line_begin || (text_capacity && !text) ||
         (n_records && (!bases || !quals || !offsets || !names || !name_off || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm)))
         return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    int rc = sam_text_check(ctx, w, n_records, ops_stride);
+    int rc = sam_text_check(ctx, w, n_records, ops_stride, bam);
     if (rc) return rc;
     if (n_records == 0) return sam_text_empty(ctx, true, line_begin, text_bytes, nullptr);
     if (!rec_read && n_records != n_reads) return fail(ctx, SNAPGPU_E_INVALID, w + ": without rec_read there is one record per read (n_records == n_reads)");
@@ -2848,25 +2879,24 @@ extern "C" int snapgpu_sam_text_single(snapgpu_ctx *ctx, uint64_t n_records, uin
     io.cap = text_capacity; io.text = st.out(text, (size_t)text_capacity); io.line_begin = st.out(line_begin, ((size_t)n_records + 1) * 8);
     if (st.rc) return st.rc;
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, n_records, io, &sum))) return rc;
+    if ((rc = sam_text_core(ctx, w, st, n_records, io, &sum, nullptr, bam))) return rc;
     st.limit(io.text, (size_t)sum.written);                              // only the lines that were written come down
     if ((rc = st.download())) return rc;
     *text_bytes = sum.total;
     return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
-extern "C" int snapgpu_align_sam_single_text(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+static int align_sam_single_text_call(snapgpu_ctx *ctx, const char *who, bool bam, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
                                              const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
                                              const char *names, const uint64_t *name_off, uint32_t ops_stride,
                                              uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
                                              uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
 {
-    const char *who = "snapgpu_align_sam_single_text";
     const std::string w(who);
     if (!ctx || !n_records || !rec_begin || !line_begin || !text_bytes || (text_capacity && !text) || (record_capacity && !flag) ||
         (n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off)))
         return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    int rc = sam_text_check(ctx, w, record_capacity, ops_stride);
+    int rc = sam_text_check(ctx, w, record_capacity, ops_stride, bam);
     if (rc) return rc;
     if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, w + ": ops_stride must be at least 3");
     if (ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, w + ": a single-end context is needed (no snapgpu_enable_paired)");
@@ -2904,7 +2934,7 @@ extern "C" int snapgpu_align_sam_single_text(snapgpu_ctx *ctx, uint32_t n, const
     if (f) {
         const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
                            text_capacity, d_text, d_line_begin};
-        if ((rc = sam_text_core(ctx, w, st, f, io, &sum))) return rc;
+        if ((rc = sam_text_core(ctx, w, st, f, io, &sum, nullptr, bam))) return rc;
         if (sum.flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
     } else HIPCHK(ctx, hipMemsetAsync(d_line_begin, 0, 8, st.s), SNAPGPU_E_LAUNCH);
     // ---- one download: rec_begin, the flags and line offsets of the formatted records, the lines that were written
@@ -2988,7 +3018,7 @@ extern "C" int snapgpu_sam_fields_paired_device(snapgpu_ctx *ctx, uint32_t n_pai
 // round trip of the results.
 // (`text`, snapgpu_align_sam_paired_text: the fields but flag and first_written stay in HBM -- a NULL output is a device-only buffer -- and the
 // lines of the batch's pairs follow them, with the names uploaded beside the batch and the lines that were written in the one download)
-struct PairedTextOut { const char *names; const uint64_t *name_off; uint64_t cap; char *text; uint64_t *line_begin; uint64_t *text_bytes; };
+struct PairedTextOut { const char *names; const uint64_t *name_off; uint64_t cap; char *text; uint64_t *line_begin; uint64_t *text_bytes; bool bam; };
 static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
                                  const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
                                  snapgpu_paired_result *results, snapgpu_paired_result *first_alt,
@@ -3001,7 +3031,7 @@ static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_p
     if (!ctx->paired || ctx->secondary)
         return fail(ctx, SNAPGPU_E_INVALID, w + ": a paired-end context without secondary results is needed (snapgpu_enable_paired, no snapgpu_enable_secondary)");
     if (text) {
-        if (const int rc = sam_text_check(ctx, w, 2 * (uint64_t)n_pairs, ops_stride)) return rc;
+        if (const int rc = sam_text_check(ctx, w, 2 * (uint64_t)n_pairs, ops_stride, text->bam)) return rc;
         *text->line_begin = 0; *text->text_bytes = 0;
     }
     if (n_pairs == 0) return SNAPGPU_OK;
@@ -3055,7 +3085,7 @@ static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_p
                        text->cap, d_text, d_line_begin};
     const SamTextPairIO pio{a.rnext, a.pnext, a.tlen, a.first_written};
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, n, io, &sum, &pio))) return rc;
+    if ((rc = sam_text_core(ctx, w, st, n, io, &sum, &pio, text->bam))) return rc;
     if (sum.flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
     st.limit(d_text, (size_t)sum.written);                               // only the lines that were written come down
     if ((rc = st.download())) return rc;
@@ -3088,25 +3118,25 @@ extern "C" int snapgpu_align_sam_paired_text(snapgpu_ctx *ctx, uint32_t n_pairs,
     if (!ctx || !line_begin || !text_bytes || (text_capacity && !text) ||
         (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off || !flag || !first_written)))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired_text: null argument");
-    const PairedTextOut t{names, name_off, text_capacity, text, line_begin, text_bytes};
+    const PairedTextOut t{names, name_off, text_capacity, text, line_begin, text_bytes, false};
     return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_text", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
                                  flag, nullptr, nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, &t);
 }
 
 // The two lines of each pair unit from fields in HBM (SAMFormat::writePairs' snprintf, SAM.cpp:1854-1875; QNAME: ReadWriter.cpp:405-420; QS: SAM.cpp:1826-1834)
-extern "C" int snapgpu_sam_text_paired_device(snapgpu_ctx *ctx, uint64_t n_units, const void *d_bases, const void *d_quals, const void *d_offsets,
+static int sam_text_paired_device_call(snapgpu_ctx *ctx, const char *who, bool bam, uint64_t n_units, const void *d_bases, const void *d_quals, const void *d_offsets,
                                               const void *d_names, const void *d_name_off, const void *d_unit_pair, const void *d_flag, const void *d_contig,
                                               const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
                                               const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
                                               uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
 {
-    const std::string w = "snapgpu_sam_text_paired_device";
+    const std::string w(who);
     if (!ctx || !text_bytes || !d_line_begin || (text_capacity && !d_text) ||
         (n_units && (!d_bases || !d_quals || !d_offsets || !d_names || !d_name_off || !d_flag || !d_contig || !d_pos || !d_mapq || !d_ops || !d_n_ops || !d_nm ||
                      !d_rnext || !d_pnext || !d_tlen || !d_first_written)))
         return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
     if (n_units > 0x7fffffffull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^31 - 1 pair units in one call");
-    int rc = sam_text_check(ctx, w, 2 * n_units, ops_stride);
+    int rc = sam_text_check(ctx, w, 2 * n_units, ops_stride, bam);
     if (rc) return rc;
     if (n_units == 0) return sam_text_empty(ctx, false, d_line_begin, text_bytes, stream);
     HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
@@ -3115,26 +3145,26 @@ extern "C" int snapgpu_sam_text_paired_device(snapgpu_ctx *ctx, uint64_t n_units
                        text_capacity, d_text, d_line_begin};
     const SamTextPairIO pio{d_rnext, d_pnext, d_tlen, d_first_written};
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, 2 * n_units, io, &sum, &pio))) return rc;
+    if ((rc = sam_text_core(ctx, w, st, 2 * n_units, io, &sum, &pio, bam))) return rc;
     *text_bytes = sum.total;
     return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
 // Host-pointer form: one upload, and only the lines that were written and line_begin come down
-extern "C" int snapgpu_sam_text_paired(snapgpu_ctx *ctx, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+static int sam_text_paired_call(snapgpu_ctx *ctx, const char *who, bool bam, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
                                        const char *names, const uint64_t *name_off, const uint32_t *unit_pair, const int32_t *flag, const int32_t *contig,
                                        const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
                                        const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
                                        uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
 {
-    const std::string w = "snapgpu_sam_text_paired";
+    const std::string w(who);
     if (!ctx || !text_bytes || !line_begin || (text_capacity && !text) ||
         (n_units && (!bases || !quals || !offsets || !names || !name_off || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm || !rnext || !pnext || !tlen ||
                      !first_written)))
         return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
     if (n_units > 0x7fffffffull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^31 - 1 pair units in one call");
     if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, w + ": too many pairs");
-    int rc = sam_text_check(ctx, w, 2 * n_units, ops_stride);
+    int rc = sam_text_check(ctx, w, 2 * n_units, ops_stride, bam);
     if (rc) return rc;
     if (n_units == 0) return sam_text_empty(ctx, true, line_begin, text_bytes, nullptr);
     if (!unit_pair && n_units != n_pairs) return fail(ctx, SNAPGPU_E_INVALID, w + ": without unit_pair there is one unit per pair (n_units == n_pairs)");
@@ -3156,11 +3186,117 @@ extern "C" int snapgpu_sam_text_paired(snapgpu_ctx *ctx, uint64_t n_units, uint3
     io.cap = text_capacity; io.text = st.out(text, (size_t)text_capacity); io.line_begin = st.out(line_begin, (nl + 1) * 8);
     if (st.rc) return st.rc;
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, nl, io, &sum, &pio))) return rc;
+    if ((rc = sam_text_core(ctx, w, st, nl, io, &sum, &pio, bam))) return rc;
     st.limit(io.text, (size_t)sum.written);                              // only the lines that were written come down
     if ((rc = st.download())) return rc;
     *text_bytes = sum.total;
     return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+}
+
+// ---- the exported forms of the bodies above: SAM lines (sam_text.h) and BAM records (sam_bam.h) ------------------------------------------------
+extern "C" int snapgpu_sam_text_single_device(snapgpu_ctx *ctx, uint64_t n_records, const void *d_bases, const void *d_quals, const void *d_offsets,
+                                              const void *d_names, const void *d_name_off, const void *d_rec_read, const void *d_flag, const void *d_contig,
+                                              const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                              uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
+{
+    return sam_text_single_device_call(ctx, "snapgpu_sam_text_single_device", false, n_records, d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig,
+                                       d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, text_capacity, d_text, d_line_begin, text_bytes, stream);
+}
+extern "C" int snapgpu_sam_text_single(snapgpu_ctx *ctx, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
+                                       const char *names, const uint64_t *name_off, const uint32_t *rec_read, const int32_t *flag, const int32_t *contig,
+                                       const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                                       uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    return sam_text_single_call(ctx, "snapgpu_sam_text_single", false, n_records, n_reads, bases, quals, offsets, names, name_off, rec_read, flag, contig, pos, mapq, ops,
+                                ops_stride, n_ops, nm, text_capacity, text, line_begin, text_bytes);
+}
+extern "C" int snapgpu_align_sam_single_text(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                             uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    return align_sam_single_text_call(ctx, "snapgpu_align_sam_single_text", false, n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
+                                      ops_stride, record_capacity, n_records, rec_begin, flag, text_capacity, text, line_begin, text_bytes);
+}
+extern "C" int snapgpu_sam_text_paired_device(snapgpu_ctx *ctx, uint64_t n_units, const void *d_bases, const void *d_quals, const void *d_offsets,
+                                              const void *d_names, const void *d_name_off, const void *d_unit_pair, const void *d_flag, const void *d_contig,
+                                              const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                              const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
+                                              uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
+{
+    return sam_text_paired_device_call(ctx, "snapgpu_sam_text_paired_device", false, n_units, d_bases, d_quals, d_offsets, d_names, d_name_off, d_unit_pair, d_flag, d_contig,
+                                       d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_rnext, d_pnext, d_tlen, d_first_written, text_capacity, d_text, d_line_begin,
+                                       text_bytes, stream);
+}
+extern "C" int snapgpu_sam_text_paired(snapgpu_ctx *ctx, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                       const char *names, const uint64_t *name_off, const uint32_t *unit_pair, const int32_t *flag, const int32_t *contig,
+                                       const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                                       const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
+                                       uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    return sam_text_paired_call(ctx, "snapgpu_sam_text_paired", false, n_units, n_pairs, bases, quals, offsets, names, name_off, unit_pair, flag, contig, pos, mapq, ops,
+                                ops_stride, n_ops, nm, rnext, pnext, tlen, first_written, text_capacity, text, line_begin, text_bytes);
+}
+
+// Records -> the bytes of their BAM records (BAMFormat::writeRead, Bam.cpp:1312-1508): the three forms of the single-end text calls
+extern "C" int snapgpu_bam_records_single_device(snapgpu_ctx *ctx, uint64_t n_records, const void *d_bases, const void *d_quals, const void *d_offsets,
+                                                 const void *d_names, const void *d_name_off, const void *d_rec_read, const void *d_flag, const void *d_contig,
+                                                 const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                                 uint64_t byte_capacity, void *d_bytes, void *d_block_begin, uint64_t *bam_bytes, void *stream)
+{
+    return sam_text_single_device_call(ctx, "snapgpu_bam_records_single_device", true, n_records, d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig,
+                                       d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, byte_capacity, d_bytes, d_block_begin, bam_bytes, stream);
+}
+extern "C" int snapgpu_bam_records_single(snapgpu_ctx *ctx, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
+                                          const char *names, const uint64_t *name_off, const uint32_t *rec_read, const int32_t *flag, const int32_t *contig,
+                                          const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                                          uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
+{
+    return sam_text_single_call(ctx, "snapgpu_bam_records_single", true, n_records, n_reads, bases, quals, offsets, names, name_off, rec_read, flag, contig, pos, mapq, ops,
+                                ops_stride, n_ops, nm, byte_capacity, (char *)bytes, block_begin, bam_bytes);
+}
+extern "C" int snapgpu_align_sam_single_bam(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                            const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                            const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                            uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                            uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
+{
+    return align_sam_single_text_call(ctx, "snapgpu_align_sam_single_bam", true, n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
+                                      ops_stride, record_capacity, n_records, rec_begin, flag, byte_capacity, (char *)bytes, block_begin, bam_bytes);
+}
+// The two BAM records of each pair unit (BAMFormat::writePairs, Bam.cpp:1033-1309): the three forms of the paired text calls
+extern "C" int snapgpu_bam_records_paired_device(snapgpu_ctx *ctx, uint64_t n_units, const void *d_bases, const void *d_quals, const void *d_offsets,
+                                                 const void *d_names, const void *d_name_off, const void *d_unit_pair, const void *d_flag, const void *d_contig,
+                                                 const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
+                                                 const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
+                                                 uint64_t byte_capacity, void *d_bytes, void *d_block_begin, uint64_t *bam_bytes, void *stream)
+{
+    return sam_text_paired_device_call(ctx, "snapgpu_bam_records_paired_device", true, n_units, d_bases, d_quals, d_offsets, d_names, d_name_off, d_unit_pair, d_flag, d_contig,
+                                       d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_rnext, d_pnext, d_tlen, d_first_written, byte_capacity, d_bytes, d_block_begin,
+                                       bam_bytes, stream);
+}
+extern "C" int snapgpu_bam_records_paired(snapgpu_ctx *ctx, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                          const char *names, const uint64_t *name_off, const uint32_t *unit_pair, const int32_t *flag, const int32_t *contig,
+                                          const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
+                                          const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
+                                          uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
+{
+    return sam_text_paired_call(ctx, "snapgpu_bam_records_paired", true, n_units, n_pairs, bases, quals, offsets, names, name_off, unit_pair, flag, contig, pos, mapq, ops,
+                                ops_stride, n_ops, nm, rnext, pnext, tlen, first_written, byte_capacity, (char *)bytes, block_begin, bam_bytes);
+}
+extern "C" int snapgpu_align_sam_paired_bam(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                            const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                            const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                            snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                            uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
+{
+    if (!ctx || !block_begin || !bam_bytes || (byte_capacity && !bytes) ||
+        (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off || !flag || !first_written)))
+        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired_bam: null argument");
+    const PairedTextOut t{names, name_off, byte_capacity, (char *)bytes, block_begin, bam_bytes, true};
+    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bam", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
+                                 flag, nullptr, nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, &t);
 }
 
 // Diagnostics (not part of the drop-in surface): how many SamfPre records the row-loop pre-pass (k_samf_dp8 / k_samf_dp8_paired) of the context's
