@@ -41,6 +41,8 @@
  *       sequence codes :505-510, the aux fields :1510-1650)
  *   snapgpu_bam_records_paired / _device, snapgpu_align_sam_paired_bam
  *       BAMFormat::writePairs, the bytes of the two records of a pair's result  SNAPLib/Bam.cpp:1033-1309
+ *   snapgpu_bgzf_compress / _device, snapgpu_align_sam_single_bgzf, snapgpu_align_sam_paired_bgzf
+ *       the BGZF writer behind BAMFormat (SNAPLib/Bam.cpp) and DataWriter's gzip filter: bytes to BGZF blocks
  *   snapgpu_sam_fields_single
  *       SimpleReadWriter::writeReads            SNAPLib/ReadWriter.cpp:170-330
  *       SAMFormat::writeRead / createSAMLine / computeCigarString  SNAPLib/SAM.cpp:1898-2352 / 1424-1572 / 2595-2766
@@ -781,6 +783,55 @@ int  snapgpu_align_sam_paired_bam(snapgpu_ctx *ctx, uint32_t n_pairs, const char
                                   const char *names, const uint64_t *name_off, uint32_t ops_stride,
                                   snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
                                   uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes);
+
+/*
+ * Bytes -> BGZF blocks on the device: what the tool's bgzf_append (snap_amd/csrc/host/snapgpu_sam.cpp) does with zlib, and on the reference's
+ * side the BGZF writer of SNAPLib/Bam.cpp behind DataWriter's gzip filter.  Member m covers the input bytes [m * block_input,
+ * min((m + 1) * block_input, n_bytes)); n_members = max(1, ceil(n_bytes / block_input)), so an empty input (n_bytes 0, valid) gives the one
+ * 28-byte end-of-file member of the BGZF specification.  A member is
+ *   1f 8b 08 04 | MTIME 0 | XFL 0 | OS ff | XLEN 6 | 42 43 02 00 | BSIZE = size - 1 | raw DEFLATE | CRC32 | ISIZE
+ * with one dynamic-Huffman block, or one stored block where that is not smaller: never more than len + 31 bytes, so a capacity of
+ * n_members * (block_input + 31) always suffices.  The bytes are a function of the input and block_input alone (not of the device, the
+ * grid or the stream), but they are NOT zlib's bytes: only what they decompress to is.
+ *   d_in / in: n_bytes at any byte address; block_input: 1 .. 0xff00; d_out / out: out_capacity bytes at any byte address;
+ *   d_member_begin / member_begin: uint64 [n_members + 1], member m is out[member_begin[m], member_begin[m + 1]);
+ *   *n_members, *out_bytes: the number of members and what all of them need.
+ * SNAPGPU_W_TEXT_TRUNCATED (*out_bytes > out_capacity): member_begin is complete, every member that lies wholly below the capacity is written
+ * exactly as a large enough call writes it, nothing at or beyond the capacity is touched.  SNAPGPU_E_INVALID: block_input 0 or > 0xff00, NULL
+ * where a pointer is needed.  The device form is synchronous on `stream` (NULL: the context's); the host form goes through the staging layer
+ * of the other host-pointer entry points.
+ */
+int  snapgpu_bgzf_compress_device(snapgpu_ctx *ctx, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t out_capacity, void *d_out,
+                                  void *d_member_begin, uint64_t *n_members, uint64_t *out_bytes, void *stream);
+int  snapgpu_bgzf_compress(snapgpu_ctx *ctx, uint64_t n_bytes, const uint8_t *in, uint32_t block_input, uint64_t out_capacity, uint8_t *out,
+                           uint64_t *member_begin, uint64_t *n_members, uint64_t *out_bytes);
+
+/*
+ * snapgpu_align_sam_single_bam / snapgpu_align_sam_paired_bam with the BGZF stage behind them: the record bytes and block_begin stay in HBM, in
+ * buffers whose size is the library's business, snapgpu_bgzf_compress_device runs over them on the same stream, and the blocks come down in the
+ * call's one download.  This replaces, for the records of a batch, the BGZF writer of SNAPLib/Bam.cpp behind DataWriter's gzip filter, and the
+ * tool's bgzf_append.  Every argument, check, warning and error is the _bam form's, except that
+ *   block_input, bgzf_capacity, bgzf, member_begin (uint64 [member_capacity + 1]), member_capacity, n_members, bgzf_bytes
+ *       stand where byte_capacity, bytes and block_begin stand, with the meaning they have in snapgpu_bgzf_compress: the batch's record bytes
+ *       are ONE input, cut at multiples of block_input;
+ *   *bam_bytes is still the uncompressed total.
+ * flags, rec_begin, first_written and the results come down as in the _bam form.  SNAPGPU_W_TEXT_TRUNCATED: *bgzf_bytes > bgzf_capacity, with
+ * what that means in snapgpu_bgzf_compress, or *n_members > member_capacity, and then member_begin holds its first member_capacity + 1 entries;
+ * both figures are complete either way.  SNAPGPU_W_RECORDS_TRUNCATED comes first (the blocks are then those of the records that were formatted).
+ * SNAPGPU_E_INVALID for a block_input of 0 or above 0xff00.  n = 0 (n_pairs = 0): no member at all; a batch without a record: one empty member.
+ */
+int  snapgpu_align_sam_single_bgzf(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                   const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                   const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                   uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                   uint32_t block_input, uint64_t bgzf_capacity, uint8_t *bgzf, uint64_t *member_begin, uint64_t member_capacity,
+                                   uint64_t *n_members, uint64_t *bgzf_bytes, uint64_t *bam_bytes);
+int  snapgpu_align_sam_paired_bgzf(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                   const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                   const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                   snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                   uint32_t block_input, uint64_t bgzf_capacity, uint8_t *bgzf, uint64_t *member_begin, uint64_t member_capacity,
+                                   uint64_t *n_members, uint64_t *bgzf_bytes, uint64_t *bam_bytes);
 
 /*
  * Batched AffineGapVectorized<dir>::computeScore (banded[i] == 0) / computeScoreBanded

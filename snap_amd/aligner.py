@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "snapgpu_compute_cigar_lv", "snapgpu_compute_cigar_ag", "snapgpu_adjust_alignments", "snapgpu_set_aligner_flags", "snapgpu_affine_gap_sequence", "snapgpu_sam_fields_single", "snapgpu_sam_fields_single_device", "snapgpu_sam_fields_paired", "snapgpu_sam_fields_paired_device", "snapgpu_align_sam_single", "snapgpu_align_sam_single_records", "snapgpu_align_sam_single_records_device", "snapgpu_set_contig_names", "snapgpu_sam_text_single", "snapgpu_sam_text_single_device", "snapgpu_align_sam_single_text", "snapgpu_align_sam_paired", "snapgpu_sam_text_paired", "snapgpu_sam_text_paired_device", "snapgpu_align_sam_paired_text","snapgpu_create_replica_with_params",
     "snapgpu_set_contig_bam_ids", "snapgpu_bam_records_single", "snapgpu_bam_records_single_device", "snapgpu_align_sam_single_bam",
     "snapgpu_bam_records_paired", "snapgpu_bam_records_paired_device", "snapgpu_align_sam_paired_bam",
+    "snapgpu_bgzf_compress", "snapgpu_bgzf_compress_device", "snapgpu_align_sam_single_bgzf", "snapgpu_align_sam_paired_bgzf",
     "snapgpu_default_index_build_params", "snapgpu_index_build", "snapgpu_index_build_from_fasta", "snapgpu_index_build_shaped",
     "snapgpu_index_build_from_fasta_shaped", "snapgpu_built_index_view",
     "snapgpu_built_index_save", "snapgpu_built_index_stats", "snapgpu_built_index_destroy",
@@ -556,6 +557,88 @@ class BaseAligner:
                                               adjust_primary=adjust_primary, capacity=capacity, text_capacity=byte_capacity, grow=grow,
                                               _fn="snapgpu_align_sam_single_bam"))
 
+    # ---- bytes -> BGZF blocks (the BGZF writer behind BAMFormat, DataWriter's gzip filter) ----
+    @staticmethod
+    def _bgzf_members(n_bytes: int, block_input: int = 0xff00) -> int:
+        """how many BGZF blocks n_bytes make when every block takes block_input of them (an empty input makes one empty block)"""
+        return max(1, -(-int(n_bytes) // int(block_input))) if block_input else 1
+
+    def bgzfCompress(self, data, block_input: int = 0xff00, capacity: int | None = None, grow: bool = True, out=None):
+        """BGZF blocks of `data` (uint8 / bytes), one per block_input bytes (snapgpu_bgzf_compress).  capacity: bytes to make room for (default:
+        what always suffices, n_members * (block_input + 31)); grow: call again with the size the library asks for when that was too few; out:
+        a uint8 array to write into (its size is the capacity).  Returns dict(bgzf uint8[capacity], member_begin uint64[n_members + 1],
+        n_members, bgzf_bytes, truncated)."""
+        data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8).reshape(-1)
+        nm = self._bgzf_members(data.size, block_input)
+        cap = out.size if out is not None else (int(capacity) if capacity is not None else nm * (int(block_input) + 31))
+        member_begin = np.zeros(nm + 1, np.uint64)
+        f = self.lib.snapgpu_bgzf_compress
+        f.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 4
+        while True:
+            if out is None or out.size != cap:
+                out = np.zeros(cap, np.uint8)
+            n_mem = C.c_uint64(0); ob = C.c_uint64(0)
+            rc = f(self.handle, data.size, ptr(data) if data.size else None, block_input, cap, ptr(out) if cap else None, ptr(member_begin),
+                   C.addressof(n_mem), C.addressof(ob))
+            if rc == W_TEXT_TRUNCATED and grow:
+                cap = int(ob.value)
+                continue
+            if rc != W_TEXT_TRUNCATED:
+                self._check(rc, "snapgpu_bgzf_compress")
+            return dict(bgzf=out, member_begin=member_begin, n_members=int(n_mem.value), bgzf_bytes=int(ob.value), truncated=rc == W_TEXT_TRUNCATED)
+
+    def bgzfCompress_device(self, n_bytes: int, d_in: int, block_input: int, capacity: int, d_out: int, d_member_begin: int, stream: int = 0):
+        """Device-pointer form of bgzfCompress (snapgpu_bgzf_compress_device): the input, the blocks and member_begin (uint64[n_members + 1]) in
+        HBM, at any byte address.  Synchronous on `stream` (0: the context's).  Returns (n_members, bgzf_bytes, truncated)."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        f = self.lib.snapgpu_bgzf_compress_device
+        f.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 5
+        n_mem = C.c_uint64(0); ob = C.c_uint64(0)
+        rc = f(self.handle, n_bytes, vp(d_in), block_input, capacity, vp(d_out), vp(d_member_begin), C.addressof(n_mem), C.addressof(ob), vp(stream))
+        if rc != W_TEXT_TRUNCATED:
+            self._check(rc, "snapgpu_bgzf_compress_device")
+        return int(n_mem.value), int(ob.value), rc == W_TEXT_TRUNCATED
+
+    def alignSamBgzf(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
+                     adjust_primary: bool = False, capacity: int | None = None, block_input: int = 0xff00, bgzf_capacity: int | None = None,
+                     member_capacity: int | None = None, grow: bool = True):
+        """alignSamBam with the BGZF stage behind it on the device (snapgpu_align_sam_single_bgzf): the record bytes stay in HBM and their
+        blocks come down.  bgzf_capacity / member_capacity: bytes / blocks to make room for (defaults: estimates); grow: call again with
+        what the library asks for.  Returns dict(bgzf, member_begin, n_members, bgzf_bytes, bam_bytes, truncated, n_records,
+        records_truncated, rec_begin, flag); member_begin is cut to the blocks it has room for."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1); quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        front_clip = np.ascontiguousarray(front_clip, dtype=np.int32); data_len = np.ascontiguousarray(data_len, dtype=np.int32)
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        names = np.ascontiguousarray(names, dtype=np.uint8).reshape(-1); name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        n = offsets.size - 1
+        cap = int(capacity) if capacity is not None else n + n // 2 + 16
+        zcap = int(bgzf_capacity) if bgzf_capacity is not None else 2 * int(bases.size) + 128 * cap + 64
+        mcap = int(member_capacity) if member_capacity is not None else (zcap // block_input if block_input else 0) + 2
+        rec_begin = np.zeros(n + 1, np.uint64)
+        f = self.lib.snapgpu_align_sam_single_bgzf
+        f.argtypes = ([C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 3 +
+                      [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3)
+        while True:
+            flag = np.zeros(cap, np.int32); member_begin = np.zeros(mcap + 1, np.uint64); bgzf = np.zeros(zcap, np.uint8)
+            n_rec = C.c_uint64(0); n_mem = C.c_uint64(0); zb = C.c_uint64(0); bb = C.c_uint64(0)
+            rc = f(self.handle, n, ptr(bases), ptr(quals), ptr(offsets), ptr(front_clip), ptr(data_len), ptr(skip), 1 if use_m else 0, 1 if adjust_primary else 0,
+                   ptr(names), ptr(name_off), ops_stride, cap, C.addressof(n_rec), ptr(rec_begin), ptr(flag), block_input, zcap, ptr(bgzf) if zcap else None,
+                   ptr(member_begin), mcap, C.addressof(n_mem), C.addressof(zb), C.addressof(bb))
+            if rc == W_RECORDS_TRUNCATED and grow:
+                cap = int(n_rec.value)
+                continue
+            if rc == W_TEXT_TRUNCATED and grow:
+                zcap = max(zcap, int(zb.value)); mcap = max(mcap, int(n_mem.value))
+                continue
+            if rc not in (W_RECORDS_TRUNCATED, W_TEXT_TRUNCATED):
+                self._check(rc, "snapgpu_align_sam_single_bgzf")
+            break
+        m = min(int(n_rec.value), cap)
+        return dict(bgzf=bgzf, member_begin=member_begin[:min(int(n_mem.value), mcap) + 1], n_members=int(n_mem.value), bgzf_bytes=int(zb.value),
+                    bam_bytes=int(bb.value), truncated=rc == W_TEXT_TRUNCATED, n_records=int(n_rec.value), records_truncated=rc == W_RECORDS_TRUNCATED,
+                    rec_begin=rec_begin, flag=flag[:m])
+
     def samFieldsPaired(self, bases, quals, offsets, front_clip, data_len, results, use_m: bool = False, ops_stride: int = 64):
         """SAMFormat::writePairs + fillMateInfo up to the point of printing (see snapgpu_sam_fields_paired).  offsets has 2 n + 1
         entries (read 0 and read 1 of each pair); results: PAIRED_RESULT_DTYPE array of n."""
@@ -888,6 +971,42 @@ class ChimericPairedEndAligner(BaseAligner):
         dict(bytes, block_begin uint64[2 n_pairs + 1], bam_bytes, truncated, flag, first_written, results, first_alt)."""
         return self._as_bam(self.alignSamTextPaired(bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m=use_m, ops_stride=ops_stride,
                                                     text_capacity=byte_capacity, grow=grow, want_results=want_results, _fn="snapgpu_align_sam_paired_bam"))
+
+    def alignSamBgzfPaired(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
+                           block_input: int = 0xff00, bgzf_capacity: int | None = None, member_capacity: int | None = None, grow: bool = True,
+                           want_results: bool = False):
+        """alignSamBamPaired with the BGZF stage behind it on the device (snapgpu_align_sam_paired_bgzf), as alignSamBgzf.  Returns dict(bgzf,
+        member_begin, n_members, bgzf_bytes, bam_bytes, truncated, flag, first_written, results, first_alt)."""
+        from .abi import PAIRED_RESULT_DTYPE
+        bases = np.ascontiguousarray(bases, dtype=np.uint8).reshape(-1); quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        front_clip = np.ascontiguousarray(front_clip, dtype=np.int32); data_len = np.ascontiguousarray(data_len, dtype=np.int32)
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        names = np.ascontiguousarray(names, dtype=np.uint8).reshape(-1); name_off = np.ascontiguousarray(name_off, dtype=np.uint64)
+        if (offsets.size - 1) % 2:
+            raise ValueError("offsets must have 2*n_pairs + 1 entries")
+        n = offsets.size - 1; npairs = n // 2
+        zcap = int(bgzf_capacity) if bgzf_capacity is not None else 2 * int(bases.size) + 128 * n + 64
+        mcap = int(member_capacity) if member_capacity is not None else (zcap // block_input if block_input else 0) + 2
+        results = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
+        first_alt = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
+        f = self.lib.snapgpu_align_sam_paired_bgzf
+        f.argtypes = ([C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 +
+                      [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3)
+        while True:
+            flag = np.zeros(n, np.int32); first = np.zeros(npairs, np.int32); member_begin = np.zeros(mcap + 1, np.uint64); bgzf = np.zeros(zcap, np.uint8)
+            n_mem = C.c_uint64(0); zb = C.c_uint64(0); bb = C.c_uint64(0)
+            rc = f(self.handle, npairs, ptr(bases), ptr(quals), ptr(offsets), ptr(front_clip), ptr(data_len), ptr(skip), 1 if use_m else 0, ptr(names), ptr(name_off),
+                   ops_stride, ptr(results) if want_results else None, ptr(first_alt) if want_results else None, ptr(flag), ptr(first), block_input, zcap,
+                   ptr(bgzf) if zcap else None, ptr(member_begin), mcap, C.addressof(n_mem), C.addressof(zb), C.addressof(bb))
+            if rc == W_TEXT_TRUNCATED and grow:
+                zcap = max(zcap, int(zb.value)); mcap = max(mcap, int(n_mem.value))
+                continue
+            if rc != W_TEXT_TRUNCATED:
+                self._check(rc, "snapgpu_align_sam_paired_bgzf")
+            break
+        return dict(bgzf=bgzf, member_begin=member_begin[:min(int(n_mem.value), mcap) + 1], n_members=int(n_mem.value), bgzf_bytes=int(zb.value),
+                    bam_bytes=int(bb.value), truncated=rc == W_TEXT_TRUNCATED, flag=flag, first_written=first, results=results, first_alt=first_alt)
 
     def align_secondary(self, bases: np.ndarray, quals: np.ndarray, offsets: np.ndarray, stride: int = 8, single_stride: int = 16):
         """ChimericPairedEndAligner::align with secondary results (after enable_secondary(...)): returns

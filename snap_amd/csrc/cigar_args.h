@@ -139,6 +139,20 @@ struct SamBamArgs : SamTextPairedArgs {
     const int32_t *ref_id;                                                       // [n_contigs] snapgpu_set_contig_bam_ids: the BAM number of each contig
 };
 extern "C" void snapgpu_launch_sam_bam(const SamBamArgs *a, int paired, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s);
+// snapgpu_bgzf_compress*: bytes -> BGZF blocks (bgzf.h).  Member m covers in[m * block_input, ...) and is first written into slots + m * slot_stride
+// (zero beforehand; slot_stride >= block_input + 31, a multiple of 4); a wavefront of the deflate launch keeps its tokens in tok + wave * tok_stride.
+#define BGZF_MAX_BLOCK_INPUT 0xff00u
+#define BGZF_LDS_WORDS 4800u        // dwords of LDS per wavefront of k_bgzf_deflate
+struct BgzfArgs {
+    uint64_t n_bytes; uint32_t block_input, n_members;
+    const uint8_t *in;
+    uint32_t *tok; uint64_t tok_stride;                                          // [deflate waves * tok_stride], tok_stride >= block_input + 1
+    uint8_t *slots; uint64_t slot_stride;                                        // [n_members * slot_stride]
+    uint32_t *size; uint64_t *partial;                                           // [n_members + 1] member sizes, [tiles of SAMREC_CHUNK] their sums
+    uint64_t cap; uint8_t *out; uint64_t *member_begin;                          // [cap], [n_members + 1]
+    SamTextSummary *summary;                                                     // total: bytes all members need; written: end of the last member below cap
+};
+extern "C" void snapgpu_launch_bgzf(const BgzfArgs *a, uint32_t deflate_blocks, uint32_t scan_blocks, uint32_t place_blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_count(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_list(const SamRecArgs *a, uint32_t blocks, hipStream_t s);

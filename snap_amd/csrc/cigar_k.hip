@@ -1,7 +1,8 @@
 // cigar_k.hip -- the SAM writer's kernels, one wavefront per item on a persistent grid: SAMFormat::computeCigar for a batch of written reads
 // (k_cigar_lv, k_cigar_ag), result -> SAM fields (k_sam_fields*: one body, sam_fields_run, over the reads of a batch, the records of a record
 // list or the mates of a paired batch, with the pre-pass k_samf_dp8* ahead of it), AlignmentAdjuster (k_adjust_alignments) and the launches
-// of the record-list kernels (sam_records.h), of the SAM-line kernels (sam_text.h) and of the BAM-record kernels (sam_bam.h).
+// of the record-list kernels (sam_records.h), of the SAM-line kernels (sam_text.h), of the BAM-record kernels (sam_bam.h) and of the BGZF
+// kernels (bgzf.h).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -c cigar_k.hip
 #include <hip/hip_runtime.h>
 #include "cigar_lv.h"
@@ -12,6 +13,7 @@
 #include "sam_records.h"
 #include "sam_text.h"
 #include "sam_bam.h"
+#include "bgzf.h"
 
 __global__ __launch_bounds__(256) void k_cigar_lv(CigarArgs a)
 {
@@ -558,4 +560,17 @@ extern "C" void snapgpu_launch_sam_bam(const SamBamArgs *a, int paired, uint32_t
     hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, base);
     if (paired) hipLaunchKernelGGL(k_sambam_pair_write, dim3(write_blocks), dim3(256), 0, s, *a);
     else hipLaunchKernelGGL(k_sambam_write, dim3(write_blocks), dim3(256), 0, s, *a);
+}
+
+// ---- bytes -> BGZF blocks (bgzf.h): every member into its slot, sam_text.h's scan over the sizes, the members that fit the capacity into place ---
+extern "C" void snapgpu_launch_bgzf(const BgzfArgs *a, uint32_t deflate_blocks, uint32_t scan_blocks, uint32_t place_blocks, hipStream_t s)
+{
+    SamTextArgs scan{};
+    scan.n = a->n_members; scan.n_chunks = (a->n_members + SAMREC_CHUNK - 1u) / SAMREC_CHUNK; scan.len = a->size; scan.partial = a->partial;
+    scan.line_begin = a->member_begin; scan.cap = a->cap; scan.summary = a->summary;
+    hipLaunchKernelGGL(k_bgzf_deflate, dim3(deflate_blocks), dim3(64), (size_t)BGZF_LDS_WORDS * 4, s, *a);
+    hipLaunchKernelGGL(k_bgzf_sums, dim3(scan_blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samtext_partials, dim3(1), dim3(64), 0, s, scan);
+    hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, scan);
+    hipLaunchKernelGGL(k_bgzf_place, dim3(place_blocks), dim3(256), 0, s, *a);
 }

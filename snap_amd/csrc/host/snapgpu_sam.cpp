@@ -292,6 +292,7 @@ struct Work {                                // a batch on its way through the p
     uint32_t max_len = 0;                    // the longest read of the batch (unclipped): picks the context's read-length class
     std::string text;                        // the formatted records (BAM: BGZF blocks)
     bool text_done = false;                  // the feeder left the SAM lines in `text` (SNAPGPU_SAM_DEVICE_TEXT): nothing for the formatter to do
+    bool bgzf_done = false;                  // ... and `text` holds the batch's BGZF blocks already (SNAPGPU_SAM_DEVICE_BGZF): nothing to compress either
     bool bam = false;
     unsigned long long mapped = 0;
     // as newly constructed, but every vector keeps its capacity (WorkPool)
@@ -302,7 +303,7 @@ struct Work {                                // a batch on its way through the p
         emit.clear(); pu_pair.clear(); pu_secondary.clear(); su_read.clear();
         s_flag.clear(); s_contig.clear(); s_mapq.clear(); s_n_ops.clear(); s_nm.clear(); s_pos.clear(); s_ops.clear(); s_ops_stride = 64;
         prepared = false; front_clip.clear(); data_len.clear(); to_align.clear(); ab.clear(); aq.clear(); ao.clear(); skip.clear();
-        max_len = 0; text.clear(); text_done = false; bam = false; mapped = 0;
+        max_len = 0; text.clear(); text_done = false; bgzf_done = false; bam = false; mapped = 0;
     }
 };
 
@@ -596,14 +597,25 @@ static bool device_text_paired_path(const Options &o)
 // (snapgpu_align_sam_single_bam, every option set; snapgpu_align_sam_paired_bam, no -om, first-ALT batches through the host path) and the
 // formatter threads only compress them.  A switch of its own: SNAPGPU_SAM_DEVICE_TEXT keeps ignoring BAM.  Off unless asked for (DESIGN.md
 // section 13); SAM output ignores it.  The file is the same bytes either way (tests/test_zz_gpu_sam_bam.py).
+// SNAPGPU_SAM_DEVICE_BGZF=1: the same two paths again, and the batch's BGZF blocks come from the device as well (snapgpu_align_sam_single_bgzf /
+// snapgpu_align_sam_paired_bgzf with block_input 0xff00: a batch is one compression unit cut where bgzf_append cuts it): the formatter threads
+// pass the batch through and the writer writes it.  The header block, the end-of-file block and first-ALT batches of pairs stay with the host's
+// zlib.  The file has the members of the switch-off file with other compressed payloads (tests/test_zz_gpu_bgzf.py).  Off unless asked for.
+static bool device_bgzf_switch(const Options &o)
+{
+    static const bool on = getenv("SNAPGPU_SAM_DEVICE_BGZF") && atoi(getenv("SNAPGPU_SAM_DEVICE_BGZF")) != 0;
+    return on && o.bam;
+}
 static bool device_bam_switch(const Options &o)
 {
     static const bool on = getenv("SNAPGPU_SAM_DEVICE_BAM") && atoi(getenv("SNAPGPU_SAM_DEVICE_BAM")) != 0;
-    return on && o.bam;
+    return (on && o.bam) || device_bgzf_switch(o);
 }
 static bool device_bam_path(const Options &o) { return device_bam_switch(o) && !o.paired; }
 static bool device_bam_paired_path(const Options &o) { return device_bam_switch(o) && o.paired && o.om < 0; }
 static std::atomic<unsigned long long> g_bam_batches(0), g_bam_records(0);      // what the device-BAM paths produced (the line on stderr at the end)
+static std::atomic<unsigned long long> g_bgzf_batches(0), g_bgzf_members(0), g_bgzf_in(0), g_bgzf_out(0);      // what SNAPGPU_SAM_DEVICE_BGZF produced (its line on stderr)
+static std::atomic<uint32_t> g_bgzf_per_mille(500);             // BGZF capacity of the next call, in thousandths of the record-byte estimate: grows to what batches have needed
 static std::atomic<uint32_t> g_text_extra_per_record(128);      // text capacity of the next call: bytes per record beyond its name, SEQ and QUAL; grows to what batches have needed
 static std::atomic<uint32_t> g_records_per_read_x16(24);        // record capacity of the next call, in sixteenths of a record per read: grows to what batches have needed
 
@@ -635,6 +647,14 @@ static bool g_index_has_alt = false;        // the index has ALT contigs: only t
 // SNAPGPU_SAM_DEVICE_TEXT / SNAPGPU_SAM_DEVICE_BAM: the batch goes up as it was parsed, with its names, and its SAM lines (BAM output: its
 // uncompressed BAM records, which are shorter than the lines, so the same estimate has room for them) come down.  Both capacities start from an
 // estimate and follow what the library reports; a cigar that outgrows its row is met with a larger row, as with_growing_stride does.
+// a batch whose blocks came from the device: the counts of the line on stderr, and the next batch's capacity (est: this batch's record-byte estimate)
+static void bgzf_from_device(Work &w, size_t est, uint64_t n_members, uint64_t in_bytes, uint64_t out_bytes)
+{
+    w.bgzf_done = true;
+    g_bgzf_batches++; g_bgzf_members += n_members; g_bgzf_in += in_bytes; g_bgzf_out += out_bytes;
+    const uint32_t need = (uint32_t)(out_bytes * 1000 / (est ? est : 1)) + 20;
+    uint32_t cur = g_bgzf_per_mille.load(); while (need > cur && !g_bgzf_per_mille.compare_exchange_weak(cur, need)) {}
+}
 static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
 {
     auto t_stage = std::chrono::steady_clock::now();
@@ -650,11 +670,18 @@ static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
     const size_t per_read = (2 * b.bases.size() + b.names.size() + n - 1) / n;             // name, SEQ and QUAL of the average record
     size_t tcap = cap * (per_read + g_text_extra_per_record.load());
     uint32_t ops_stride = o.ops_stride;
-    uint64_t n_rec = 0, text_bytes = 0;
+    uint64_t n_rec = 0, text_bytes = 0, n_mem = 0, z_bytes = 0;
+    const bool bgzf = device_bgzf_switch(o);
+    size_t zcap = tcap / 1000 * g_bgzf_per_mille.load() + 64;
     lap(g_ns_prep);
     for (;;) {
-        w.flag.resize(cap); line_begin.resize(cap + 1); w.text.resize(tcap);
-        const int rc = o.bam
+        w.flag.resize(cap); line_begin.resize(bgzf ? tcap / 0xff00 + 2 : cap + 1); w.text.resize(bgzf ? zcap : tcap);
+        const int rc = bgzf
+            ? snapgpu_align_sam_single_bgzf(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
+                                            w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
+                                            (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), 0xff00, (uint64_t)zcap, (uint8_t *)&w.text[0], line_begin.data(),
+                                            (uint64_t)line_begin.size() - 1, &n_mem, &z_bytes, &text_bytes)
+            : o.bam
             ? snapgpu_align_sam_single_bam(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
                                            w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
                                            (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), (uint64_t)tcap, (uint8_t *)&w.text[0], line_begin.data(), &text_bytes)
@@ -664,12 +691,12 @@ static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
         if (rc == SNAPGPU_E_UNSUPPORTED && o.ae && !strncmp(snapgpu_last_error(ctx), "-ae:", 4))
             die("-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)");
         if (rc == SNAPGPU_W_RECORDS_TRUNCATED) { cap = (size_t)n_rec + (size_t)n_rec / 16; tcap = cap * (per_read + g_text_extra_per_record.load()); continue; }
-        if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; continue; }
+        if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; if (z_bytes > zcap) zcap = (size_t)z_bytes + (size_t)z_bytes / 64; continue; }
         if (rc == SNAPGPU_E_INVALID && strstr(snapgpu_last_error(ctx), "ops_stride")) {
             if (ops_stride >= 4096) die("a cigar needs more than 4096 operations");
             ops_stride *= 4; continue;
         }
-        if (rc != SNAPGPU_OK) fail_rc(ctx, o.bam ? "snapgpu_align_sam_single_bam" : "snapgpu_align_sam_single_text", rc);
+        if (rc != SNAPGPU_OK) fail_rc(ctx, bgzf ? "snapgpu_align_sam_single_bgzf" : o.bam ? "snapgpu_align_sam_single_bam" : "snapgpu_align_sam_single_text", rc);
         break;
     }
     const size_t nr = (size_t)n_rec;
@@ -677,7 +704,8 @@ static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
     { const uint32_t need = (uint32_t)((nr * 16 + n - 1) / n) + 2; uint32_t cur = g_records_per_read_x16.load(); while (need > cur && !g_records_per_read_x16.compare_exchange_weak(cur, need)) {} }
     if (nr) { const size_t per_rec = ((size_t)text_bytes + nr - 1) / nr; const uint32_t need = per_rec > per_read ? (uint32_t)(per_rec - per_read) + 16 : 16;
               uint32_t cur = g_text_extra_per_record.load(); while (need > cur && !g_text_extra_per_record.compare_exchange_weak(cur, need)) {} }
-    w.text.resize((size_t)text_bytes);
+    w.text.resize((size_t)(bgzf ? z_bytes : text_bytes));
+    if (bgzf) bgzf_from_device(w, tcap, n_mem, text_bytes, z_bytes);
     for (size_t r = 0; r < nr; r++) w.mapped += (w.flag[r] & 0x4) == 0;
     lap(g_ns_align);
 }
@@ -982,11 +1010,20 @@ static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
             const size_t per_read = (2 * b.bases.size() + b.names.size() + nrec - 1) / nrec;       // name, SEQ and QUAL of the average record
             size_t tcap = nrec * (per_read + g_text_extra_per_record.load());
             uint32_t ops_stride = o.ops_stride;
-            uint64_t text_bytes = 0;
+            uint64_t text_bytes = 0, n_mem = 0, z_bytes = 0;
+            const bool bgzf = device_bgzf_switch(o);
+            size_t zcap = tcap / 1000 * g_bgzf_per_mille.load() + 64;
+            std::vector<uint64_t> member_begin;
             w.flag.assign(nrec, 0); w.first_written.assign(np, 0);
             for (;;) {
-                w.text.resize(tcap);
-                const int rc = o.bam
+                w.text.resize(bgzf ? zcap : tcap); if (bgzf) member_begin.resize(tcap / 0xff00 + 2);
+                const int rc = bgzf
+                    ? snapgpu_align_sam_paired_bgzf(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
+                                                    skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
+                                                    want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
+                                                    0xff00, (uint64_t)zcap, (uint8_t *)&w.text[0], member_begin.data(), (uint64_t)member_begin.size() - 1,
+                                                    &n_mem, &z_bytes, &text_bytes)
+                    : o.bam
                     ? snapgpu_align_sam_paired_bam(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
                                                    skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
                                                    want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
@@ -995,23 +1032,25 @@ static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
                                                     skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
                                                     want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
                                                     (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
-                if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; continue; }
+                if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; if (z_bytes > zcap) zcap = (size_t)z_bytes + (size_t)z_bytes / 64; continue; }
                 if (rc == SNAPGPU_E_INVALID && strstr(snapgpu_last_error(ctx), "ops_stride")) {
                     if (ops_stride >= 4096) die("a cigar needs more than 4096 operations");
                     ops_stride *= 4; continue;
                 }
-                if (rc != SNAPGPU_OK) fail_rc(ctx, o.bam ? "snapgpu_align_sam_paired_bam" : "snapgpu_align_sam_paired_text", rc);
+                if (rc != SNAPGPU_OK) fail_rc(ctx, bgzf ? "snapgpu_align_sam_paired_bgzf" : o.bam ? "snapgpu_align_sam_paired_bam" : "snapgpu_align_sam_paired_text", rc);
                 break;
             }
             if (!first_alt_pair()) {
                 { const size_t per_rec = ((size_t)text_bytes + nrec - 1) / nrec; const uint32_t need = per_rec > per_read ? (uint32_t)(per_rec - per_read) + 16 : 16;
                   uint32_t cur = g_text_extra_per_record.load(); while (need > cur && !g_text_extra_per_record.compare_exchange_weak(cur, need)) {} }
-                w.text.resize((size_t)text_bytes); w.text_done = true; w.mapped = 0;
+                w.text.resize((size_t)(bgzf ? z_bytes : text_bytes)); w.text_done = true; w.mapped = 0;
+                if (bgzf) bgzf_from_device(w, tcap, n_mem, text_bytes, z_bytes);
                 for (size_t r = 0; r < nrec; r++) w.mapped += (w.flag[r] & 0x4) == 0;
                 if (o.bam) { g_bam_batches++; g_bam_records += nrec; }
                 return;
             }
-            w.text.clear();                                             // (rare: a first-ALT pair to write -- the batch goes through the calls below)
+            w.text.clear();                                             // (rare: a first-ALT pair to write -- the batch goes through the calls below; with
+                                                                        // SNAPGPU_SAM_DEVICE_BGZF the call above has compressed its records for nothing, too)
         } else {
             w.emit.clear(); w.pu_pair.resize(np); w.pu_secondary.assign(np, 0); w.su_read.clear();
             for (size_t k = 0; k < np; k++) { w.emit.push_back(Work::Emit{(uint32_t)k, 0}); w.pu_pair[k] = (uint32_t)k; }
@@ -1582,7 +1621,7 @@ int main(int argc, char **argv)
     std::vector<double> pass_s;
     WorkPool pool(256);
     for (int pass = 0; pass < o.passes; pass++) {
-        g_bam_batches = 0; g_bam_records = 0;
+        g_bam_batches = 0; g_bam_records = 0; g_bgzf_batches = 0; g_bgzf_members = 0; g_bgzf_in = 0; g_bgzf_out = 0;
     total = 0; mapped = 0;
     if (pass > 0) (void)unlink(out_path.c_str());        // (-passes: the previous pass's output goes BEFORE this pass is timed -- replacing a 5.6 GB file at the end of a pass
                                                          //  cost it 1.3 s of page-cache work that streaming a FASTQ file into a new SAM file does not have: profiles/r06j)
@@ -1723,7 +1762,7 @@ int main(int argc, char **argv)
             Work *w;
             while (q_aligned.pop(w)) {
                 if (!w->text_done) { StageTimer st(g_ns_format); if (o.paired) format_paired(contigs, *w); else format_single(contigs, *w); }
-                if (o.bam) { std::string z; z.reserve(w->text.size() / 3 + 64); bgzf_append(z, w->text.data(), w->text.size()); w->text.swap(z); }
+                if (o.bam && !w->bgzf_done) { std::string z; z.reserve(w->text.size() / 3 + 64); bgzf_append(z, w->text.data(), w->text.size()); w->text.swap(z); }
                 std::lock_guard<std::mutex> l(done_m); done[w->b.seq] = w; done_cv.notify_all();
             }
         });
@@ -1773,6 +1812,9 @@ int main(int argc, char **argv)
     fprintf(stderr, "snapgpu-sam: %llu reads, %llu mapped records, %d GPU(s) x %d feeder(s), %d formatter thread(s)\n", total, mapped, o.n_gpus, o.ctx_per_gpu, o.n_format);
     if (device_bam_switch(o) && (!o.paired || o.om < 0))                     // (the last pass's, like the counts above)
         fprintf(stderr, "snapgpu-sam: BAM records from the device: %llu batches, %llu records\n", g_bam_batches.load(), g_bam_records.load());
+    if (device_bgzf_switch(o) && (!o.paired || o.om < 0))
+        fprintf(stderr, "snapgpu-sam: BGZF blocks from the device: %llu batches, %llu blocks, %llu -> %llu bytes\n", g_bgzf_batches.load(), g_bgzf_members.load(),
+                g_bgzf_in.load(), g_bgzf_out.load());
     {   // (AlignerContext.cpp:489-543 prints reads/s over the alignment phase, the index load apart: the same split here)
         const double s_stream = pass_s.back();                              // (the last pass; with -passes N each pass printed its own line above)
         fprintf(stderr, "snapgpu-sam: index resident after %.2f s; FASTQ -> %s in %.2f s = %.0f reads/s (%s reader, %d parser thread(s))\n", s_load, o.bam ? "BAM" : "SAM", s_stream,

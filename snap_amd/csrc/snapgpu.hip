@@ -2886,13 +2886,69 @@ static int sam_text_single_call(snapgpu_ctx *ctx, const char *who, bool bam, uin
     return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
+// ---- the BGZF end of the fused BAM calls (snapgpu_align_sam_single_bgzf / _paired_bgzf): the record bytes and block_begin stay in buffers of the
+// library's own and the blocks come down in their place
+struct BgzfOut { uint32_t block_input; uint64_t cap; uint8_t *bgzf; uint64_t *member_begin; uint64_t member_capacity; uint64_t *n_members, *bgzf_bytes; };
+static uint64_t bgzf_members(uint64_t n_bytes, uint32_t block_input);
+static int bgzf_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_bytes, uint32_t block_input);
+static int bgzf_core(snapgpu_ctx *ctx, Stage &st, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t cap, void *d_out, void *d_member_begin,
+                     SamTextSummary *sum);
+static int bgzf_out_check(snapgpu_ctx *ctx, const std::string &w, const BgzfOut &z)
+{
+    if (!z.member_begin || !z.n_members || !z.bgzf_bytes || (z.cap && !z.bgzf)) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    if (const int rc = bgzf_check(ctx, w, 0, z.block_input)) return rc;
+    *z.n_members = 0; *z.bgzf_bytes = 0; *z.member_begin = 0;
+    return SNAPGPU_OK;
+}
+// The BAM records of a call into a buffer of the library's (io.cap / io.text / io.line_begin are set here).  Its size is an estimate from the longest
+// name, the longest read (RL) and eight cigar operations a record; records that need more are written by a second pass into a buffer of the exact size.
+static int bam_bytes_in_hbm(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, uint32_t n_reads, const uint64_t *name_off, uint32_t RL,
+                            SamTextIO io, const SamTextPairIO *pair, SamTextSummary *sum, void **d_bytes)
+{
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < n_reads; i++) if (name_off[i + 1] - name_off[i] > longest) longest = name_off[i + 1] - name_off[i];
+    if (longest > 254) longest = 254;                                    // (a longer QNAME fails the call)
+    const uint32_t ops = io.ops_stride < 8 ? io.ops_stride : 8;
+    io.cap = n_records * (36 + longest + 1 + 4ull * ops + (RL + 1) / 2 + RL + 58);      // (sam_bam.h: 36 fixed bytes, 50 + 1 + 7 of aux)
+    io.line_begin = st.scratch((size_t)(n_records + 1) * 8);
+    for (int pass = 0;; pass++) {
+        io.text = st.scratch((size_t)io.cap);
+        if (st.rc) return st.rc;
+        memset(sum, 0, sizeof(*sum));
+        if (const int rc = sam_text_core(ctx, w, st, n_records, io, sum, pair, true)) return rc;
+        if (sum->flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
+        if (sum->total <= io.cap) break;
+        if (pass) return fail(ctx, SNAPGPU_E_LAUNCH, w + ": the BAM records changed size between two passes");
+        io.cap = sum->total;
+    }
+    *d_bytes = io.text;
+    return SNAPGPU_OK;
+}
+// bam_total bytes at d_bytes -> the blocks, registered for the call's one download.  *truncated: SNAPGPU_W_TEXT_TRUNCATED is due.
+static int bgzf_tail(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t bam_total, const void *d_bytes, const BgzfOut &z, bool *truncated)
+{
+    int rc = bgzf_check(ctx, w, bam_total, z.block_input);
+    if (rc) return rc;
+    const uint64_t nm = bgzf_members(bam_total, z.block_input), kept = nm < z.member_capacity ? nm : z.member_capacity;
+    void *d_bgzf = st.out(z.bgzf, (size_t)z.cap), *d_member_begin = st.out(z.member_begin, ((size_t)nm + 1) * 8);
+    if (st.rc) return st.rc;
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = bgzf_core(ctx, st, bam_total, d_bytes, z.block_input, z.cap, d_bgzf, d_member_begin, &sum))) return rc;
+    st.limit(d_bgzf, (size_t)sum.written); st.limit(d_member_begin, ((size_t)kept + 1) * 8);
+    *z.n_members = nm; *z.bgzf_bytes = sum.total;
+    *truncated = sum.total > z.cap || nm > z.member_capacity;
+    return SNAPGPU_OK;
+}
+
 static int align_sam_single_text_call(snapgpu_ctx *ctx, const char *who, bool bam, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
                                              const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
                                              const char *names, const uint64_t *name_off, uint32_t ops_stride,
                                              uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
-                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes, const BgzfOut *z = nullptr)
 {
     const std::string w(who);
+    uint64_t no_line_begin = 0;
+    if (z) { if (const int rc = bgzf_out_check(ctx, w, *z)) return rc; line_begin = &no_line_begin; }
     if (!ctx || !n_records || !rec_begin || !line_begin || !text_bytes || (text_capacity && !text) || (record_capacity && !flag) ||
         (n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off)))
         return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
@@ -2920,7 +2976,7 @@ static int align_sam_single_text_call(snapgpu_ctx *ctx, const char *who, bool ba
     void *d_rec_begin = st.out(rec_begin, ((size_t)n + 1) * 8), *d_rec_read = st.scratch(c4), *d_rec_kind = st.scratch((size_t)record_capacity);
     void *d_flag = st.out(flag, c4), *d_contig = st.scratch(c4), *d_pos = st.scratch((size_t)record_capacity * 8), *d_mapq = st.scratch(c4);
     void *d_ops = st.scratch(c4 * ops_stride), *d_n_ops = st.scratch(c4), *d_nm = st.scratch(c4), *d_stale = st.scratch(c4);
-    void *d_text = st.out(text, (size_t)text_capacity), *d_line_begin = st.out(line_begin, ((size_t)record_capacity + 1) * 8);
+    void *d_text = z ? nullptr : (void *)st.out(text, (size_t)text_capacity), *d_line_begin = z ? nullptr : (void *)st.out(line_begin, ((size_t)record_capacity + 1) * 8);
     if (st.rc) return st.rc;
     // ---- the records, where snapgpu_align_sam_single_records_device leaves them (RL: the longest unclipped read, as check_sam_reads found it)
     uint64_t total = 0;
@@ -2931,6 +2987,16 @@ static int align_sam_single_text_call(snapgpu_ctx *ctx, const char *who, bool ba
     const uint64_t f = total < record_capacity ? total : record_capacity;                            // the records that were formatted
     // ---- their lines
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if (z) {                                                             // ---- their BAM records, left in HBM, and the blocks of those
+        void *d_bytes = nullptr; bool z_truncated = false;
+        const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, 0, nullptr, nullptr};
+        if (f && (rc = bam_bytes_in_hbm(ctx, w, st, f, n, name_off, RL, io, nullptr, &sum, &d_bytes))) return rc;
+        if ((rc = bgzf_tail(ctx, w, st, sum.total, d_bytes, *z, &z_truncated))) return rc;
+        st.limit(d_flag, (size_t)f * 4);
+        if ((rc = st.download())) return rc;
+        *n_records = total; *text_bytes = sum.total;
+        return rec_truncated ? SNAPGPU_W_RECORDS_TRUNCATED : (z_truncated ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK);
+    }
     if (f) {
         const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
                            text_capacity, d_text, d_line_begin};
@@ -3018,7 +3084,7 @@ extern "C" int snapgpu_sam_fields_paired_device(snapgpu_ctx *ctx, uint32_t n_pai
 // round trip of the results.
 // (`text`, snapgpu_align_sam_paired_text: the fields but flag and first_written stay in HBM -- a NULL output is a device-only buffer -- and the
 // lines of the batch's pairs follow them, with the names uploaded beside the batch and the lines that were written in the one download)
-struct PairedTextOut { const char *names; const uint64_t *name_off; uint64_t cap; char *text; uint64_t *line_begin; uint64_t *text_bytes; bool bam; };
+struct PairedTextOut { const char *names; const uint64_t *name_off; uint64_t cap; char *text; uint64_t *line_begin; uint64_t *text_bytes; bool bam; const BgzfOut *z = nullptr; };
 static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
                                  const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
                                  snapgpu_paired_result *results, snapgpu_paired_result *first_alt,
@@ -3066,7 +3132,7 @@ static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_p
     const void *d_names = nullptr, *d_name_off = nullptr; void *d_text = nullptr, *d_line_begin = nullptr;
     if (text) {
         d_names = st.in(text->names, (size_t)text->name_off[n]); d_name_off = st.in(text->name_off, ((size_t)n + 1) * 8);
-        d_text = st.out(text->text, (size_t)text->cap); d_line_begin = st.out(text->line_begin, ((size_t)n + 1) * 8);
+        if (!text->z) { d_text = st.out(text->text, (size_t)text->cap); d_line_begin = st.out(text->line_begin, ((size_t)n + 1) * 8); }
     }
     if (st.rc) return st.rc;
     if ((rc = launch_paired(ctx, n_pairs, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s, &clip)) || (rc = finish_timing(ctx))) return rc;      // (the align launches' own hipEvent time, before the events are reused)
@@ -3085,6 +3151,14 @@ static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_p
                        text->cap, d_text, d_line_begin};
     const SamTextPairIO pio{a.rnext, a.pnext, a.tlen, a.first_written};
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if (text->z) {                                                       // the BAM records left in HBM, and the blocks of those
+        void *d_bytes = nullptr; bool z_truncated = false;
+        if ((rc = bam_bytes_in_hbm(ctx, w, st, n, n, text->name_off, RL, io, &pio, &sum, &d_bytes)) ||
+            (rc = bgzf_tail(ctx, w, st, sum.total, d_bytes, *text->z, &z_truncated)) || (rc = st.download())) return rc;
+        *text->text_bytes = sum.total;
+        if (h_overflowed) return fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG);
+        return z_truncated ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+    }
     if ((rc = sam_text_core(ctx, w, st, n, io, &sum, &pio, text->bam))) return rc;
     if (sum.flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
     st.limit(d_text, (size_t)sum.written);                               // only the lines that were written come down
@@ -3297,6 +3371,108 @@ extern "C" int snapgpu_align_sam_paired_bam(snapgpu_ctx *ctx, uint32_t n_pairs, 
     const PairedTextOut t{names, name_off, byte_capacity, (char *)bytes, block_begin, bam_bytes, true};
     return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bam", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
                                  flag, nullptr, nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, &t);
+}
+
+// The two calls above with the record bytes and block_begin left in HBM and snapgpu_bgzf_compress_device behind them on the same stream: what the
+// BGZF writer of SNAPLib/Bam.cpp behind DataWriter's gzip filter, and bgzf_append of the tool, do with the records of a batch
+extern "C" int snapgpu_align_sam_single_bgzf(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                             uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                             uint32_t block_input, uint64_t bgzf_capacity, uint8_t *bgzf, uint64_t *member_begin, uint64_t member_capacity,
+                                             uint64_t *n_members, uint64_t *bgzf_bytes, uint64_t *bam_bytes)
+{
+    if (!ctx) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_bgzf: null argument");
+    const BgzfOut z{block_input, bgzf_capacity, bgzf, member_begin, member_capacity, n_members, bgzf_bytes};
+    return align_sam_single_text_call(ctx, "snapgpu_align_sam_single_bgzf", true, n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
+                                      ops_stride, record_capacity, n_records, rec_begin, flag, 0, nullptr, nullptr, bam_bytes, &z);
+}
+extern "C" int snapgpu_align_sam_paired_bgzf(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                             snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                             uint32_t block_input, uint64_t bgzf_capacity, uint8_t *bgzf, uint64_t *member_begin, uint64_t member_capacity,
+                                             uint64_t *n_members, uint64_t *bgzf_bytes, uint64_t *bam_bytes)
+{
+    const std::string w("snapgpu_align_sam_paired_bgzf");
+    if (!ctx || !bam_bytes || (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off || !flag || !first_written)))
+        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    const BgzfOut z{block_input, bgzf_capacity, bgzf, member_begin, member_capacity, n_members, bgzf_bytes};
+    if (const int rc = bgzf_out_check(ctx, w, z)) return rc;
+    uint64_t no_block_begin = 0;
+    PairedTextOut t{names, name_off, 0, nullptr, &no_block_begin, bam_bytes, true}; t.z = &z;
+    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bgzf", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
+                                 flag, nullptr, nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, &t);
+}
+
+// ---- bytes -> BGZF blocks (bgzf.h): what bgzf_append of the tool (host/snapgpu_sam.cpp) does with zlib, and on the reference's side the BGZF writer
+// of SNAPLib/Bam.cpp behind DataWriter's gzip filter.  Everything in HBM; the stream is synchronised when bgzf_core returns.
+static uint64_t bgzf_members(uint64_t n_bytes, uint32_t block_input) { return n_bytes ? (n_bytes + block_input - 1) / block_input : 1; }
+static int bgzf_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_bytes, uint32_t block_input)
+{
+    if (block_input == 0 || block_input > BGZF_MAX_BLOCK_INPUT) return fail(ctx, SNAPGPU_E_INVALID, w + ": block_input must be between 1 and 0xff00");
+    if (bgzf_members(n_bytes, block_input) > 0xFFFFFFFFull - SAMREC_CHUNK) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^32 - 1 blocks in one call");
+    return SNAPGPU_OK;
+}
+static int bgzf_core(snapgpu_ctx *ctx, Stage &st, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t cap, void *d_out, void *d_member_begin,
+                     SamTextSummary *sum)
+{
+    BgzfArgs a; memset(&a, 0, sizeof(a));
+    a.n_bytes = n_bytes; a.block_input = block_input; a.n_members = (uint32_t)bgzf_members(n_bytes, block_input);
+    a.in = (const uint8_t *)d_in; a.cap = cap; a.out = (uint8_t *)d_out; a.member_begin = (uint64_t *)d_member_begin;
+    // a wavefront of the deflate launch holds BGZF_LDS_WORDS dwords of LDS: eight to a CU
+    uint32_t deflate_blocks = (uint32_t)ctx->num_cus * 4, scan_blocks = (uint32_t)ctx->num_cus * 8, place_blocks = scan_blocks;
+    if (deflate_blocks > a.n_members) deflate_blocks = a.n_members;
+    { const uint32_t need = (a.n_members + SAMREC_CHUNK - 1) / SAMREC_CHUNK; if (scan_blocks > (need + 3) / 4) scan_blocks = (need + 3) / 4; }
+    { const uint32_t need = (a.n_members + 3) / 4; if (place_blocks > need) place_blocks = need; }
+    a.tok_stride = (uint64_t)block_input + 1; a.slot_stride = ((uint64_t)block_input + 31 + 3) & ~(uint64_t)3;
+    a.tok = st.scratch((size_t)deflate_blocks * a.tok_stride * 4); a.slots = st.scratch((size_t)a.n_members * a.slot_stride);
+    a.size = st.scratch((size_t)a.n_members * 4 + 4); a.partial = st.scratch((size_t)((a.n_members + SAMREC_CHUNK - 1) / SAMREC_CHUNK) * 8);
+    a.summary = st.scratch(sizeof(SamTextSummary));
+    if (st.rc) return st.rc;
+    HIPCHK(ctx, hipMemsetAsync(a.summary, 0, sizeof(SamTextSummary), st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemsetAsync(a.slots, 0, (size_t)a.n_members * a.slot_stride, st.s), SNAPGPU_E_LAUNCH);      // (the bits of a member are ORed into its slot)
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
+    snapgpu_launch_bgzf(&a, deflate_blocks, scan_blocks, place_blocks, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemcpyAsync(sum, a.summary, sizeof(SamTextSummary), hipMemcpyDeviceToHost, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    return finish_timing(ctx);
+}
+extern "C" int snapgpu_bgzf_compress_device(snapgpu_ctx *ctx, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t out_capacity, void *d_out,
+                                            void *d_member_begin, uint64_t *n_members, uint64_t *out_bytes, void *stream)
+{
+    const std::string w("snapgpu_bgzf_compress_device");
+    if (!ctx || !n_members || !out_bytes || !d_member_begin || (out_capacity && !d_out) || (n_bytes && !d_in)) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    int rc = bgzf_check(ctx, w, n_bytes, block_input);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = bgzf_core(ctx, st, n_bytes, d_in, block_input, out_capacity, d_out, d_member_begin, &sum))) return rc;
+    *n_members = bgzf_members(n_bytes, block_input); *out_bytes = sum.total;
+    return sum.total > out_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+}
+extern "C" int snapgpu_bgzf_compress(snapgpu_ctx *ctx, uint64_t n_bytes, const uint8_t *in, uint32_t block_input, uint64_t out_capacity, uint8_t *out,
+                                     uint64_t *member_begin, uint64_t *n_members, uint64_t *out_bytes)
+{
+    const std::string w("snapgpu_bgzf_compress");
+    if (!ctx || !n_members || !out_bytes || !member_begin || (out_capacity && !out) || (n_bytes && !in)) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    int rc = bgzf_check(ctx, w, n_bytes, block_input);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, ctx->stream);
+    const uint64_t nm = bgzf_members(n_bytes, block_input);
+    const void *d_in = st.in(in, (size_t)n_bytes, 16);
+    void *d_out = st.out(out, (size_t)out_capacity), *d_member_begin = st.out(member_begin, ((size_t)nm + 1) * 8);
+    if (st.rc) return st.rc;
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = bgzf_core(ctx, st, n_bytes, d_in, block_input, out_capacity, d_out, d_member_begin, &sum))) return rc;
+    st.limit(d_out, (size_t)sum.written);                                // only the members that were written come down
+    if ((rc = st.download())) return rc;
+    *n_members = nm; *out_bytes = sum.total;
+    return sum.total > out_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
 // Diagnostics (not part of the drop-in surface): how many SamfPre records the row-loop pre-pass (k_samf_dp8 / k_samf_dp8_paired) of the context's
