@@ -56,6 +56,10 @@ struct StageTimer {
     explicit StageTimer(std::atomic<unsigned long long> &a) : acc(a), t0(std::chrono::steady_clock::now()) {}
     ~StageTimer() { acc += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
 };
+struct StageLap {                            // consecutive stages of one thread: lap(acc) adds the time since the previous lap
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(std::atomic<unsigned long long> &acc) { const auto t = std::chrono::steady_clock::now(); acc += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(t - t0).count(); t0 = t; }
+};
 static void die(const char *msg, const char *arg = "") {
     fprintf(stderr, "snapgpu-sam: %s%s\n", msg, arg);
     if (!g_partial_path.empty()) remove(g_partial_path.c_str());
@@ -268,23 +272,54 @@ struct Options {
     int passes = 1;                                                        // -passes N (measurement): stream the input N times over the resident index
     uint32_t ops_stride = 64;
     bool bam = false;                                                      // -o x.bam: BAM records in BGZF blocks (SNAPLib/Bam.cpp)
+    bool verbose = false, host_loop = false;                               // SNAPGPU_SAM_VERBOSE; SNAPGPU_SAM_HOST_LOOP (tests: every record of a multi-result paired batch through the host loop)
+    // The path a batch takes, chosen once (choose_paths) from the mode, the output kind, the options and five switches in the environment.
+    // Every path writes the same file (BGZF: the same members with other compressed payloads); the opt-in ones are off until they have been
+    // timed on a full-size input (DESIGN.md section 13 says what to measure).
+    //   `output`, who writes a batch's records     -o x.sam                               -o x.bam
+    //   single; paired without -om                 SNAPGPU_SAM_DEVICE_TEXT=1: DeviceText  SNAPGPU_SAM_DEVICE_BGZF=1: DeviceBgzf; else SNAPGPU_SAM_DEVICE_BAM=1: DeviceBam
+    //   paired with -om; no switch set             HostFormat                             HostFormat
+    //   DeviceText: the batch goes up as it was parsed, with its names, and its SAM lines come down (snapgpu_align_sam_single_text / _paired_text);
+    //   DeviceBam: its uncompressed BAM records (.._bam), which the formatter threads only compress; DeviceBgzf: its BGZF blocks (.._bgzf with
+    //   block_input 0xff00: a batch is one compression unit, cut where bgzf_append cuts it) -- the header and end-of-file blocks stay with zlib.
+    //   A paired batch in which -ea finds a first-ALT pair goes through the host path whatever `output` says.
+    //   With HostFormat, who computes the records' fields:
+    //   single, no -om / -ae        `single_one_call`: one call per group of batches (snapgpu_align_sam_single); a first-ALT record in the group: batch by batch
+    //   single, -om / -ae / -ea     SNAPGPU_SAM_SINGLE_FUSED=1: `single_records_call`, all records from snapgpu_align_sam_single_records; 0 or unset: -ea alone as
+    //                               the row above, -om / -ae through separate calls on the clipped reads that prepare_single gathers (`gather_for_aligner`)
+    //   paired, no -om              `paired_one_call` (snapgpu_align_sam_paired) unless SNAPGPU_SAM_PAIRED_FUSED=0, a measurement knob (unset: on);
+    //                               off, or with a first-ALT pair: snapgpu_align_paired + snapgpu_sam_fields_paired
+    //   paired, -om                 snapgpu_align_paired_secondary, then the records of each pair in rounds (PairedBatch::rounds)
+    //   `need_bam_ids`: BAM output with either BAM switch (paired -om too): the contexts get the contigs' BAM reference numbers.
+    enum Output { HostFormat, DeviceText, DeviceBam, DeviceBgzf };
+    struct Paths { Output output = HostFormat; bool single_one_call = false, single_records_call = false, paired_one_call = false, need_bam_ids = false, gather_for_aligner = false; } paths;
+};
+
+// the computed fields of a list of SAM records, cigars in rows of ops_stride (a row that was too short: n_ops -1 with nm -2)
+struct Records {
+    std::vector<int32_t> flag, contig, mapq, n_ops, nm; std::vector<int64_t> pos;
+    std::vector<uint32_t> ops; uint32_t ops_stride = 64;
+    void assign(size_t n) { flag.assign(n, 0); contig.assign(n, 0); mapq.assign(n, 0); n_ops.assign(n, 0); nm.assign(n, 0); pos.assign(n, 0); }     // (the cigar rows are with_growing_stride's)
+    void resize(size_t n) { flag.resize(n); contig.resize(n); mapq.resize(n); n_ops.resize(n); nm.resize(n); pos.resize(n); }
+    void clear() { assign(0); ops.clear(); ops_stride = 64; }
+    const uint32_t *cigar(size_t i) const { return ops.data() + i * (size_t)ops_stride; }
+    uint32_t *cigar(size_t i) { return ops.data() + i * (size_t)ops_stride; }
 };
 
 struct Work {                                // a batch on its way through the pipeline
     Batch b;
     // single-end: one entry per RECORD (a read with secondary results appears once per record); paired: one per read
     std::vector<uint32_t> rec_read; std::vector<char> rec_secondary;
-    std::vector<int32_t> flag, contig, mapq, n_ops, nm, rnext, first_written;
-    std::vector<int64_t> pos, pnext, tlen;
-    std::vector<uint32_t> ops; uint32_t ops_stride = 64;
+    Records rec;
+    std::vector<int32_t> rnext, first_written; std::vector<int64_t> pnext, tlen;
     // paired end: what to write, in order.  A "pair unit" is one PairedAlignmentResult of a pair (the primary, a secondary one, the first
-    // ALT one): two records, fields at [2u], [2u + 1] of the arrays above, first_written[u].  A "single unit" is one single-end secondary
-    // result of a mate (ReadWriter.cpp:508-590): one record, fields in the s_* arrays.
+    // ALT one): two records, fields at [2u], [2u + 1] of `rec` and of rnext / pnext / tlen, first_written[u].  A "single unit" is one
+    // single-end secondary result of a mate (ReadWriter.cpp:508-590): one record, fields in `srec`.
     struct Emit { uint32_t unit; uint8_t single; };
     std::vector<Emit> emit;
     std::vector<uint32_t> pu_pair; std::vector<char> pu_secondary;       // per pair unit: the pair it belongs to, flag 0x100
     std::vector<uint32_t> su_read;                                       // per single unit: the read (2 * pair + mate)
-    std::vector<int32_t> s_flag, s_contig, s_mapq, s_n_ops, s_nm; std::vector<int64_t> s_pos; std::vector<uint32_t> s_ops; uint32_t s_ops_stride = 64;
+    Records srec;
     // single end: what prepare_single() leaves for the feeder
     bool prepared = false;
     std::vector<int32_t> front_clip, data_len; std::vector<uint32_t> to_align; std::vector<char> ab, aq; std::vector<uint64_t> ao;
@@ -298,10 +333,8 @@ struct Work {                                // a batch on its way through the p
     // as newly constructed, but every vector keeps its capacity (WorkPool)
     void reset() {
         b.clear(); b.seq = 0;
-        rec_read.clear(); rec_secondary.clear(); flag.clear(); contig.clear(); mapq.clear(); n_ops.clear(); nm.clear(); rnext.clear(); first_written.clear();
-        pos.clear(); pnext.clear(); tlen.clear(); ops.clear(); ops_stride = 64;
+        rec_read.clear(); rec_secondary.clear(); rec.clear(); srec.clear(); rnext.clear(); first_written.clear(); pnext.clear(); tlen.clear();
         emit.clear(); pu_pair.clear(); pu_secondary.clear(); su_read.clear();
-        s_flag.clear(); s_contig.clear(); s_mapq.clear(); s_n_ops.clear(); s_nm.clear(); s_pos.clear(); s_ops.clear(); s_ops_stride = 64;
         prepared = false; front_clip.clear(); data_len.clear(); to_align.clear(); ab.clear(); aq.clear(); ao.clear(); skip.clear();
         max_len = 0; text.clear(); text_done = false; bgzf_done = false; bam = false; mapped = 0;
     }
@@ -516,26 +549,25 @@ struct FeederCtx {
     snapgpu_ctx *owner = NULL; int device = 0;                             // whose index blobs they share
 };
 static uint32_t class_len(const Options &o, int k) { return RL_CLASS[k] && RL_CLASS[k] < o.p.max_read_len ? RL_CLASS[k] : o.p.max_read_len; }
-static bool device_bam_switch(const Options &o);
 static void configure_ctx(const Options &o, snapgpu_ctx *c)
 {
     snapgpu_set_aligner_flags(c, o.stop_on_first_hit ? 1 : 0, o.explore_popular_seeds ? 1 : 0);      // -f, -x (single-end launches only)
     {   // RNAME of the SAM-line kernels (snapgpu_align_sam_single_text): the contig table in the index's order
         std::vector<const char *> names; for (const Contig &ct : *g_contigs) names.push_back(ct.name.c_str());
         int rc = snapgpu_set_contig_names(c, (uint32_t)names.size(), names.data());
-        if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_set_contig_names failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); }
+        if (rc != SNAPGPU_OK) fail_rc(c, "snapgpu_set_contig_names", rc);
     }
-    if (device_bam_switch(o)) {   // refID of the BAM-record kernels: the contigs' original numbers, which order the header's reference table (main checks that they are a permutation)
+    if (o.paths.need_bam_ids) {   // refID of the BAM-record kernels: the contigs' original numbers, which order the header's reference table (main checks that they are a permutation)
         std::vector<int32_t> ids; for (const Contig &ct : *g_contigs) ids.push_back(ct.orig);
         int rc = snapgpu_set_contig_bam_ids(c, (uint32_t)ids.size(), ids.data());
-        if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_set_contig_bam_ids failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); }
+        if (rc != SNAPGPU_OK) fail_rc(c, "snapgpu_set_contig_bam_ids", rc);
     }
-    if (o.paired) { int rc = snapgpu_enable_paired(c, &o.pp); if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_enable_paired failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); } }
+    if (o.paired) { int rc = snapgpu_enable_paired(c, &o.pp); if (rc != SNAPGPU_OK) fail_rc(c, "snapgpu_enable_paired", rc); }
     if (o.om >= 0) {
         snapgpu_secondary_params sp; memset(&sp, 0, sizeof(sp));
         sp.max_edit_distance = o.om; sp.max_per_contig = o.mpc; sp.max_results = o.omax; sp.adjust_alignments = o.ae ? 1u : 0u;
         int rc = snapgpu_enable_secondary(c, &sp);
-        if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_enable_secondary failed (%d): %s\n", rc, snapgpu_last_error(c)); exit(1); }
+        if (rc != SNAPGPU_OK) fail_rc(c, "snapgpu_enable_secondary", rc);
     }
 }
 static snapgpu_ctx *ctx_for(const Options &o, FeederCtx &f, uint32_t max_len)
@@ -547,78 +579,45 @@ static snapgpu_ctx *ctx_for(const Options &o, FeederCtx &f, uint32_t max_len)
     for (int j = 0; j < 3; j++) if (f.c[j] && class_len(o, j) == class_len(o, k)) return f.c[k] = f.c[j];
     snapgpu_params p = o.p; p.max_read_len = class_len(o, k);
     int rc = snapgpu_create_replica_with_params(f.owner, f.device, 1, &p, &f.c[k]);
-    if (rc != SNAPGPU_OK) { fprintf(stderr, "snapgpu-sam: snapgpu_create_replica_with_params failed (%d): %s\n", rc, snapgpu_last_error(f.owner)); exit(1); }
+    if (rc != SNAPGPU_OK) fail_rc(f.owner, "snapgpu_create_replica_with_params", rc);
     configure_ctx(o, f.c[k]);
     return f.c[k];
 }
-
+// the switches of Options::Paths, read once (an unset switch: `unset`; otherwise on unless it reads as 0)
+static bool env_switch(const char *name, bool unset) { const char *e = getenv(name); return e ? atoi(e) != 0 : unset; }
+static void choose_paths(Options &o)
+{
+    Options::Paths &p = o.paths;
+    const bool text = env_switch("SNAPGPU_SAM_DEVICE_TEXT", false), bgzf = env_switch("SNAPGPU_SAM_DEVICE_BGZF", false), bam = env_switch("SNAPGPU_SAM_DEVICE_BAM", false) || bgzf;
+    if (!(o.paired && o.om >= 0)) p.output = o.bam ? (bgzf ? Options::DeviceBgzf : bam ? Options::DeviceBam : Options::HostFormat) : (text ? Options::DeviceText : Options::HostFormat);
+    p.need_bam_ids = o.bam && bam;
+    p.single_records_call = !o.paired && env_switch("SNAPGPU_SAM_SINGLE_FUSED", false) && (o.om >= 0 || o.ae || o.p.emit_alt_alignments != 0);
+    p.paired_one_call = o.paired && o.om < 0 && env_switch("SNAPGPU_SAM_PAIRED_FUSED", true);
+    p.single_one_call = !o.paired && o.om < 0 && !o.ae && !p.single_records_call;
+    p.gather_for_aligner = !o.paired && !p.single_one_call && !p.single_records_call && p.output == Options::HostFormat;
+    o.verbose = getenv("SNAPGPU_SAM_VERBOSE") != NULL; o.host_loop = getenv("SNAPGPU_SAM_HOST_LOOP") != NULL;
+}
 // A cigar that does not fit ops_stride comes back as n_ops = -1 with nm = -2 (the reference's "cigarBuf too small" never happens: its
 // buffer is large): call again with a larger stride rather than print a wrong record.
-template <class F> static void with_growing_stride(Work &w, size_t n_rec, F call)
+static bool cigar_overflowed(const int32_t *nm, size_t n) { for (size_t i = 0; i < n; i++) if (nm[i] == -2) return true; return false; }
+static void grow_stride(uint32_t &stride) { if (stride >= 4096) die("a cigar needs more than 4096 operations"); stride *= 4; }
+template <class F> static void with_growing_stride(Records &r, size_t n_rec, F call)
 {
     for (;;) {
-        w.ops.assign(n_rec * (size_t)w.ops_stride, 0);
+        r.ops.assign(n_rec * (size_t)r.ops_stride, 0);
         call();
-        bool too_small = false;
-        for (size_t i = 0; i < n_rec; i++) if (w.nm[i] == -2) { too_small = true; break; }
-        if (!too_small) return;
-        if (w.ops_stride >= 4096) die("a cigar needs more than 4096 operations");
-        w.ops_stride *= 4;
+        if (!cigar_overflowed(r.nm.data(), n_rec)) return;
+        grow_stride(r.ops_stride);
     }
 }
-
-// `single` with -om / -omax / -mpc / -ea / -ae: every record of every read from ONE call (snapgpu_align_sam_single_records) -- the batch goes up
-// as it was parsed and the records come down ready to print; no clipped copy, no second call for -ae, no results coming back to be expanded
-// into a record batch and sent up again.  The files are the same bytes either way (tests/test_zz_gpu_sam_single_records.py).
-// SNAPGPU_SAM_SINGLE_FUSED=1 turns it on, =0 (and, for now, unset) keeps the calls it replaces: the one-call path has not been timed against
-// them on the hardware yet (DESIGN.md section 13 says what to measure), and an untimed path does not become the tool's default.
-static bool single_records_path(const Options &o)
-{
-    static const bool fused_on = getenv("SNAPGPU_SAM_SINGLE_FUSED") && atoi(getenv("SNAPGPU_SAM_SINGLE_FUSED")) != 0;
-    return fused_on && !o.paired && (o.om >= 0 || o.ae || o.p.emit_alt_alignments != 0);
-}
-// SNAPGPU_SAM_DEVICE_TEXT=1: `single` with SAM output takes the LINES of a batch from the device (snapgpu_align_sam_single_text, every option
-// set) and the formatter threads pass the batch through.  Off unless asked for: DESIGN.md section 13 has what to measure before that changes.
-// BAM output does not have the path and ignores the switch.  The file is the same bytes either way (tests/test_zz_gpu_sam_text.py).
-static bool device_text_path(const Options &o)
-{
-    static const bool on = getenv("SNAPGPU_SAM_DEVICE_TEXT") && atoi(getenv("SNAPGPU_SAM_DEVICE_TEXT")) != 0;
-    return on && !o.paired && !o.bam;
-}
-// The same switch for `paired` with SAM output: the batches of the one-call path (no -om) take their lines from snapgpu_align_sam_paired_text;
-// a batch in which -ea finds a first-ALT pair goes through the host path as it does without the switch.  -om ignores the switch.  Same file
-// (tests/test_zz_gpu_sam_text_paired.py).
-static bool device_text_paired_path(const Options &o)
-{
-    static const bool on = getenv("SNAPGPU_SAM_DEVICE_TEXT") && atoi(getenv("SNAPGPU_SAM_DEVICE_TEXT")) != 0;
-    return on && o.paired && !o.bam && o.om < 0;
-}
-// SNAPGPU_SAM_DEVICE_BAM=1: the same two paths for BAM output -- the uncompressed RECORDS of a batch come from the device
-// (snapgpu_align_sam_single_bam, every option set; snapgpu_align_sam_paired_bam, no -om, first-ALT batches through the host path) and the
-// formatter threads only compress them.  A switch of its own: SNAPGPU_SAM_DEVICE_TEXT keeps ignoring BAM.  Off unless asked for (DESIGN.md
-// section 13); SAM output ignores it.  The file is the same bytes either way (tests/test_zz_gpu_sam_bam.py).
-// SNAPGPU_SAM_DEVICE_BGZF=1: the same two paths again, and the batch's BGZF blocks come from the device as well (snapgpu_align_sam_single_bgzf /
-// snapgpu_align_sam_paired_bgzf with block_input 0xff00: a batch is one compression unit cut where bgzf_append cuts it): the formatter threads
-// pass the batch through and the writer writes it.  The header block, the end-of-file block and first-ALT batches of pairs stay with the host's
-// zlib.  The file has the members of the switch-off file with other compressed payloads (tests/test_zz_gpu_bgzf.py).  Off unless asked for.
-static bool device_bgzf_switch(const Options &o)
-{
-    static const bool on = getenv("SNAPGPU_SAM_DEVICE_BGZF") && atoi(getenv("SNAPGPU_SAM_DEVICE_BGZF")) != 0;
-    return on && o.bam;
-}
-static bool device_bam_switch(const Options &o)
-{
-    static const bool on = getenv("SNAPGPU_SAM_DEVICE_BAM") && atoi(getenv("SNAPGPU_SAM_DEVICE_BAM")) != 0;
-    return (on && o.bam) || device_bgzf_switch(o);
-}
-static bool device_bam_path(const Options &o) { return device_bam_switch(o) && !o.paired; }
-static bool device_bam_paired_path(const Options &o) { return device_bam_switch(o) && o.paired && o.om < 0; }
 static std::atomic<unsigned long long> g_bam_batches(0), g_bam_records(0);      // what the device-BAM paths produced (the line on stderr at the end)
 static std::atomic<unsigned long long> g_bgzf_batches(0), g_bgzf_members(0), g_bgzf_in(0), g_bgzf_out(0);      // what SNAPGPU_SAM_DEVICE_BGZF produced (its line on stderr)
 static std::atomic<uint32_t> g_bgzf_per_mille(500);             // BGZF capacity of the next call, in thousandths of the record-byte estimate: grows to what batches have needed
 static std::atomic<uint32_t> g_text_extra_per_record(128);      // text capacity of the next call: bytes per record beyond its name, SEQ and QUAL; grows to what batches have needed
 static std::atomic<uint32_t> g_records_per_read_x16(24);        // record capacity of the next call, in sixteenths of a record per read: grows to what batches have needed
-
+static void raise_to(std::atomic<uint32_t> &a, uint32_t need) { uint32_t cur = a.load(); while (need > cur && !a.compare_exchange_weak(cur, need)) {} }
+static size_t record_capacity(size_t n_reads) { return (n_reads * (size_t)g_records_per_read_x16.load() + 15) / 16 + 16; }
+static void records_needed(size_t n_rec, size_t n_reads) { raise_to(g_records_per_read_x16, (uint32_t)((n_rec * 16 + n_reads - 1) / n_reads) + 2); }
 // Read::clip and the useless-read filter for a batch, and the reads to align gathered into one buffer: host work that does not need the GPU,
 // done by the parser threads where there are several (the feeder threads' time belongs to the device)
 static void prepare_single(const Options &o, Work &w)
@@ -626,8 +625,8 @@ static void prepare_single(const Options &o, Work &w)
     const Batch &b = w.b;
     const size_t n = b.n();
     w.front_clip.assign(n, 0); w.data_len.assign(n, 0); w.skip.assign(n, 1); w.to_align.clear(); w.ab.clear(); w.aq.clear(); w.ao.assign(1, 0);
-    const bool fused = (o.om < 0 && !o.ae) || single_records_path(o) || device_text_path(o) || device_bam_path(o);      // gpu_single's one-call paths work on the batch itself: nothing to gather
-    if (!fused) { w.ab.reserve(b.bases.size()); w.aq.reserve(b.quals.size()); w.ao.reserve(n + 1); }
+    const bool gather = o.paths.gather_for_aligner;      // (the one-call paths work on the batch itself: nothing to gather)
+    if (gather) { w.ab.reserve(b.bases.size()); w.aq.reserve(b.quals.size()); w.ao.reserve(n + 1); }
     w.to_align.reserve(n);
     w.max_len = 0;
     for (size_t i = 0; i < n; i++) {
@@ -635,254 +634,273 @@ static void prepare_single(const Options &o, Work &w)
         if (U > w.max_len) w.max_len = U;
         if (clip_read(o, b, i, w.front_clip[i], w.data_len[i])) {
             w.to_align.push_back((uint32_t)i); w.skip[i] = 0;
-            if (fused) continue;
+            if (!gather) continue;
             const char *q = b.quals.data() + b.offsets[i] + w.front_clip[i], *s = b.bases.data() + b.offsets[i] + w.front_clip[i];
             w.ab.insert(w.ab.end(), s, s + w.data_len[i]); w.aq.insert(w.aq.end(), q, q + w.data_len[i]); w.ao.push_back(w.ab.size());
         }
     }
     w.prepared = true;
 }
-
 static bool g_index_has_alt = false;        // the index has ALT contigs: only then can a first-ALT result (an extra record) exist
-// SNAPGPU_SAM_DEVICE_TEXT / SNAPGPU_SAM_DEVICE_BAM: the batch goes up as it was parsed, with its names, and its SAM lines (BAM output: its
-// uncompressed BAM records, which are shorter than the lines, so the same estimate has room for them) come down.  Both capacities start from an
-// estimate and follow what the library reports; a cigar that outgrows its row is met with a larger row, as with_growing_stride does.
+// The adjuster (-ae) is restated for reads the reader has not clipped (adjust.h): the reference settles a contig-end overhang on the
+// UNCLIPPED buffer (AlignmentAdjuster.cpp:167), which only differs for a clipped read that hangs over the end of its contig.  Such a
+// read is refused rather than answered differently (-C-- switches the reader's clipping off): by the library in its one-call paths
+// (SNAPGPU_E_UNSUPPORTED, "-ae: ..."), by refuse_ae_at_contig_end after the separate calls.
+static const char AE_REFUSAL[] = "-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)";
+static void die_if_ae_refused(const Options &o, snapgpu_ctx *ctx, int rc)
+{
+    if (rc == SNAPGPU_E_UNSUPPORTED && o.ae && !strncmp(snapgpu_last_error(ctx), "-ae:", 4)) die(AE_REFUSAL);
+}
+// Options::DeviceText / DeviceBam / DeviceBgzf: the batch goes up as it was parsed, with its names, and its SAM lines (BAM output: its
+// uncompressed BAM records, which are shorter than the lines, so the same estimate has room for them; or their BGZF blocks) come down into
+// w.text, the records' flags into w.rec.flag.  The capacities start from estimates and follow what the library reports; a cigar that
+// outgrows its row is met with a larger row, as with_growing_stride does.  `call(DeviceCall &)` makes the ABI call `<stem>_text`, `_bam` or
+// `_bgzf`.  `rec_cap` is the first record capacity or, with `fixed_records` (pairs), the record count itself, which the call does not report.
+// `discard()` is asked once the call has succeeded: true sends the batch through the host path after all (false is returned, w.text is empty).
+struct DeviceCall {                          // one attempt: the capacities the call is given (`begin`: line_begin or, DeviceBgzf, member_begin) and what it reports
+    uint32_t ops_stride; uint64_t rec_cap, text_cap, bgzf_cap, *begin, max_members;
+    uint64_t n_rec, text_bytes, n_members, bgzf_bytes;
+};
 // a batch whose blocks came from the device: the counts of the line on stderr, and the next batch's capacity (est: this batch's record-byte estimate)
 static void bgzf_from_device(Work &w, size_t est, uint64_t n_members, uint64_t in_bytes, uint64_t out_bytes)
 {
     w.bgzf_done = true;
     g_bgzf_batches++; g_bgzf_members += n_members; g_bgzf_in += in_bytes; g_bgzf_out += out_bytes;
-    const uint32_t need = (uint32_t)(out_bytes * 1000 / (est ? est : 1)) + 20;
-    uint32_t cur = g_bgzf_per_mille.load(); while (need > cur && !g_bgzf_per_mille.compare_exchange_weak(cur, need)) {}
+    raise_to(g_bgzf_per_mille, (uint32_t)(out_bytes * 1000 / (est ? est : 1)) + 20);
+}
+template <class Call, class Discard>
+static bool device_output(const Options &o, snapgpu_ctx *ctx, Work &w, const char *stem, size_t rec_cap, bool fixed_records, Call call, Discard discard)
+{
+    const Batch &b = w.b;
+    const size_t n = b.n();
+    const bool bgzf = o.paths.output == Options::DeviceBgzf;
+    const size_t per_read = (2 * b.bases.size() + b.names.size() + n - 1) / n;             // name, SEQ and QUAL of the average record (pairs: both readers make n even, a record per read)
+    size_t cap = rec_cap, tcap = cap * (per_read + g_text_extra_per_record.load());
+    size_t zcap = tcap / 1000 * g_bgzf_per_mille.load() + 64;
+    std::vector<uint64_t> begin;
+    DeviceCall c; memset(&c, 0, sizeof(c));
+    c.ops_stride = o.ops_stride;
+    for (;;) {
+        w.rec.flag.resize(cap); begin.resize(bgzf ? tcap / 0xff00 + 2 : cap + 1); w.text.resize(bgzf ? zcap : tcap);
+        if (fixed_records) c.n_rec = cap;
+        c.rec_cap = cap; c.text_cap = tcap; c.bgzf_cap = zcap; c.begin = begin.data(); c.max_members = begin.size() - 1;
+        const int rc = call(c);
+        die_if_ae_refused(o, ctx, rc);
+        if (rc == SNAPGPU_W_RECORDS_TRUNCATED) { cap = (size_t)c.n_rec + (size_t)c.n_rec / 16; tcap = cap * (per_read + g_text_extra_per_record.load()); continue; }
+        if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)c.text_bytes + (size_t)c.text_bytes / 64; if (c.bgzf_bytes > zcap) zcap = (size_t)c.bgzf_bytes + (size_t)c.bgzf_bytes / 64; continue; }
+        if (rc == SNAPGPU_E_INVALID && strstr(snapgpu_last_error(ctx), "ops_stride")) { grow_stride(c.ops_stride); continue; }
+        if (rc != SNAPGPU_OK) fail_rc(ctx, (std::string(stem) + (bgzf ? "_bgzf" : o.bam ? "_bam" : "_text")).c_str(), rc);
+        break;
+    }
+    if (discard()) { w.text.clear(); return false; }
+    const size_t nr = (size_t)c.n_rec;
+    if (o.bam) { g_bam_batches++; g_bam_records += nr; }
+    if (!fixed_records) records_needed(nr, n);
+    if (nr) { const size_t per_rec = ((size_t)c.text_bytes + nr - 1) / nr; raise_to(g_text_extra_per_record, per_rec > per_read ? (uint32_t)(per_rec - per_read) + 16 : 16); }
+    w.text.resize((size_t)(bgzf ? c.bgzf_bytes : c.text_bytes)); w.text_done = true; w.mapped = 0;
+    if (bgzf) bgzf_from_device(w, tcap, c.n_members, c.text_bytes, c.bgzf_bytes);
+    for (size_t r = 0; r < nr; r++) w.mapped += (w.rec.flag[r] & 0x4) == 0;
+    return true;
 }
 static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
 {
-    auto t_stage = std::chrono::steady_clock::now();
-    auto lap = [&](std::atomic<unsigned long long> &acc) { const auto t = std::chrono::steady_clock::now(); acc += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(t - t_stage).count(); t_stage = t; };
+    StageLap lap;
     const Batch &b = w.b;
     const size_t n = b.n();
     w.text.clear(); w.text_done = true; w.mapped = 0;
     if (n == 0) return;
     if (!w.prepared) prepare_single(o, w);
     snapgpu_ctx *ctx = ctx_for(o, fc, w.max_len);
-    std::vector<uint64_t> name_off(b.name_off.begin(), b.name_off.end()), rec_begin(n + 1), line_begin;
-    size_t cap = (n * (size_t)g_records_per_read_x16.load() + 15) / 16 + 16;
-    const size_t per_read = (2 * b.bases.size() + b.names.size() + n - 1) / n;             // name, SEQ and QUAL of the average record
-    size_t tcap = cap * (per_read + g_text_extra_per_record.load());
-    uint32_t ops_stride = o.ops_stride;
-    uint64_t n_rec = 0, text_bytes = 0, n_mem = 0, z_bytes = 0;
-    const bool bgzf = device_bgzf_switch(o);
-    size_t zcap = tcap / 1000 * g_bgzf_per_mille.load() + 64;
+    std::vector<uint64_t> name_off(b.name_off.begin(), b.name_off.end()), rec_begin(n + 1);
+    const int use_m = o.use_m ? 1 : 0, adjust_primary = (o.ae && o.om < 0) ? 1 : 0;
     lap(g_ns_prep);
-    for (;;) {
-        w.flag.resize(cap); line_begin.resize(bgzf ? tcap / 0xff00 + 2 : cap + 1); w.text.resize(bgzf ? zcap : tcap);
-        const int rc = bgzf
+    device_output(o, ctx, w, "snapgpu_align_sam_single", record_capacity(n), false, [&](DeviceCall &c) {
+        return o.paths.output == Options::DeviceBgzf
             ? snapgpu_align_sam_single_bgzf(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
-                                            w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
-                                            (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), 0xff00, (uint64_t)zcap, (uint8_t *)&w.text[0], line_begin.data(),
-                                            (uint64_t)line_begin.size() - 1, &n_mem, &z_bytes, &text_bytes)
-            : o.bam
+                                            w.skip.data(), use_m, adjust_primary, b.names.data(), name_off.data(), c.ops_stride,
+                                            c.rec_cap, &c.n_rec, rec_begin.data(), w.rec.flag.data(), 0xff00, c.bgzf_cap, (uint8_t *)&w.text[0], c.begin,
+                                            c.max_members, &c.n_members, &c.bgzf_bytes, &c.text_bytes)
+            : o.paths.output == Options::DeviceBam
             ? snapgpu_align_sam_single_bam(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
-                                           w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
-                                           (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), (uint64_t)tcap, (uint8_t *)&w.text[0], line_begin.data(), &text_bytes)
+                                           w.skip.data(), use_m, adjust_primary, b.names.data(), name_off.data(), c.ops_stride,
+                                           c.rec_cap, &c.n_rec, rec_begin.data(), w.rec.flag.data(), c.text_cap, (uint8_t *)&w.text[0], c.begin, &c.text_bytes)
             : snapgpu_align_sam_single_text(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
-                                            w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
-                                            (uint64_t)cap, &n_rec, rec_begin.data(), w.flag.data(), (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
-        if (rc == SNAPGPU_E_UNSUPPORTED && o.ae && !strncmp(snapgpu_last_error(ctx), "-ae:", 4))
-            die("-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)");
-        if (rc == SNAPGPU_W_RECORDS_TRUNCATED) { cap = (size_t)n_rec + (size_t)n_rec / 16; tcap = cap * (per_read + g_text_extra_per_record.load()); continue; }
-        if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; if (z_bytes > zcap) zcap = (size_t)z_bytes + (size_t)z_bytes / 64; continue; }
-        if (rc == SNAPGPU_E_INVALID && strstr(snapgpu_last_error(ctx), "ops_stride")) {
-            if (ops_stride >= 4096) die("a cigar needs more than 4096 operations");
-            ops_stride *= 4; continue;
-        }
-        if (rc != SNAPGPU_OK) fail_rc(ctx, bgzf ? "snapgpu_align_sam_single_bgzf" : o.bam ? "snapgpu_align_sam_single_bam" : "snapgpu_align_sam_single_text", rc);
-        break;
-    }
-    const size_t nr = (size_t)n_rec;
-    if (o.bam) { g_bam_batches++; g_bam_records += nr; }
-    { const uint32_t need = (uint32_t)((nr * 16 + n - 1) / n) + 2; uint32_t cur = g_records_per_read_x16.load(); while (need > cur && !g_records_per_read_x16.compare_exchange_weak(cur, need)) {} }
-    if (nr) { const size_t per_rec = ((size_t)text_bytes + nr - 1) / nr; const uint32_t need = per_rec > per_read ? (uint32_t)(per_rec - per_read) + 16 : 16;
-              uint32_t cur = g_text_extra_per_record.load(); while (need > cur && !g_text_extra_per_record.compare_exchange_weak(cur, need)) {} }
-    w.text.resize((size_t)(bgzf ? z_bytes : text_bytes));
-    if (bgzf) bgzf_from_device(w, tcap, n_mem, text_bytes, z_bytes);
-    for (size_t r = 0; r < nr; r++) w.mapped += (w.flag[r] & 0x4) == 0;
+                                            w.skip.data(), use_m, adjust_primary, b.names.data(), name_off.data(), c.ops_stride,
+                                            c.rec_cap, &c.n_rec, rec_begin.data(), w.rec.flag.data(), c.text_cap, &w.text[0], c.begin, &c.text_bytes);
+    }, [] { return false; });
     lap(g_ns_align);
 }
-static void gpu_single(const Options &o, FeederCtx &fc, Work &w)
+
+// secondary results, -ae, -ea: all records in ONE call -- no clipped copy, no second call for -ae, no results expanded on the host and sent up again
+static void single_records_call(const Options &o, snapgpu_ctx *ctx, Work &w, StageLap &lap)
 {
-    auto t_stage = std::chrono::steady_clock::now();
-    auto lap = [&](std::atomic<unsigned long long> &acc) { const auto t = std::chrono::steady_clock::now(); acc += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(t - t_stage).count(); t_stage = t; };
     const Batch &b = w.b;
     const size_t n = b.n();
-    if (!w.prepared) prepare_single(o, w);            // (the parser threads of the mapped reader have done it already)
-    snapgpu_ctx *ctx = ctx_for(o, fc, w.max_len);
-    // ---- secondary results, -ae, -ea: all records in ONE call (snapgpu_align_sam_single_records)
-    if (single_records_path(o) && n > 0) {
-        w.ops_stride = o.ops_stride;
-        std::vector<uint64_t> rec_begin(n + 1);
-        std::vector<uint8_t> kind;
-        std::vector<int32_t> stale;
-        uint64_t n_rec = 0;
-        size_t cap = (n * (size_t)g_records_per_read_x16.load() + 15) / 16 + 16;
-        lap(g_ns_prep);
-        for (;;) {
-            w.rec_read.resize(cap); kind.resize(cap); stale.resize(cap);
-            w.flag.resize(cap); w.contig.resize(cap); w.mapq.resize(cap); w.n_ops.resize(cap); w.nm.resize(cap); w.pos.resize(cap);
-            w.ops.assign(cap * (size_t)w.ops_stride, 0);
-            const int rc2 = snapgpu_align_sam_single_records(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
-                                                             w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, NULL, NULL, NULL, 0, NULL, (uint64_t)cap, &n_rec,
-                                                             rec_begin.data(), w.rec_read.data(), kind.data(), w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(),
-                                                             w.ops.data(), w.ops_stride, w.n_ops.data(), w.nm.data(), stale.data());
-            if (rc2 == SNAPGPU_E_UNSUPPORTED && o.ae && !strncmp(snapgpu_last_error(ctx), "-ae:", 4))
-                die("-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)");
-            if (rc2 == SNAPGPU_W_RECORDS_TRUNCATED) { cap = (size_t)n_rec + (size_t)n_rec / 16; continue; }       // (rare: the capacity follows what batches need)
-            if (rc2 != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_single_records", rc2);
-            bool too_small = false;
-            for (size_t i = 0; i < (size_t)n_rec && !too_small; i++) too_small = w.nm[i] == -2;
-            if (!too_small) break;
-            if (w.ops_stride >= 4096) die("a cigar needs more than 4096 operations");
-            w.ops_stride *= 4;
-        }
-        const size_t nr = (size_t)n_rec;
-        { const uint32_t need = (uint32_t)((nr * 16 + n - 1) / n) + 2; uint32_t cur = g_records_per_read_x16.load(); while (need > cur && !g_records_per_read_x16.compare_exchange_weak(cur, need)) {} }
-        w.rec_read.resize(nr); w.flag.resize(nr); w.contig.resize(nr); w.mapq.resize(nr); w.n_ops.resize(nr); w.nm.resize(nr); w.pos.resize(nr);
-        w.ops.resize(nr * (size_t)w.ops_stride);
-        w.rec_secondary.resize(nr); for (size_t r = 0; r < nr; r++) w.rec_secondary[r] = kind[r] != 0;      // (0x100 is in the flags already)
-        lap(g_ns_align);
-        return;
+    w.rec.ops_stride = o.ops_stride;
+    std::vector<uint64_t> rec_begin(n + 1);
+    std::vector<uint8_t> kind;
+    std::vector<int32_t> stale;
+    uint64_t n_rec = 0;
+    size_t cap = record_capacity(n);
+    lap(g_ns_prep);
+    for (;;) {
+        w.rec_read.resize(cap); kind.resize(cap); stale.resize(cap); w.rec.resize(cap);
+        w.rec.ops.assign(cap * (size_t)w.rec.ops_stride, 0);
+        const int rc = snapgpu_align_sam_single_records(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
+                                                        w.skip.data(), o.use_m ? 1 : 0, (o.ae && o.om < 0) ? 1 : 0, NULL, NULL, NULL, 0, NULL, (uint64_t)cap, &n_rec,
+                                                        rec_begin.data(), w.rec_read.data(), kind.data(), w.rec.flag.data(), w.rec.contig.data(), w.rec.pos.data(), w.rec.mapq.data(),
+                                                        w.rec.ops.data(), w.rec.ops_stride, w.rec.n_ops.data(), w.rec.nm.data(), stale.data());
+        die_if_ae_refused(o, ctx, rc);
+        if (rc == SNAPGPU_W_RECORDS_TRUNCATED) { cap = (size_t)n_rec + (size_t)n_rec / 16; continue; }       // (rare: the capacity follows what batches need)
+        if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_single_records", rc);
+        if (!cigar_overflowed(w.rec.nm.data(), (size_t)n_rec)) break;
+        grow_stride(w.rec.ops_stride);
     }
-    // ---- the common case in ONE call (snapgpu_align_sam_single): no secondary results, no -ae; one record per read unless a first-ALT result turns up
-    std::vector<snapgpu_single_result> fused_res, fused_alt;
-    bool fused_done = false;
-    if (o.om < 0 && !o.ae && n > 0) {
-        const bool want_alt = o.p.alt_awareness && g_index_has_alt;
-        if (want_alt) { fused_res.resize(n); fused_alt.resize(n); }
-        w.rec_read.resize(n); for (size_t i = 0; i < n; i++) w.rec_read[i] = (uint32_t)i;
-        w.rec_secondary.assign(n, 0);
-        w.flag.assign(n, 0); w.contig.assign(n, 0); w.mapq.assign(n, 0); w.n_ops.assign(n, 0); w.nm.assign(n, 0); w.pos.assign(n, 0);
-        std::vector<int32_t> stale(n);
-        w.ops_stride = o.ops_stride;
-        lap(g_ns_prep);
-        with_growing_stride(w, n, [&] {
-            int rc2 = snapgpu_align_sam_single(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(), w.skip.data(),
-                                               o.use_m ? 1 : 0, want_alt ? fused_res.data() : NULL, want_alt ? fused_alt.data() : NULL,
-                                               w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(), w.ops.data(), w.ops_stride, w.n_ops.data(), w.nm.data(), stale.data());
-            if (rc2 != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_single", rc2);
-        });
-        lap(g_ns_align);
-        bool any_alt = false;
-        if (want_alt) for (size_t i = 0; i < n && !any_alt; i++) any_alt = !w.skip[i] && fused_alt[i].status != SNAPGPU_NotFound;
-        if (!any_alt) return;
-        fused_done = true;                             // (rare: ALT records to add -- the records are built below from the results, as after the two-call path)
-    }
-    std::vector<int32_t> &front_clip = w.front_clip, &data_len = w.data_len;
-    std::vector<uint32_t> &to_align = w.to_align;
-    std::vector<char> &ab = w.ab, &aq = w.aq; std::vector<uint64_t> &ao = w.ao;
-    std::vector<snapgpu_single_result> results(n), aligned_res(to_align.size()), alt_res(to_align.size());
-    for (size_t i = 0; i < n; i++) {                                       // SingleAligner.cpp:215-225
-        memset(&results[i], 0, sizeof(results[i]));
-        results[i].status = SNAPGPU_NotFound; results[i].location = SNAPGPU_InvalidGenomeLocation32; results[i].score = -1;
-    }
-    // records to write: every read's primary, then its secondary results in the aligner's order (SingleAligner.cpp:300-318 -> writeReads)
-    std::vector<snapgpu_single_result> rec_res;
+    const size_t nr = (size_t)n_rec;
+    records_needed(nr, n);
+    w.rec_read.resize(nr); w.rec.resize(nr); w.rec.ops.resize(nr * (size_t)w.rec.ops_stride);
+    w.rec_secondary.resize(nr); for (size_t r = 0; r < nr; r++) w.rec_secondary[r] = kind[r] != 0;      // (0x100 is in the flags already)
+    lap(g_ns_align);
+}
+// the records of a batch as results, in the order they are written: every read's primary, then its secondary results in the aligner's
+// order, then its first-ALT result (SingleAligner.cpp:300-322 -> writeReads); w.rec_read / w.rec_secondary beside them
+typedef std::vector<snapgpu_single_result> ResultList;
+static void add_record(Work &w, ResultList &rec_res, size_t read, bool secondary, const snapgpu_single_result &r) { w.rec_read.push_back((uint32_t)read); w.rec_secondary.push_back(secondary ? 1 : 0); rec_res.push_back(r); }
+static snapgpu_single_result not_found_result()                                // SingleAligner.cpp:215-225
+{
+    snapgpu_single_result r; memset(&r, 0, sizeof(r));
+    r.status = SNAPGPU_NotFound; r.location = SNAPGPU_InvalidGenomeLocation32; r.score = -1;
+    return r;
+}
+// the common case in ONE call (snapgpu_align_sam_single): no secondary results, no -ae; one record per read unless a first-ALT result
+// turns up.  True when the batch is finished; otherwise (rare) rec_res has the records to compute, ALT ones included, as after the separate calls
+static bool single_one_call(const Options &o, snapgpu_ctx *ctx, Work &w, StageLap &lap, ResultList &rec_res)
+{
+    const Batch &b = w.b;
+    const size_t n = b.n();
+    const bool want_alt = o.p.alt_awareness && g_index_has_alt;
+    ResultList res, alt;
+    if (want_alt) { res.resize(n); alt.resize(n); }
+    w.rec_read.resize(n); for (size_t i = 0; i < n; i++) w.rec_read[i] = (uint32_t)i;
+    w.rec_secondary.assign(n, 0);
+    w.rec.assign(n);
+    std::vector<int32_t> stale(n);
+    w.rec.ops_stride = o.ops_stride;
+    lap(g_ns_prep);
+    with_growing_stride(w.rec, n, [&] {
+        int rc = snapgpu_align_sam_single(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(), w.skip.data(),
+                                          o.use_m ? 1 : 0, want_alt ? res.data() : NULL, want_alt ? alt.data() : NULL,
+                                          w.rec.flag.data(), w.rec.contig.data(), w.rec.pos.data(), w.rec.mapq.data(), w.rec.ops.data(), w.rec.ops_stride, w.rec.n_ops.data(), w.rec.nm.data(), stale.data());
+        if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_single", rc);
+    });
+    lap(g_ns_align);
+    bool any_alt = false;
+    if (want_alt) for (size_t i = 0; i < n && !any_alt; i++) any_alt = !w.skip[i] && alt[i].status != SNAPGPU_NotFound;
+    if (!any_alt) return true;
     w.rec_read.clear(); w.rec_secondary.clear();
-    int rc;
-    if (fused_done) {                                  // the alignment is done: results per read, straight from the one call
-        for (size_t i = 0; i < n; i++) {
-            if (!w.skip[i]) results[i] = fused_res[i];
-            w.rec_read.push_back((uint32_t)i); w.rec_secondary.push_back(0); rec_res.push_back(results[i]);
-            if (!w.skip[i] && fused_alt[i].status != SNAPGPU_NotFound) { w.rec_read.push_back((uint32_t)i); w.rec_secondary.push_back(1); rec_res.push_back(fused_alt[i]); }
-        }
-    } else if (!to_align.empty()) {
-        std::vector<snapgpu_single_result> sec; std::vector<uint32_t> nsec(to_align.size(), 0);
-        uint32_t stride = 0;
+    for (size_t i = 0; i < n; i++) {
+        add_record(w, rec_res, i, false, w.skip[i] ? not_found_result() : res[i]);
+        if (!w.skip[i] && alt[i].status != SNAPGPU_NotFound) add_record(w, rec_res, i, true, alt[i]);
+    }
+    return false;
+}
+static void refuse_ae_at_contig_end(const Options &o, const Work &w, size_t read, const snapgpu_single_result &r)
+{
+    if (r.status == SNAPGPU_NotFound) return;
+    const int c = h_contig_at(r.location);
+    if (c >= 0 && r.location + w.data_len[read] + (long long)o.p.max_k + 2 > h_contig_end(c) - (long long)g_padding) die(AE_REFUSAL);
+}
+// -om / -ae in separate calls: the clipped reads prepare_single gathered go to the aligner and the results are expanded into rec_res
+static void single_separate_calls(const Options &o, snapgpu_ctx *ctx, Work &w, StageLap &lap, ResultList &rec_res)
+{
+    const Batch &b = w.b;
+    const size_t n = b.n(), na = w.to_align.size();
+    ResultList aligned_res(na), alt_res(na), sec; std::vector<uint32_t> nsec(na, 0);
+    uint32_t stride = 0;
+    if (na > 0) {
+        int rc;
         lap(g_ns_prep);
-        if (o.om >= 0) {
+        if (o.om >= 0) {                     // (-ae with -om: the adjuster runs inside the call, on the primary AND on every secondary result: finalizeSecondaryResults, BaseAligner.cpp:2444-2463)
             stride = 8;
             for (;;) {
-                sec.assign((size_t)to_align.size() * stride, snapgpu_single_result());
-                rc = snapgpu_align_single_secondary(ctx, (uint32_t)to_align.size(), ab.data(), aq.data(), ao.data(), aligned_res.data(), alt_res.data(),
-                                                    sec.data(), stride, nsec.data());
+                sec.assign(na * stride, snapgpu_single_result());
+                rc = snapgpu_align_single_secondary(ctx, (uint32_t)na, w.ab.data(), w.aq.data(), w.ao.data(), aligned_res.data(), alt_res.data(), sec.data(), stride, nsec.data());
                 if (rc != SNAPGPU_W_SECONDARY_TRUNCATED) break;
                 uint32_t need = stride; for (uint32_t v : nsec) if (v > need) need = v;
                 stride = need;
             }
-            // -ae with -om: the adjuster ran inside the call (finalizeSecondaryResults, BaseAligner.cpp:2444-2463) on the primary AND on
-            // every secondary result, with the limitation described below for the primary: refuse the same reads here
-            for (size_t a = 0; o.ae && rc == SNAPGPU_OK && a < to_align.size(); a++) {
-                const size_t i = to_align[a];
-                if (front_clip[i] == 0 && (uint64_t)data_len[i] == b.offsets[i + 1] - b.offsets[i]) continue;      // the reader clipped nothing
-                for (uint32_t j = 0; j <= (nsec[a] < stride ? nsec[a] : stride); j++) {
-                    const snapgpu_single_result &r = j == 0 ? aligned_res[a] : sec[a * (size_t)stride + (j - 1)];
-                    if (r.status == SNAPGPU_NotFound) continue;
-                    const int c = h_contig_at(r.location);
-                    if (c >= 0 && r.location + data_len[i] + (long long)o.p.max_k + 2 > h_contig_end(c) - (long long)g_padding)
-                        die("-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)");
-                }
-            }
         } else {
-            rc = snapgpu_align_single(ctx, (uint32_t)to_align.size(), ab.data(), aq.data(), ao.data(), aligned_res.data(), alt_res.data());
+            rc = snapgpu_align_single(ctx, (uint32_t)na, w.ab.data(), w.aq.data(), w.ao.data(), aligned_res.data(), alt_res.data());
             if (rc == SNAPGPU_OK && o.ae) {                 // finalizeSecondaryResults has only the primary to adjust (BaseAligner.cpp:2444-2452)
-                std::vector<int32_t> lens(to_align.size());
-                for (size_t k = 0; k < to_align.size(); k++) lens[k] = (int32_t)(ao[k + 1] - ao[k]);
-                rc = snapgpu_adjust_alignments(ctx, (uint32_t)to_align.size(), ab.data(), (uint64_t)ab.size(), ao.data(), lens.data(), aligned_res.data());
-                // The adjuster is restated for reads the reader has not clipped (adjust.h): the reference settles a contig-end overhang on the
-                // UNCLIPPED buffer (AlignmentAdjuster.cpp:167), which only differs for a clipped read that hangs over the end of its contig.
-                // Such a read is refused rather than answered differently (-C-- switches the reader's clipping off).
-                for (size_t a = 0; rc == SNAPGPU_OK && a < to_align.size(); a++) {
-                    const size_t i = to_align[a];
-                    if (front_clip[i] == 0 && (uint64_t)data_len[i] == b.offsets[i + 1] - b.offsets[i]) continue;
-                    const snapgpu_single_result &r = aligned_res[a];
-                    if (r.status == SNAPGPU_NotFound) continue;
-                    const int c = h_contig_at(r.location);
-                    if (c >= 0 && r.location + data_len[i] + (long long)o.p.max_k + 2 > h_contig_end(c) - (long long)g_padding)
-                        die("-ae: a quality-clipped read hangs over the end of its contig, which the adjuster does not reproduce (run with -C--)");
-                }
+                std::vector<int32_t> lens(na);
+                for (size_t k = 0; k < na; k++) lens[k] = (int32_t)(w.ao[k + 1] - w.ao[k]);
+                rc = snapgpu_adjust_alignments(ctx, (uint32_t)na, w.ab.data(), (uint64_t)w.ab.size(), w.ao.data(), lens.data(), aligned_res.data());
             }
+        }
+        for (size_t a = 0; o.ae && rc == SNAPGPU_OK && a < na; a++) {      // every adjusted result: the primary and the nsec[a] secondary ones that are there
+            const size_t i = w.to_align[a];
+            if (w.front_clip[i] == 0 && (uint64_t)w.data_len[i] == b.offsets[i + 1] - b.offsets[i]) continue;      // the reader clipped nothing
+            refuse_ae_at_contig_end(o, w, i, aligned_res[a]);
+            for (uint32_t j = 0; j < (nsec[a] < stride ? nsec[a] : stride); j++) refuse_ae_at_contig_end(o, w, i, sec[a * (size_t)stride + j]);
         }
         if (rc != SNAPGPU_OK) fail_rc(ctx, "alignment", rc);
         lap(g_ns_align);
-        std::vector<uint32_t> slot(n, 0xffffffffu);
-        for (size_t k = 0; k < to_align.size(); k++) { results[to_align[k]] = aligned_res[k]; slot[to_align[k]] = (uint32_t)k; }
-        for (size_t i = 0; i < n; i++) {
-            w.rec_read.push_back((uint32_t)i); w.rec_secondary.push_back(0); rec_res.push_back(results[i]);
-            if (o.om >= 0 && slot[i] != 0xffffffffu)
-                for (uint32_t j = 0; j < nsec[slot[i]]; j++) { w.rec_read.push_back((uint32_t)i); w.rec_secondary.push_back(1); rec_res.push_back(sec[(size_t)slot[i] * stride + j]); }
-            if (o.p.alt_awareness && slot[i] != 0xffffffffu && alt_res[slot[i]].status != SNAPGPU_NotFound) {      // writeReads(&firstALTResult, 1, firstIsPrimary = false)
-                w.rec_read.push_back((uint32_t)i); w.rec_secondary.push_back(1); rec_res.push_back(alt_res[slot[i]]);
-            }
-        }
-    } else for (size_t i = 0; i < n; i++) { w.rec_read.push_back((uint32_t)i); w.rec_secondary.push_back(0); rec_res.push_back(results[i]); }
-    const size_t nr = w.rec_read.size();
-    // the record batch: a read with secondary results appears once per record
-    std::vector<char> rb, rq; std::vector<uint64_t> ro(1, 0); std::vector<int32_t> rfc(nr), rdl(nr);
-    const bool one_to_one = nr == n;
-    if (!one_to_one) {
-        for (size_t r = 0; r < nr; r++) {
-            const size_t i = w.rec_read[r];
-            rb.insert(rb.end(), b.bases.begin() + (long)b.offsets[i], b.bases.begin() + (long)b.offsets[i + 1]);
-            rq.insert(rq.end(), b.quals.begin() + (long)b.offsets[i], b.quals.begin() + (long)b.offsets[i + 1]);
-            ro.push_back(rb.size()); rfc[r] = front_clip[i]; rdl[r] = data_len[i];
-        }
     }
-    w.flag.assign(nr, 0); w.contig.assign(nr, 0); w.mapq.assign(nr, 0); w.n_ops.assign(nr, 0); w.nm.assign(nr, 0); w.pos.assign(nr, 0);
+    std::vector<uint32_t> slot(n, 0xffffffffu);
+    for (size_t k = 0; k < na; k++) slot[w.to_align[k]] = (uint32_t)k;
+    w.rec_read.clear(); w.rec_secondary.clear();
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t a = slot[i];
+        add_record(w, rec_res, i, false, a == 0xffffffffu ? not_found_result() : aligned_res[a]);
+        if (a == 0xffffffffu) continue;
+        if (o.om >= 0) for (uint32_t j = 0; j < nsec[a]; j++) add_record(w, rec_res, i, true, sec[(size_t)a * stride + j]);
+        if (o.p.alt_awareness && alt_res[a].status != SNAPGPU_NotFound) add_record(w, rec_res, i, true, alt_res[a]);      // writeReads(&firstALTResult, 1, firstIsPrimary = false)
+    }
+}
+// whole reads of a batch gathered into a batch of their own (a read appears once per record computed from it), each with the clipping it is given
+struct ReadGather { std::vector<char> b, q; std::vector<uint64_t> off = std::vector<uint64_t>(1, 0); std::vector<int32_t> fc, dl; };
+static void gather_read(ReadGather &g, const Batch &b, size_t i, int32_t front_clip, int32_t data_len)
+{
+    g.b.insert(g.b.end(), b.bases.begin() + (long)b.offsets[i], b.bases.begin() + (long)b.offsets[i + 1]);
+    g.q.insert(g.q.end(), b.quals.begin() + (long)b.offsets[i], b.quals.begin() + (long)b.offsets[i + 1]);
+    g.off.push_back(g.b.size()); g.fc.push_back(front_clip); g.dl.push_back(data_len);
+}
+// records -> fields: snapgpu_sam_fields_single over rec_res, on the batch itself when every read has one record
+static void single_fields_of_records(const Options &o, snapgpu_ctx *ctx, Work &w, StageLap &lap, const ResultList &rec_res)
+{
+    const Batch &b = w.b;
+    const size_t nr = w.rec_read.size();
+    const char *bases = b.bases.data(), *quals = b.quals.data(); const uint64_t *off = b.offsets.data(); const int32_t *fc = w.front_clip.data(), *dl = w.data_len.data();
+    ReadGather g;
+    if (nr != b.n()) {                                                     // (a read with several records: once per record)
+        for (size_t r = 0; r < nr; r++) gather_read(g, b, w.rec_read[r], w.front_clip[w.rec_read[r]], w.data_len[w.rec_read[r]]);
+        bases = g.b.data(); quals = g.q.data(); off = g.off.data(); fc = g.fc.data(); dl = g.dl.data();
+    }
+    w.rec.assign(nr);
     std::vector<int32_t> stale(nr);
-    w.ops_stride = o.ops_stride;
+    w.rec.ops_stride = o.ops_stride;
     lap(g_ns_mid);
-    with_growing_stride(w, nr, [&] {
-        int rc2 = one_to_one
-            ? snapgpu_sam_fields_single(ctx, (uint32_t)nr, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(), rec_res.data(),
-                                        o.use_m ? 1 : 0, w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(), w.ops.data(), w.ops_stride, w.n_ops.data(),
-                                        w.nm.data(), stale.data())
-            : snapgpu_sam_fields_single(ctx, (uint32_t)nr, rb.data(), rq.data(), ro.data(), rfc.data(), rdl.data(), rec_res.data(), o.use_m ? 1 : 0,
-                                        w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(), w.ops.data(), w.ops_stride, w.n_ops.data(), w.nm.data(), stale.data());
-        if (rc2 != SNAPGPU_OK) fail_rc(ctx, "snapgpu_sam_fields_single", rc2);
+    with_growing_stride(w.rec, nr, [&] {
+        int rc = snapgpu_sam_fields_single(ctx, (uint32_t)nr, bases, quals, off, fc, dl, rec_res.data(), o.use_m ? 1 : 0,
+                                           w.rec.flag.data(), w.rec.contig.data(), w.rec.pos.data(), w.rec.mapq.data(), w.rec.ops.data(), w.rec.ops_stride, w.rec.n_ops.data(), w.rec.nm.data(), stale.data());
+        if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_sam_fields_single", rc);
     });
     lap(g_ns_samcall);
-    for (size_t r = 0; r < nr; r++) if (w.rec_secondary[r]) w.flag[r] |= 0x100;                  // SAM_SECONDARY (createSAMLine, SAM.cpp:1477-1479)
+    for (size_t r = 0; r < nr; r++) if (w.rec_secondary[r]) w.rec.flag[r] |= 0x100;                  // SAM_SECONDARY (createSAMLine, SAM.cpp:1477-1479)
 }
 
+static void gpu_single(const Options &o, FeederCtx &fc, Work &w)
+{
+    StageLap lap;
+    const size_t n = w.b.n();
+    if (!w.prepared) prepare_single(o, w);            // (the parser threads of the mapped reader have done it already)
+    snapgpu_ctx *ctx = ctx_for(o, fc, w.max_len);
+    if (o.paths.single_records_call && n > 0) { single_records_call(o, ctx, w, lap); return; }
+    ResultList rec_res;
+    if (o.paths.single_one_call && n > 0) { if (single_one_call(o, ctx, w, lap, rec_res)) return; }
+    else single_separate_calls(o, ctx, w, lap, rec_res);
+    single_fields_of_records(o, ctx, w, lap, rec_res);
+}
 // Several batches in ONE GPU call.  The host stages want fine grain -- a batch is parsed by one thread and formatted by one thread, so the
 // pipeline fills and drains in the time ONE batch takes -- and the GPU wants ~1 M reads per launch (a launch ends on its slowest read).
 // So the batches stay small (131 072 reads) and a feeder hands `-g` of them to snapgpu_align_sam_single as one batch: inputs gathered into
@@ -923,11 +941,9 @@ struct GroupBuf {
 };
 static void gpu_single_group(const Options &o, FeederCtx &fc, std::vector<Work *> &ws, GroupBuf &g)
 {
-    if (device_text_path(o) || device_bam_path(o)) { for (Work *w : ws) gpu_single_text(o, fc, *w); return; }
-    const bool fusable = o.om < 0 && !o.ae && !single_records_path(o);
-    if (ws.size() == 1 || !fusable) { for (Work *w : ws) gpu_single(o, fc, *w); return; }
-    auto t_stage = std::chrono::steady_clock::now();
-    auto lap = [&](std::atomic<unsigned long long> &acc) { const auto t = std::chrono::steady_clock::now(); acc += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(t - t_stage).count(); t_stage = t; };
+    if (o.paths.output != Options::HostFormat) { for (Work *w : ws) gpu_single_text(o, fc, *w); return; }
+    if (ws.size() == 1 || !o.paths.single_one_call) { for (Work *w : ws) gpu_single(o, fc, *w); return; }
+    StageLap lap;
     size_t n = 0, nbytes = 0; uint32_t max_len = 0;
     for (Work *w : ws) { if (!w->prepared) prepare_single(o, *w); n += w->b.n(); nbytes += w->b.bases.size(); if (w->max_len > max_len) max_len = w->max_len; }
     if (n == 0) { for (Work *w : ws) gpu_single(o, fc, *w); return; }
@@ -956,170 +972,167 @@ static void gpu_single_group(const Options &o, FeederCtx &fc, std::vector<Work *
                                                 want_alt ? g.res.data() : NULL, want_alt ? g.alt.data() : NULL,
                                                 g.flag.data(), g.contig.data(), g.pos.data(), g.mapq.data(), g.ops.data(), stride, g.n_ops.data(), g.nm.data(), g.stale.data());
         if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_single", rc);
-        bool too_small = false;
-        for (size_t i = 0; i < n && !too_small; i++) too_small = g.nm[i] == -2;
-        if (!too_small) break;
-        if (stride >= 4096) die("a cigar needs more than 4096 operations");
-        stride *= 4;
+        if (!cigar_overflowed(g.nm.data(), n)) break;
+        grow_stride(stride);
     }
     lap(g_ns_align);
     if (want_alt) for (size_t i = 0; i < n; i++) if (!g.skip[i] && g.alt[i].status != SNAPGPU_NotFound) { for (Work *w : ws) gpu_single(o, fc, *w); return; }   // (rare: ALT records: batch by batch)
     at = 0;
     for (Work *w : ws) {
         const size_t m = w->b.n();
+        Records &r = w->rec;
         w->rec_read.resize(m); for (size_t i = 0; i < m; i++) w->rec_read[i] = (uint32_t)i;
         w->rec_secondary.assign(m, 0);
-        w->flag.assign(g.flag.begin() + (long)at, g.flag.begin() + (long)(at + m)); w->contig.assign(g.contig.begin() + (long)at, g.contig.begin() + (long)(at + m));
-        w->mapq.assign(g.mapq.begin() + (long)at, g.mapq.begin() + (long)(at + m)); w->n_ops.assign(g.n_ops.begin() + (long)at, g.n_ops.begin() + (long)(at + m));
-        w->nm.assign(g.nm.begin() + (long)at, g.nm.begin() + (long)(at + m)); w->pos.assign(g.pos.begin() + (long)at, g.pos.begin() + (long)(at + m));
-        w->ops_stride = stride; w->ops.assign(g.ops.begin() + (long)(at * stride), g.ops.begin() + (long)((at + m) * stride));
+        auto part = [&](auto &to, const auto &from, size_t per) { to.assign(from.begin() + (long)(at * per), from.begin() + (long)((at + m) * per)); };
+        part(r.flag, g.flag, 1); part(r.contig, g.contig, 1); part(r.mapq, g.mapq, 1); part(r.n_ops, g.n_ops, 1); part(r.nm, g.nm, 1); part(r.pos, g.pos, 1);
+        r.ops_stride = stride; part(r.ops, g.ops, stride);
         at += m;
     }
     lap(g_ns_mid);
 }
 
-static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
+typedef std::vector<snapgpu_paired_result> PairedResultList;
+static HostRes host_res(const snapgpu_single_result &r)
 {
-    const Batch &b = w.b;
-    const size_t n = b.n(), np = n / 2;
-    w.max_len = 0;
-    for (size_t i = 0; i < n; i++) { const uint32_t U = (uint32_t)(b.offsets[i + 1] - b.offsets[i]); if (U > w.max_len) w.max_len = U; }
-    snapgpu_ctx *ctx = ctx_for(o, fc, w.max_len);
-    std::vector<int32_t> front_clip(n, 0), data_len(n, 0);
-    std::vector<char> useful(n, 0);
-    for (size_t i = 0; i < n; i++) useful[i] = clip_read(o, b, i, front_clip[i], data_len[i]);
-    // ---- the common case in ONE call (snapgpu_align_sam_paired): no secondary results, one record pair per pair unless -ea has a first-ALT result to
-    // write.  The batch goes up as it was parsed -- no clipped copy for the aligner, no results coming back to be scattered and sent up again.
-    // (SNAPGPU_SAM_PAIRED_FUSED=0: measurement knob, the calls it replaces)
-    static const bool fused_on = !(getenv("SNAPGPU_SAM_PAIRED_FUSED") && atoi(getenv("SNAPGPU_SAM_PAIRED_FUSED")) == 0);
-    if (o.om < 0 && np > 0 && fused_on) {
+    return HostRes{r.status, r.direction, r.score, r.mapq, r.clipping_for_read_adjustment, r.used_affine_gap_scoring, r.bases_clipped_before, r.bases_clipped_after, r.supplementary, (long long)r.location};
+}
+static HostRes host_res(const snapgpu_paired_result &r, int v)
+{
+    return HostRes{r.status[v], r.direction[v], r.score[v], r.mapq[v], r.clipping_for_read_adjustment[v], r.used_affine_gap_scoring[v], r.bases_clipped_before[v], r.bases_clipped_after[v],
+                   r.supplementary[v], (long long)r.location[v]};
+}
+// the pair fields of a batch beside w.rec: sized for n_units pair units and n_singles single units, cigar rows of the starting stride
+static void size_pair_fields(const Options &o, Work &w, size_t n_units, size_t n_singles)
+{
+    const size_t nrec = 2 * n_units;
+    w.rec.assign(nrec); w.rnext.assign(nrec, 0); w.first_written.assign(n_units, 0); w.pnext.assign(nrec, 0); w.tlen.assign(nrec, 0);
+    w.srec.assign(n_singles);
+    w.rec.ops_stride = w.srec.ops_stride = o.ops_stride;
+}
+// one record's fields and cigar row into place (`from` has the same stride); a record the host loop computed: false when its cigar does not fit the row
+static void copy_record(Records &to, size_t dst, const Records &from, size_t src, int or_flag)
+{
+    to.flag[dst] = from.flag[src] | or_flag; to.contig[dst] = from.contig[src]; to.pos[dst] = from.pos[src]; to.mapq[dst] = from.mapq[src]; to.n_ops[dst] = from.n_ops[src]; to.nm[dst] = from.nm[src];
+    memcpy(to.cigar(dst), from.cigar(src), (size_t)to.ops_stride * 4);
+}
+static bool store_host_record(Records &to, size_t dst, const HostRec &rec, int flag, int contig, long long pos)
+{
+    if ((uint32_t)(rec.n_ops > 0 ? rec.n_ops : 0) > to.ops_stride) return false;
+    to.flag[dst] = flag; to.contig[dst] = contig; to.pos[dst] = pos; to.mapq[dst] = rec.mapq; to.n_ops[dst] = rec.n_ops; to.nm[dst] = rec.nm;
+    for (int c = 0; c < rec.n_ops; c++) to.cigar(dst)[c] = rec.ops[(size_t)c];
+    return true;
+}
+// A batch of pairs in its feeder, and gpu_paired's steps over it: one_call; align_calls, emit_list and then one snapgpu_sam_fields_paired call or rounds()
+struct PairedBatch {
+    const Options &o; snapgpu_ctx *ctx; Work &w; const Batch &b;
+    size_t n, np;                            // reads, pairs
+    std::vector<int32_t> front_clip, data_len; std::vector<char> useful;      // per read: Read::clip, and whether the aligner gets the read
+    PairedBatch(const Options &o_, snapgpu_ctx *c, Work &w_) : o(o_), ctx(c), w(w_), b(w_.b), n(b.n()), np(n / 2), front_clip(n, 0), data_len(n, 0), useful(n, 0)
+    {
+        for (size_t i = 0; i < n; i++) useful[i] = clip_read(o, b, i, front_clip[i], data_len[i]);
+    }
+    // The common case in ONE call: no secondary results, one record pair per pair unless -ea has a first-ALT result to write.  The batch goes up
+    // as it was parsed and its fields (snapgpu_align_sam_paired) or, on the device-output paths, its lines, records or blocks come down.  True when
+    // the batch is finished; false (rare) when it has a first-ALT pair to write and goes through the separate calls: the call was then for nothing.
+    bool one_call()
+    {
+        const size_t nrec = 2 * np;
         const bool want_alt = o.p.emit_alt_alignments != 0;
+        const int use_m = o.use_m ? 1 : 0;
         std::vector<uint8_t> skip(np);
         for (size_t k = 0; k < np; k++) skip[k] = !useful[2 * k] && !useful[2 * k + 1];      // neither mate useful (PairedAligner.cpp:680-682)
-        std::vector<snapgpu_paired_result> fres, falt;
+        PairedResultList fres, falt;
         if (want_alt) { fres.resize(np); falt.resize(np); }
-        const size_t nrec = 2 * np;
+        snapgpu_paired_result *res = want_alt ? fres.data() : NULL, *alt = want_alt ? falt.data() : NULL;
         auto first_alt_pair = [&] {
             if (want_alt) for (size_t k = 0; k < np; k++) if (!skip[k] && (falt[k].status[0] != SNAPGPU_NotFound || falt[k].status[1] != SNAPGPU_NotFound)) return true;
             return false;
         };
-        // SNAPGPU_SAM_DEVICE_TEXT: the batch goes up as it was parsed, with its names, and the lines of its pairs come down (as gpu_single_text: the
-        // capacity follows what the library reports, a cigar that outgrows its row is met with a larger row)
-        if (device_text_paired_path(o) || device_bam_paired_path(o)) {
-            std::vector<uint64_t> name_off(b.name_off.begin(), b.name_off.end()), line_begin(nrec + 1);
-            const size_t per_read = (2 * b.bases.size() + b.names.size() + nrec - 1) / nrec;       // name, SEQ and QUAL of the average record
-            size_t tcap = nrec * (per_read + g_text_extra_per_record.load());
-            uint32_t ops_stride = o.ops_stride;
-            uint64_t text_bytes = 0, n_mem = 0, z_bytes = 0;
-            const bool bgzf = device_bgzf_switch(o);
-            size_t zcap = tcap / 1000 * g_bgzf_per_mille.load() + 64;
-            std::vector<uint64_t> member_begin;
-            w.flag.assign(nrec, 0); w.first_written.assign(np, 0);
-            for (;;) {
-                w.text.resize(bgzf ? zcap : tcap); if (bgzf) member_begin.resize(tcap / 0xff00 + 2);
-                const int rc = bgzf
+        if (o.paths.output != Options::HostFormat) {
+            std::vector<uint64_t> name_off(b.name_off.begin(), b.name_off.end());
+            w.rec.flag.assign(nrec, 0); w.first_written.assign(np, 0);
+            return device_output(o, ctx, w, "snapgpu_align_sam_paired", nrec, true, [&](DeviceCall &c) {
+                return o.paths.output == Options::DeviceBgzf
                     ? snapgpu_align_sam_paired_bgzf(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
-                                                    skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
-                                                    want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
-                                                    0xff00, (uint64_t)zcap, (uint8_t *)&w.text[0], member_begin.data(), (uint64_t)member_begin.size() - 1,
-                                                    &n_mem, &z_bytes, &text_bytes)
-                    : o.bam
+                                                    skip.data(), use_m, b.names.data(), name_off.data(), c.ops_stride, res, alt, w.rec.flag.data(), w.first_written.data(),
+                                                    0xff00, c.bgzf_cap, (uint8_t *)&w.text[0], c.begin, c.max_members, &c.n_members, &c.bgzf_bytes, &c.text_bytes)
+                    : o.paths.output == Options::DeviceBam
                     ? snapgpu_align_sam_paired_bam(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
-                                                   skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
-                                                   want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
-                                                   (uint64_t)tcap, (uint8_t *)&w.text[0], line_begin.data(), &text_bytes)
+                                                   skip.data(), use_m, b.names.data(), name_off.data(), c.ops_stride, res, alt, w.rec.flag.data(), w.first_written.data(),
+                                                   c.text_cap, (uint8_t *)&w.text[0], c.begin, &c.text_bytes)
                     : snapgpu_align_sam_paired_text(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
-                                                    skip.data(), o.use_m ? 1 : 0, b.names.data(), name_off.data(), ops_stride,
-                                                    want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL, w.flag.data(), w.first_written.data(),
-                                                    (uint64_t)tcap, &w.text[0], line_begin.data(), &text_bytes);
-                if (rc == SNAPGPU_W_TEXT_TRUNCATED) { tcap = (size_t)text_bytes + (size_t)text_bytes / 64; if (z_bytes > zcap) zcap = (size_t)z_bytes + (size_t)z_bytes / 64; continue; }
-                if (rc == SNAPGPU_E_INVALID && strstr(snapgpu_last_error(ctx), "ops_stride")) {
-                    if (ops_stride >= 4096) die("a cigar needs more than 4096 operations");
-                    ops_stride *= 4; continue;
-                }
-                if (rc != SNAPGPU_OK) fail_rc(ctx, bgzf ? "snapgpu_align_sam_paired_bgzf" : o.bam ? "snapgpu_align_sam_paired_bam" : "snapgpu_align_sam_paired_text", rc);
-                break;
-            }
-            if (!first_alt_pair()) {
-                { const size_t per_rec = ((size_t)text_bytes + nrec - 1) / nrec; const uint32_t need = per_rec > per_read ? (uint32_t)(per_rec - per_read) + 16 : 16;
-                  uint32_t cur = g_text_extra_per_record.load(); while (need > cur && !g_text_extra_per_record.compare_exchange_weak(cur, need)) {} }
-                w.text.resize((size_t)(bgzf ? z_bytes : text_bytes)); w.text_done = true; w.mapped = 0;
-                if (bgzf) bgzf_from_device(w, tcap, n_mem, text_bytes, z_bytes);
-                for (size_t r = 0; r < nrec; r++) w.mapped += (w.flag[r] & 0x4) == 0;
-                if (o.bam) { g_bam_batches++; g_bam_records += nrec; }
-                return;
-            }
-            w.text.clear();                                             // (rare: a first-ALT pair to write -- the batch goes through the calls below; with
-                                                                        // SNAPGPU_SAM_DEVICE_BGZF the call above has compressed its records for nothing, too)
-        } else {
-            w.emit.clear(); w.pu_pair.resize(np); w.pu_secondary.assign(np, 0); w.su_read.clear();
-            for (size_t k = 0; k < np; k++) { w.emit.push_back(Work::Emit{(uint32_t)k, 0}); w.pu_pair[k] = (uint32_t)k; }
-            w.flag.assign(nrec, 0); w.contig.assign(nrec, 0); w.mapq.assign(nrec, 0); w.n_ops.assign(nrec, 0); w.nm.assign(nrec, 0); w.rnext.assign(nrec, 0);
-            w.first_written.assign(np, 0); w.pos.assign(nrec, 0); w.pnext.assign(nrec, 0); w.tlen.assign(nrec, 0);
-            w.s_flag.clear(); w.s_contig.clear(); w.s_mapq.clear(); w.s_n_ops.clear(); w.s_nm.clear(); w.s_pos.clear();
-            w.ops_stride = w.s_ops_stride = o.ops_stride;
-            std::vector<int32_t> stale(nrec);
-            with_growing_stride(w, nrec, [&] {
-                int rc = snapgpu_align_sam_paired(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(), skip.data(),
-                                                  o.use_m ? 1 : 0, want_alt ? fres.data() : NULL, want_alt ? falt.data() : NULL,
-                                                  w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(), w.ops.data(), w.ops_stride, w.n_ops.data(),
-                                                  w.nm.data(), w.rnext.data(), w.pnext.data(), w.tlen.data(), w.first_written.data(), stale.data());
-                if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_paired", rc);
-            });
-            if (!first_alt_pair()) return;                                         // (rare: a first-ALT pair to write -- the batch goes through the calls below)
+                                                    skip.data(), use_m, b.names.data(), name_off.data(), c.ops_stride, res, alt, w.rec.flag.data(), w.first_written.data(),
+                                                    c.text_cap, &w.text[0], c.begin, &c.text_bytes);
+            }, first_alt_pair);
         }
+        w.emit.clear(); w.pu_pair.resize(np); w.pu_secondary.assign(np, 0); w.su_read.clear();
+        for (size_t k = 0; k < np; k++) { w.emit.push_back(Work::Emit{(uint32_t)k, 0}); w.pu_pair[k] = (uint32_t)k; }
+        size_pair_fields(o, w, np, 0);
+        std::vector<int32_t> stale(nrec);
+        with_growing_stride(w.rec, nrec, [&] {
+            int rc = snapgpu_align_sam_paired(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(), skip.data(),
+                                              use_m, res, alt, w.rec.flag.data(), w.rec.contig.data(), w.rec.pos.data(), w.rec.mapq.data(), w.rec.ops.data(), w.rec.ops_stride, w.rec.n_ops.data(),
+                                              w.rec.nm.data(), w.rnext.data(), w.pnext.data(), w.tlen.data(), w.first_written.data(), stale.data());
+            if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_sam_paired", rc);
+        });
+        return !first_alt_pair();
     }
-    std::vector<uint32_t> to_align;                                     // pairs with at least one useful mate (PairedAligner.cpp:680-682)
-    std::vector<char> ab, aq; std::vector<uint64_t> ao(1, 0);
-    for (size_t k = 0; k < np; k++) {
-        if (!useful[2 * k] && !useful[2 * k + 1]) continue;
-        to_align.push_back((uint32_t)k);
-        for (size_t i = 2 * k; i < 2 * k + 2; i++) {
-            const char *q = b.quals.data() + b.offsets[i], *s = b.bases.data() + b.offsets[i];
-            ab.insert(ab.end(), s + front_clip[i], s + front_clip[i] + data_len[i]); aq.insert(aq.end(), q + front_clip[i], q + front_clip[i] + data_len[i]); ao.push_back(ab.size());
+    // The separate align calls: the pairs with at least one useful mate (PairedAligner.cpp:680-682), clipped, through snapgpu_align_paired or --
+    // secondary results (-om): paired ones and each mate's single-end ones (PairedAligner.cpp:727-779) -- snapgpu_align_paired_secondary
+    std::vector<uint32_t> slot;                                          // per pair: its place among the aligned pairs, or NONE
+    static constexpr uint32_t NONE = 0xffffffffu;
+    PairedResultList results, first_alt;                                       // per pair (NotFound where it was not aligned); per aligned pair: its first-ALT result
+    PairedResultList sec; std::vector<uint32_t> nsec; uint32_t sec_stride = 0;            // per aligned pair: further pair results
+    ResultList ssec; std::vector<uint32_t> nssec; uint32_t ssec_stride = 0;               // per aligned pair: mate 0's single-end secondary results, then mate 1's (nssec[2 a + v] of them)
+    void align_calls()
+    {
+        std::vector<uint32_t> to_align;
+        std::vector<char> ab, aq; std::vector<uint64_t> ao(1, 0);
+        slot.assign(np, NONE);
+        for (size_t k = 0; k < np; k++) {
+            if (!useful[2 * k] && !useful[2 * k + 1]) continue;
+            slot[k] = (uint32_t)to_align.size(); to_align.push_back((uint32_t)k);
+            for (size_t i = 2 * k; i < 2 * k + 2; i++) {
+                const char *q = b.quals.data() + b.offsets[i], *s = b.bases.data() + b.offsets[i];
+                ab.insert(ab.end(), s + front_clip[i], s + front_clip[i] + data_len[i]); aq.insert(aq.end(), q + front_clip[i], q + front_clip[i] + data_len[i]); ao.push_back(ab.size());
+            }
         }
-    }
-    std::vector<snapgpu_paired_result> results(np), ares(to_align.size()), aalt(to_align.size());
-    for (size_t k = 0; k < np; k++) {
-        memset(&results[k], 0, sizeof(results[k]));
-        for (int v = 0; v < 2; v++) { results[k].status[v] = SNAPGPU_NotFound; results[k].location[v] = SNAPGPU_InvalidGenomeLocation32; results[k].score[v] = -1; }
-    }
-    // secondary results (-om): paired ones and each mate's single-end ones (PairedAligner.cpp:727-779)
-    std::vector<snapgpu_paired_result> sec; std::vector<uint32_t> nsec(to_align.size(), 0), nssec(2 * to_align.size(), 0);
-    std::vector<snapgpu_single_result> ssec;
-    uint32_t sec_stride = 0, ssec_stride = 0;
-    if (!to_align.empty()) {
+        const size_t na = to_align.size();
+        PairedResultList ares(na);
+        snapgpu_paired_result none; memset(&none, 0, sizeof(none));
+        for (int v = 0; v < 2; v++) { none.status[v] = SNAPGPU_NotFound; none.location[v] = SNAPGPU_InvalidGenomeLocation32; none.score[v] = -1; }
+        results.assign(np, none); first_alt.resize(na); nsec.assign(na, 0); nssec.assign(2 * na, 0);
+        if (na == 0) return;
         int rc;
         if (o.om >= 0) {
             sec_stride = 8; ssec_stride = 16;
             for (;;) {
-                sec.assign(to_align.size() * (size_t)sec_stride, snapgpu_paired_result()); ssec.assign(to_align.size() * (size_t)ssec_stride, snapgpu_single_result());
-                rc = snapgpu_align_paired_secondary(ctx, (uint32_t)to_align.size(), ab.data(), aq.data(), ao.data(), ares.data(), aalt.data(),
+                sec.assign(na * (size_t)sec_stride, snapgpu_paired_result()); ssec.assign(na * (size_t)ssec_stride, snapgpu_single_result());
+                rc = snapgpu_align_paired_secondary(ctx, (uint32_t)na, ab.data(), aq.data(), ao.data(), ares.data(), first_alt.data(),
                                                     sec.data(), sec_stride, nsec.data(), ssec.data(), ssec_stride, nssec.data());
                 if (rc != SNAPGPU_W_SECONDARY_TRUNCATED) break;
-                for (size_t k = 0; k < to_align.size(); k++) {
+                for (size_t k = 0; k < na; k++) {
                     if (nsec[k] > sec_stride) sec_stride = nsec[k];
                     if (nssec[2 * k] + nssec[2 * k + 1] > ssec_stride) ssec_stride = nssec[2 * k] + nssec[2 * k + 1];
                 }
             }
-        } else rc = snapgpu_align_paired(ctx, (uint32_t)to_align.size(), ab.data(), aq.data(), ao.data(), ares.data(), aalt.data());
+        } else rc = snapgpu_align_paired(ctx, (uint32_t)na, ab.data(), aq.data(), ao.data(), ares.data(), first_alt.data());
         if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_align_paired", rc);
-        for (size_t k = 0; k < to_align.size(); k++) results[to_align[k]] = ares[k];
+        for (size_t k = 0; k < na; k++) results[to_align[k]] = ares[k];
     }
-    // what gets written, in the reference's order (PairedAligner.cpp:874-880 -> SimpleReadWriter::writePairs): the pair's results (primary first),
-    // read 0's single-end secondary results, read 1's, then -- with -ea -- the first ALT result as a pair of its own
-    std::vector<snapgpu_paired_result> pu_res; std::vector<snapgpu_single_result> su_res;
-    w.emit.clear(); w.pu_pair.clear(); w.pu_secondary.clear(); w.su_read.clear();
+    // What gets written, in the reference's order (PairedAligner.cpp:874-880 -> SimpleReadWriter::writePairs): the pair's results (primary first),
+    // read 0's single-end secondary results, read 1's, then -- with -ea -- the first ALT result as a pair of its own.  Fills w.emit and its
+    // unit tables; pu_res / su_res: the result each pair unit / single unit is computed from
+    void emit_list()
     {
-        std::vector<uint32_t> slot(np, 0xffffffffu);
-        for (size_t k = 0; k < to_align.size(); k++) slot[to_align[k]] = (uint32_t)k;
+        w.emit.clear(); w.pu_pair.clear(); w.pu_secondary.clear(); w.su_read.clear();
         auto add_pair_unit = [&](size_t k, const snapgpu_paired_result &r, bool secondary) {
             w.emit.push_back(Work::Emit{(uint32_t)pu_res.size(), 0}); w.pu_pair.push_back((uint32_t)k); w.pu_secondary.push_back(secondary ? 1 : 0); pu_res.push_back(r);
         };
         for (size_t k = 0; k < np; k++) {
             add_pair_unit(k, results[k], false);
             const uint32_t a = slot[k];
-            if (a == 0xffffffffu) continue;
+            if (a == NONE) continue;
             if (o.om >= 0) {
                 for (uint32_t j = 0; j < nsec[a]; j++) add_pair_unit(k, sec[(size_t)a * sec_stride + j], true);
                 uint32_t at = 0;
@@ -1134,287 +1147,162 @@ static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
                     }
                 }
             }
-            if (o.p.emit_alt_alignments && (aalt[a].status[0] != SNAPGPU_NotFound || aalt[a].status[1] != SNAPGPU_NotFound)) add_pair_unit(k, aalt[a], false);
+            if (o.p.emit_alt_alignments && (first_alt[a].status[0] != SNAPGPU_NotFound || first_alt[a].status[1] != SNAPGPU_NotFound)) add_pair_unit(k, first_alt[a], false);
         }
     }
-    const size_t nu = pu_res.size(), nrec = 2 * nu, ns = su_res.size();
-    w.flag.assign(nrec, 0); w.contig.assign(nrec, 0); w.mapq.assign(nrec, 0); w.n_ops.assign(nrec, 0); w.nm.assign(nrec, 0); w.rnext.assign(nrec, 0);
-    w.first_written.assign(nu, 0); w.pos.assign(nrec, 0); w.pnext.assign(nrec, 0); w.tlen.assign(nrec, 0);
-    w.s_flag.assign(ns, 0); w.s_contig.assign(ns, 0); w.s_mapq.assign(ns, 0); w.s_n_ops.assign(ns, 0); w.s_nm.assign(ns, 0); w.s_pos.assign(ns, 0);
-    w.ops_stride = w.s_ops_stride = o.ops_stride;
-    if (nu == np && ns == 0) {                                          // one result per pair: one call over the batch as it is
-        std::vector<int32_t> stale(nrec);
-        with_growing_stride(w, nrec, [&] {
-            int rc = snapgpu_sam_fields_paired(ctx, (uint32_t)nu, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(), pu_res.data(),
-                                               o.use_m ? 1 : 0, w.flag.data(), w.contig.data(), w.pos.data(), w.mapq.data(), w.ops.data(), w.ops_stride, w.n_ops.data(),
-                                               w.nm.data(), w.rnext.data(), w.pnext.data(), w.tlen.data(), w.first_written.data(), stale.data());
-            if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_sam_fields_paired", rc);
-        });
-        return;
-    }
+    PairedResultList pu_res; ResultList su_res;                          // (emit_list) the result each pair unit / single unit is computed from
     // Several results per pair.  The reference writes them one after the other through the SAME two Read objects, and one piece of their state
     // survives from record to record: the additional BACK clipping that the affine-gap writer sets when it turns a leading insertion of a
     // reverse-complement alignment into a soft clip (SAM.cpp:1676-1680 / ReadWriter.cpp:545-551; setAdditionalFrontClipping is re-set for every
     // result, setAdditionalBackClipping never is: Read.h:537-553).  So the j-th entries of all pairs are computed together (round j), and what a
     // record leaves behind -- readable off its leading soft clip -- shortens the data length the next entry of the same read is given.
-    std::vector<std::vector<Work::Emit>> per_pair(np);
-    for (const Work::Emit &e : w.emit) per_pair[e.single ? w.su_read[e.unit] / 2 : w.pu_pair[e.unit]].push_back(e);
-    size_t n_rounds = 0;
-    for (size_t k = 0; k < np; k++) if (per_pair[k].size() > n_rounds) n_rounds = per_pair[k].size();
-    const bool host_all = getenv("SNAPGPU_SAM_HOST_LOOP") != NULL;      // (tests: every record of a multi-result batch through the host loop)
-    for (;;) {                                                           // (again with a larger stride when a cigar did not fit)
-        bool too_small = false;
-        std::vector<int32_t> carry(n, 0);
-        w.ops.assign(nrec * (size_t)w.ops_stride, 0); w.s_ops.assign(ns * (size_t)w.s_ops_stride, 0);
-        auto ag_branch = [&](int used_ag, int score) { return o.p.use_affine_gap && (used_ag != 0 || score > 0); };
-        // the state a written record leaves on its Read: `passed_len` is the data length the record was computed with
-        // (`hr` / `paired_rec`: the result the record was computed from, for the two cases in which the record alone does not say what it left
-        //  behind -- a record given up after clipping adjustments, and a reverse-complement record at the first base of a contig, whose leading
-        //  soft clip may have been cut short there: the record loop is then run on the host for that one record, with the Read's state as it
-        //  is, and ITS back clipping is what the next record of the read starts from.  Until round 4 these two cases stopped the program.)
-        auto leave_behind = [&](size_t rd, bool more, bool ag, int status_in, int flag, int64_t pos, int n_ops, const uint32_t *ops, int clipped_before, int passed_len,
-                                const HostRes &hr, bool paired_rec) {
-            if (!more || !ag) return;
-            const size_t U = (size_t)(b.offsets[rd + 1] - b.offsets[rd]);
-            if (((flag & 0x4) && status_in != SNAPGPU_NotFound) || ((flag & 0x10) && n_ops > 0 && pos == 1)) {
-                carry[rd] = host_record(o, ctx, b.bases.data() + b.offsets[rd], b.quals.data() + b.offsets[rd], (int)U, front_clip[rd], data_len[rd], carry[rd], hr, paired_rec).back_after;
-                if (getenv("SNAPGPU_SAM_VERBOSE")) fprintf(stderr, "snapgpu-sam: one record's state recomputed on the host (%s), back clipping left: %d\n", (flag & 0x4) ? "given up after clipping adjustments" : "reverse complement at the first base of a contig", carry[rd]);
-                return;
-            }
-            if (!(flag & 0x10) || n_ops <= 0) return;
-            const int lead = (ops[0] & 15u) == 4u ? (int)(ops[0] >> 4) : 0;
-            const int left = lead - ((int)U - passed_len - front_clip[rd]) - clipped_before;
-            if (left < 0) die("internal error: leading soft clip shorter than the read's own clipping");
-            if (left > 0) carry[rd] = left;                             // (device-computed records start from carry == 0: the others go through host_record)
-        };
-        for (size_t j = 0; j < n_rounds; j++) {
-            std::vector<uint32_t> pus, sus, pus_host, sus_host;          // this round's pair units / single units; `_host`: a read arrives with back clipping
-            for (size_t k = 0; k < np; k++) {
-                if (j >= per_pair[k].size()) continue;
-                const Work::Emit &e = per_pair[k][j];
-                if (e.single) (host_all || carry[w.su_read[e.unit]] > 0 ? sus_host : sus).push_back(e.unit);
-                else (host_all || carry[2 * k] > 0 || carry[2 * k + 1] > 0 ? pus_host : pus).push_back(e.unit);
-            }
-            for (uint32_t u : pus_host) {                                 // the record loop on the host, with the Reads' state as it is (exact)
-                const size_t k = w.pu_pair[u];
-                const snapgpu_paired_result &r = pu_res[u];
-                HostRec rec[2];
-                for (size_t v = 0; v < 2; v++) {
-                    const size_t i = 2 * k + v;
-                    const HostRes hr = {r.status[v], r.direction[v], r.score[v], r.mapq[v], r.clipping_for_read_adjustment[v], r.used_affine_gap_scoring[v],
-                                        r.bases_clipped_before[v], r.bases_clipped_after[v], r.supplementary[v], (long long)r.location[v]};
-                    rec[v] = host_record(o, ctx, b.bases.data() + b.offsets[i], b.quals.data() + b.offsets[i], (int)(b.offsets[i + 1] - b.offsets[i]), front_clip[i], data_len[i], carry[i], hr, true);
-                    carry[i] = rec[v].back_after;
-                }
-                for (size_t v = 0; v < 2; v++) {
-                    const size_t dst = 2 * u + v;
-                    int fl, ct, rn; long long ps, pn, tl;
-                    host_mate_info(rec[v], rec[1 - v], v == 0, r.aligned_as_pair != 0, fl, ct, ps, rn, pn, tl);
-                    if ((uint32_t)(rec[v].n_ops > 0 ? rec[v].n_ops : 0) > w.ops_stride) { too_small = true; continue; }
-                    w.flag[dst] = fl | (w.pu_secondary[u] ? 0x100 : 0); w.contig[dst] = ct; w.pos[dst] = ps; w.mapq[dst] = rec[v].mapq; w.n_ops[dst] = rec[v].n_ops; w.nm[dst] = rec[v].nm;
-                    w.rnext[dst] = rn; w.pnext[dst] = pn; w.tlen[dst] = tl;
-                    for (int c2 = 0; c2 < rec[v].n_ops; c2++) w.ops[dst * (size_t)w.ops_stride + (size_t)c2] = rec[v].ops[(size_t)c2];
-                }
-                const unsigned long long l0 = rec[0].final_loc < 0 ? ~0ull : (unsigned long long)rec[0].final_loc, l1 = rec[1].final_loc < 0 ? ~0ull : (unsigned long long)rec[1].final_loc;
-                w.first_written[u] = l0 <= l1 ? 0 : 1;                    // ReadWriter.cpp:481-488
-            }
-            for (uint32_t r : sus_host) {
-                const size_t rd = w.su_read[r];
-                const snapgpu_single_result &sr = su_res[r];
-                const HostRes hr = {sr.status, sr.direction, sr.score, sr.mapq, sr.clipping_for_read_adjustment, sr.used_affine_gap_scoring, sr.bases_clipped_before, sr.bases_clipped_after,
-                                    sr.supplementary, (long long)sr.location};
-                const HostRec rec = host_record(o, ctx, b.bases.data() + b.offsets[rd], b.quals.data() + b.offsets[rd], (int)(b.offsets[rd + 1] - b.offsets[rd]), front_clip[rd], data_len[rd], carry[rd], hr, false);
-                carry[rd] = rec.back_after;
-                if ((uint32_t)(rec.n_ops > 0 ? rec.n_ops : 0) > w.s_ops_stride) { too_small = true; continue; }
-                w.s_flag[r] = rec.flag | 0x100; w.s_contig[r] = rec.contig; w.s_pos[r] = rec.pos; w.s_mapq[r] = rec.mapq; w.s_n_ops[r] = rec.n_ops; w.s_nm[r] = rec.nm;
-                for (int c2 = 0; c2 < rec.n_ops; c2++) w.s_ops[r * (size_t)w.s_ops_stride + (size_t)c2] = rec.ops[(size_t)c2];
-            }
-            if (!pus.empty()) {
-                const size_t m = pus.size();
-                std::vector<char> rb, rq; std::vector<uint64_t> ro(1, 0); std::vector<int32_t> rfc(2 * m), rdl(2 * m), stale(2 * m);
-                std::vector<snapgpu_paired_result> rr(m);
-                for (size_t x = 0; x < m; x++) {
-                    rr[x] = pu_res[pus[x]];
-                    for (size_t v = 0; v < 2; v++) {
-                        const size_t i = 2 * (size_t)w.pu_pair[pus[x]] + v;
-                        rb.insert(rb.end(), b.bases.begin() + (long)b.offsets[i], b.bases.begin() + (long)b.offsets[i + 1]);
-                        rq.insert(rq.end(), b.quals.begin() + (long)b.offsets[i], b.quals.begin() + (long)b.offsets[i + 1]);
-                        ro.push_back(rb.size()); rfc[2 * x + v] = front_clip[i]; rdl[2 * x + v] = data_len[i] - carry[i];
-                    }
-                }
-                std::vector<int32_t> f(2 * m), c(2 * m), mq(2 * m), no(2 * m), nm(2 * m), rn(2 * m), fw(m); std::vector<int64_t> ps(2 * m), pn(2 * m), tl(2 * m);
-                std::vector<uint32_t> ops(2 * m * (size_t)w.ops_stride);
-                int rc = snapgpu_sam_fields_paired(ctx, (uint32_t)m, rb.data(), rq.data(), ro.data(), rfc.data(), rdl.data(), rr.data(), o.use_m ? 1 : 0,
-                                                   f.data(), c.data(), ps.data(), mq.data(), ops.data(), w.ops_stride, no.data(), nm.data(), rn.data(), pn.data(), tl.data(), fw.data(), stale.data());
-                if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_sam_fields_paired", rc);
-                for (size_t x = 0; x < m; x++) {
-                    const size_t u = pus[x], k = w.pu_pair[u];
-                    w.first_written[u] = fw[x];
-                    for (size_t v = 0; v < 2; v++) {
-                        const size_t src = 2 * x + v, dst = 2 * u + v;
-                        if (nm[src] == -2) too_small = true;
-                        w.flag[dst] = f[src] | (w.pu_secondary[u] ? 0x100 : 0); w.contig[dst] = c[src]; w.pos[dst] = ps[src]; w.mapq[dst] = mq[src]; w.n_ops[dst] = no[src];
-                        w.nm[dst] = nm[src]; w.rnext[dst] = rn[src]; w.pnext[dst] = pn[src]; w.tlen[dst] = tl[src];
-                        memcpy(&w.ops[dst * (size_t)w.ops_stride], &ops[src * (size_t)w.ops_stride], (size_t)w.ops_stride * 4);
-                        const HostRes hr = {rr[x].status[v], rr[x].direction[v], rr[x].score[v], rr[x].mapq[v], rr[x].clipping_for_read_adjustment[v], rr[x].used_affine_gap_scoring[v],
-                                            rr[x].bases_clipped_before[v], rr[x].bases_clipped_after[v], rr[x].supplementary[v], (long long)rr[x].location[v]};
-                        leave_behind(2 * k + v, j + 1 < per_pair[k].size(), ag_branch(rr[x].used_affine_gap_scoring[v], rr[x].score[v]), rr[x].status[v], f[src], ps[src], no[src],
-                                     &ops[src * (size_t)w.ops_stride], rr[x].bases_clipped_before[v], rdl[src], hr, true);
-                    }
-                }
-            }
-            if (!sus.empty()) {                                          // records of their own, without mate information (format->writeRead, ReadWriter.cpp:521-527)
-                const size_t m = sus.size();
-                std::vector<char> sb, sq; std::vector<uint64_t> so(1, 0); std::vector<int32_t> sfc(m), sdl(m), stale(m);
-                std::vector<snapgpu_single_result> rr(m);
-                for (size_t x = 0; x < m; x++) {
-                    const size_t i = w.su_read[sus[x]];
-                    rr[x] = su_res[sus[x]];
-                    sb.insert(sb.end(), b.bases.begin() + (long)b.offsets[i], b.bases.begin() + (long)b.offsets[i + 1]);
-                    sq.insert(sq.end(), b.quals.begin() + (long)b.offsets[i], b.quals.begin() + (long)b.offsets[i + 1]);
-                    so.push_back(sb.size()); sfc[x] = front_clip[i]; sdl[x] = data_len[i] - carry[i];
-                }
-                std::vector<int32_t> f(m), c(m), mq(m), no(m), nm(m); std::vector<int64_t> ps(m);
-                std::vector<uint32_t> ops(m * (size_t)w.s_ops_stride);
-                int rc = snapgpu_sam_fields_single(ctx, (uint32_t)m, sb.data(), sq.data(), so.data(), sfc.data(), sdl.data(), rr.data(), o.use_m ? 1 : 0,
-                                                   f.data(), c.data(), ps.data(), mq.data(), ops.data(), w.s_ops_stride, no.data(), nm.data(), stale.data());
-                if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_sam_fields_single", rc);
-                for (size_t x = 0; x < m; x++) {
-                    const size_t r = sus[x], rd = w.su_read[r], k = rd / 2;
-                    if (nm[x] == -2) too_small = true;
-                    w.s_flag[r] = f[x] | 0x100; w.s_contig[r] = c[x]; w.s_pos[r] = ps[x]; w.s_mapq[r] = mq[x]; w.s_n_ops[r] = no[x]; w.s_nm[r] = nm[x];
-                    memcpy(&w.s_ops[r * (size_t)w.s_ops_stride], &ops[x * (size_t)w.s_ops_stride], (size_t)w.s_ops_stride * 4);
-                    // (a single-end record is written without the aligner's soft clipping unless it went through the affine-gap writer: sam_fields.h)
-                    const bool ag = ag_branch(rr[x].used_affine_gap_scoring, rr[x].score);
-                    const HostRes hr = {rr[x].status, rr[x].direction, rr[x].score, rr[x].mapq, rr[x].clipping_for_read_adjustment, rr[x].used_affine_gap_scoring, rr[x].bases_clipped_before,
-                                        rr[x].bases_clipped_after, rr[x].supplementary, (long long)rr[x].location};
-                    leave_behind(rd, j + 1 < per_pair[k].size(), ag, rr[x].status, f[x], ps[x], no[x], &ops[x * (size_t)w.s_ops_stride], ag ? rr[x].bases_clipped_before : 0, sdl[x], hr, false);
-                }
-            }
-        }
-        if (!too_small) break;
-        if (w.ops_stride >= 4096) die("a cigar needs more than 4096 operations");
-        w.ops_stride *= 4; w.s_ops_stride = w.ops_stride;
+    std::vector<std::vector<Work::Emit>> per_pair;                       // per pair: its entries of w.emit, in order
+    std::vector<int32_t> carry;                                          // per read: the back clipping its records so far have left
+    bool too_small;                                                      // a cigar did not fit its row: the rounds are run again with a larger stride
+    bool ag_branch(int used_ag, int score) const { return o.p.use_affine_gap && (used_ag != 0 || score > 0); }
+    HostRec on_host(size_t rd, const HostRes &hr, bool paired_rec) const      // (exact: the record loop with the Read's state as it is)
+    {
+        return host_record(o, ctx, b.bases.data() + b.offsets[rd], b.quals.data() + b.offsets[rd], (int)(b.offsets[rd + 1] - b.offsets[rd]), front_clip[rd], data_len[rd], carry[rd], hr, paired_rec);
     }
-}
-
-// ---------------------------------------------------------------------------------------- formatting stage
-static void put_bam_record(std::string &o, const std::vector<Contig> &contigs, const char *qname, size_t qn, int flag, int contig, long long pos1,
-                           int mapq, const uint32_t *ops, int n_ops, int mate_contig, long long pnext1, long long tlen,
-                           const char *s, const char *q, size_t U, int nm, bool with_qs, int qs);
-static inline void put_cigar(std::string &o, const Work &w, size_t i)
-{
-    if (w.n_ops[i] < 0) { o.push_back('*'); return; }
-    for (int c = 0; c < w.n_ops[i]; c++) { const uint32_t op = w.ops[i * (size_t)w.ops_stride + (size_t)c]; put_uint(o, op >> 4); o.push_back("MIDNSHP=X"[op & 15]); }
-}
-static inline void put_seq_qual(std::string &o, const char *s, const char *q, size_t U, bool rc)
-{
-    const size_t at = o.size();
-    o.resize(at + 2 * U + 1);
-    char *d = &o[at];
-    if (rc) { for (size_t j = 0; j < U; j++) { d[U - 1 - j] = complement(s[j]); d[U + 1 + U - 1 - j] = q[j]; } }
-    else { memcpy(d, s, U); memcpy(d + U + 1, q, U); }
-    d[U] = '\t';
-}
-static const char AUX_TAIL[] = "\tRG:Z:FASTQ\tPL:Z:Illumina\tPU:Z:pu\tLB:Z:lb\tSM:Z:sm";
-
-static void format_single(const std::vector<Contig> &contigs, Work &w)
-{
-    const Batch &b = w.b;
-    std::string &o = w.text;
-    o.clear(); o.reserve(w.rec_read.size() * 420);
-    for (size_t i = 0; i < w.rec_read.size(); i++) {
-        const size_t rd = w.rec_read[i];
-        const char *s = b.bases.data() + b.offsets[rd], *q = b.quals.data() + b.offsets[rd];
+    // the state a written record leaves on its Read: `passed_len` is the data length the record was computed with
+    // (`hr` / `paired_rec`: the result the record was computed from, for the two cases in which the record alone does not say what it left
+    //  behind -- a record given up after clipping adjustments, and a reverse-complement record at the first base of a contig, whose leading
+    //  soft clip may have been cut short there: the record loop is then run on the host for that one record, with the Read's state as it
+    //  is, and ITS back clipping is what the next record of the read starts from.  Until round 4 these two cases stopped the program.)
+    void leave_behind(size_t rd, bool more, bool ag, int status_in, int flag, int64_t pos, int n_ops, const uint32_t *ops, int clipped_before, int passed_len, const HostRes &hr, bool paired_rec)
+    {
+        if (!more || !ag) return;
         const size_t U = (size_t)(b.offsets[rd + 1] - b.offsets[rd]);
-        const char *nm = b.names.data() + b.name_off[rd]; size_t nl = b.name_off[rd + 1] - b.name_off[rd];
-        const void *sp = memchr(nm, ' ', nl);                              // "illegal in SAM: truncate at the space" (SAM.cpp:2001-2004)
-        if (sp) nl = (size_t)((const char *)sp - nm);
-        if (w.bam) {
-            put_bam_record(o, contigs, nm, nl, w.flag[i], w.contig[i], w.pos[i], w.mapq[i], w.ops.data() + i * (size_t)w.ops_stride, w.n_ops[i], -1, 0, 0, s, q, U, w.nm[i], false, 0);
-            w.mapped += (w.flag[i] & 0x4) == 0;
-            continue;
+        if (((flag & 0x4) && status_in != SNAPGPU_NotFound) || ((flag & 0x10) && n_ops > 0 && pos == 1)) {
+            carry[rd] = on_host(rd, hr, paired_rec).back_after;
+            if (o.verbose) fprintf(stderr, "snapgpu-sam: one record's state recomputed on the host (%s), back clipping left: %d\n", (flag & 0x4) ? "given up after clipping adjustments" : "reverse complement at the first base of a contig", carry[rd]);
+            return;
         }
-        o.append(nm, nl); o.push_back('\t'); put_int(o, w.flag[i]); o.push_back('\t');
-        if (w.contig[i] >= 0) o += contigs[(size_t)w.contig[i]].name; else o.push_back('*');
-        o.push_back('\t'); put_int(o, w.pos[i]); o.push_back('\t'); put_int(o, w.mapq[i]); o.push_back('\t');
-        put_cigar(o, w, i);
-        o += "\t*\t0\t0\t";
-        put_seq_qual(o, s, q, U, (w.flag[i] & 0x10) != 0);
-        o += "\tPG:Z:SNAP\tNM:i:"; put_int(o, w.nm[i]); o += AUX_TAIL; o.push_back('\n');
-        w.mapped += (w.flag[i] & 0x4) == 0;
+        if (!(flag & 0x10) || n_ops <= 0) return;
+        const int lead = (ops[0] & 15u) == 4u ? (int)(ops[0] >> 4) : 0;
+        const int left = lead - ((int)U - passed_len - front_clip[rd]) - clipped_before;
+        if (left < 0) die("internal error: leading soft clip shorter than the read's own clipping");
+        if (left > 0) carry[rd] = left;                             // (device-computed records start from carry == 0: the others go through host_record)
     }
-}
+    void host_pair_unit(uint32_t u)
+    {
+        const size_t k = w.pu_pair[u];
+        const snapgpu_paired_result &r = pu_res[u];
+        HostRec rec[2];
+        for (size_t v = 0; v < 2; v++) { rec[v] = on_host(2 * k + v, host_res(r, (int)v), true); carry[2 * k + v] = rec[v].back_after; }
+        for (size_t v = 0; v < 2; v++) {
+            const size_t dst = 2 * u + v;
+            int fl, ct, rn; long long ps, pn, tl;
+            host_mate_info(rec[v], rec[1 - v], v == 0, r.aligned_as_pair != 0, fl, ct, ps, rn, pn, tl);
+            if (!store_host_record(w.rec, dst, rec[v], fl | (w.pu_secondary[u] ? 0x100 : 0), ct, ps)) { too_small = true; continue; }
+            w.rnext[dst] = rn; w.pnext[dst] = pn; w.tlen[dst] = tl;
+        }
+        const unsigned long long l0 = rec[0].final_loc < 0 ? ~0ull : (unsigned long long)rec[0].final_loc, l1 = rec[1].final_loc < 0 ? ~0ull : (unsigned long long)rec[1].final_loc;
+        w.first_written[u] = l0 <= l1 ? 0 : 1;                    // ReadWriter.cpp:481-488
+    }
+    void device_pair_units(const std::vector<uint32_t> &pus, size_t j)
+    {
+        const size_t m = pus.size();
+        ReadGather g; PairedResultList rr(m);
+        for (size_t x = 0; x < m; x++) {
+            rr[x] = pu_res[pus[x]];
+            for (size_t v = 0; v < 2; v++) { const size_t i = 2 * (size_t)w.pu_pair[pus[x]] + v; gather_read(g, b, i, front_clip[i], data_len[i] - carry[i]); }
+        }
+        Records t; t.ops_stride = w.rec.ops_stride; t.assign(2 * m); t.ops.resize(2 * m * (size_t)t.ops_stride);
+        std::vector<int32_t> rn(2 * m), fw(m), stale(2 * m); std::vector<int64_t> pn(2 * m), tl(2 * m);
+        int rc = snapgpu_sam_fields_paired(ctx, (uint32_t)m, g.b.data(), g.q.data(), g.off.data(), g.fc.data(), g.dl.data(), rr.data(), o.use_m ? 1 : 0,
+                                           t.flag.data(), t.contig.data(), t.pos.data(), t.mapq.data(), t.ops.data(), t.ops_stride, t.n_ops.data(), t.nm.data(), rn.data(), pn.data(), tl.data(), fw.data(), stale.data());
+        if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_sam_fields_paired", rc);
+        if (cigar_overflowed(t.nm.data(), 2 * m)) too_small = true;
+        for (size_t x = 0; x < m; x++) {
+            const size_t u = pus[x], k = w.pu_pair[u];
+            w.first_written[u] = fw[x];
+            for (size_t v = 0; v < 2; v++) {
+                const size_t src = 2 * x + v, dst = 2 * u + v;
+                copy_record(w.rec, dst, t, src, w.pu_secondary[u] ? 0x100 : 0);
+                w.rnext[dst] = rn[src]; w.pnext[dst] = pn[src]; w.tlen[dst] = tl[src];
+                leave_behind(2 * k + v, j + 1 < per_pair[k].size(), ag_branch(rr[x].used_affine_gap_scoring[v], rr[x].score[v]), rr[x].status[v], t.flag[src], t.pos[src], t.n_ops[src],
+                             t.cigar(src), rr[x].bases_clipped_before[v], g.dl[src], host_res(rr[x], (int)v), true);
+            }
+        }
+    }
+    void device_single_units(const std::vector<uint32_t> &sus, size_t j)      // records of their own, without mate information (format->writeRead, ReadWriter.cpp:521-527)
+    {
+        const size_t m = sus.size();
+        ReadGather g; ResultList rr(m);
+        for (size_t x = 0; x < m; x++) { const size_t i = w.su_read[sus[x]]; rr[x] = su_res[sus[x]]; gather_read(g, b, i, front_clip[i], data_len[i] - carry[i]); }
+        Records t; t.ops_stride = w.srec.ops_stride; t.assign(m); t.ops.resize(m * (size_t)t.ops_stride);
+        std::vector<int32_t> stale(m);
+        int rc = snapgpu_sam_fields_single(ctx, (uint32_t)m, g.b.data(), g.q.data(), g.off.data(), g.fc.data(), g.dl.data(), rr.data(), o.use_m ? 1 : 0,
+                                           t.flag.data(), t.contig.data(), t.pos.data(), t.mapq.data(), t.ops.data(), t.ops_stride, t.n_ops.data(), t.nm.data(), stale.data());
+        if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_sam_fields_single", rc);
+        if (cigar_overflowed(t.nm.data(), m)) too_small = true;
+        for (size_t x = 0; x < m; x++) {
+            const size_t r = sus[x], rd = w.su_read[r];
+            copy_record(w.srec, r, t, x, 0x100);
+            // (a single-end record is written without the aligner's soft clipping unless it went through the affine-gap writer: sam_fields.h)
+            const bool ag = ag_branch(rr[x].used_affine_gap_scoring, rr[x].score);
+            leave_behind(rd, j + 1 < per_pair[rd / 2].size(), ag, rr[x].status, t.flag[x], t.pos[x], t.n_ops[x], t.cigar(x), ag ? rr[x].bases_clipped_before : 0, g.dl[x], host_res(rr[x]), false);
+        }
+    }
+    void rounds()
+    {
+        per_pair.assign(np, std::vector<Work::Emit>());
+        for (const Work::Emit &e : w.emit) per_pair[e.single ? w.su_read[e.unit] / 2 : w.pu_pair[e.unit]].push_back(e);
+        size_t n_rounds = 0;
+        for (size_t k = 0; k < np; k++) if (per_pair[k].size() > n_rounds) n_rounds = per_pair[k].size();
+        const bool host_all = o.host_loop;
+        for (;;) {                                                           // (again with a larger stride when a cigar did not fit)
+            too_small = false;
+            carry.assign(n, 0);
+            w.rec.ops.assign(w.rec.flag.size() * (size_t)w.rec.ops_stride, 0); w.srec.ops.assign(w.srec.flag.size() * (size_t)w.srec.ops_stride, 0);
+            for (size_t j = 0; j < n_rounds; j++) {
+                std::vector<uint32_t> pus, sus, pus_host, sus_host;          // this round's pair units / single units; `_host`: a read arrives with back clipping
+                for (size_t k = 0; k < np; k++) {
+                    if (j >= per_pair[k].size()) continue;
+                    const Work::Emit &e = per_pair[k][j];
+                    if (e.single) (host_all || carry[w.su_read[e.unit]] > 0 ? sus_host : sus).push_back(e.unit);
+                    else (host_all || carry[2 * k] > 0 || carry[2 * k + 1] > 0 ? pus_host : pus).push_back(e.unit);
+                }
+                for (uint32_t u : pus_host) host_pair_unit(u);
+                for (uint32_t r : sus_host) {
+                    const size_t rd = w.su_read[r];
+                    const HostRec rec = on_host(rd, host_res(su_res[r]), false);
+                    carry[rd] = rec.back_after;
+                    if (!store_host_record(w.srec, r, rec, rec.flag | 0x100, rec.contig, rec.pos)) too_small = true;
+                }
+                if (!pus.empty()) device_pair_units(pus, j);
+                if (!sus.empty()) device_single_units(sus, j);
+            }
+            if (!too_small) break;
+            grow_stride(w.rec.ops_stride); w.srec.ops_stride = w.rec.ops_stride;
+        }
+    }
+};
 
-static void format_paired(const std::vector<Contig> &contigs, Work &w)
+static void gpu_paired(const Options &o, FeederCtx &fc, Work &w)
 {
     const Batch &b = w.b;
-    std::string &o = w.text;
-    o.clear(); o.reserve(w.emit.size() * 880);
-    for (const Work::Emit &e : w.emit) {
-        if (e.single) {
-            // a mate's single-end secondary result: SAMFormat::writeRead without a mate -- the whole read id (the "/1" stays: the call is given
-            // getIdLength(), ReadWriter.cpp:521), no mate fields, no QS
-            const size_t r = e.unit, rd = w.su_read[r];
-            const char *s = b.bases.data() + b.offsets[rd], *q = b.quals.data() + b.offsets[rd];
-            const size_t U = (size_t)(b.offsets[rd + 1] - b.offsets[rd]);
-            const char *nm = b.names.data() + b.name_off[rd]; size_t nl = b.name_off[rd + 1] - b.name_off[rd];
-            const void *sp = memchr(nm, ' ', nl);
-            if (sp) nl = (size_t)((const char *)sp - nm);
-            if (w.bam) {
-                put_bam_record(o, contigs, nm, nl, w.s_flag[r], w.s_contig[r], w.s_pos[r], w.s_mapq[r], w.s_ops.data() + r * (size_t)w.s_ops_stride, w.s_n_ops[r], -1, 0, 0, s, q, U, w.s_nm[r], false, 0);
-            } else {
-                o.append(nm, nl); o.push_back('\t'); put_int(o, w.s_flag[r]); o.push_back('\t');
-                if (w.s_contig[r] >= 0) o += contigs[(size_t)w.s_contig[r]].name; else o.push_back('*');
-                o.push_back('\t'); put_int(o, w.s_pos[r]); o.push_back('\t'); put_int(o, w.s_mapq[r]); o.push_back('\t');
-                if (w.s_n_ops[r] < 0) o.push_back('*');
-                else for (int c = 0; c < w.s_n_ops[r]; c++) { const uint32_t op = w.s_ops[r * (size_t)w.s_ops_stride + (size_t)c]; put_uint(o, op >> 4); o.push_back("MIDNSHP=X"[op & 15]); }
-                o += "\t*\t0\t0\t";
-                put_seq_qual(o, s, q, U, (w.s_flag[r] & 0x10) != 0);
-                o += "\tPG:Z:SNAP\tNM:i:"; put_int(o, w.s_nm[r]); o += AUX_TAIL; o.push_back('\n');
-            }
-            w.mapped += (w.s_flag[r] & 0x4) == 0;
-            continue;
-        }
-        const size_t u = e.unit, k = w.pu_pair[u];
-        // QNAME: the /1 /2 suffixes go when both names carry them (ReadWriter.cpp:392-404)
-        const char *n0 = b.names.data() + b.name_off[2 * k], *n1 = b.names.data() + b.name_off[2 * k + 1];
-        size_t idl[2] = { (size_t)(b.name_off[2 * k + 1] - b.name_off[2 * k]), (size_t)(b.name_off[2 * k + 2] - b.name_off[2 * k + 1]) };
-        if (idl[0] == idl[1] && idl[0] > 2 && n0[idl[0] - 2] == '/' && n1[idl[0] - 2] == '/') {
-            const char c0 = n0[idl[0] - 1], c1 = n1[idl[1] - 1];
-            if ((c0 == '1' || c0 == '2') && (c1 == '1' || c1 == '2') && c0 != c1) { idl[0] -= 2; idl[1] -= 2; }
-        }
-        for (int ord = 0; ord < 2; ord++) {
-            const int v = ord == 0 ? w.first_written[u] : 1 - w.first_written[u];
-            const size_t i = 2 * u + (size_t)v;                                             // fields
-            const size_t rd = 2 * k + (size_t)v, rm = 2 * k + (size_t)(1 - v);              // the read and its mate in the batch
-            const char *s = b.bases.data() + b.offsets[rd], *q = b.quals.data() + b.offsets[rd];
-            const size_t U = (size_t)(b.offsets[rd + 1] - b.offsets[rd]);
-            const char *nm = v == 0 ? n0 : n1;
-            size_t qn = idl[v];
-            const void *sp = memchr(nm, ' ', qn);
-            if (sp) qn = (size_t)((const char *)sp - nm);
-            int mqs = 0;                                                // QS: the mate's qualities >= 15, summed (SAM.cpp:1826-1837)
-            { const unsigned char *mq = (const unsigned char *)b.quals.data() + b.offsets[rm]; const size_t mu = (size_t)(b.offsets[rm + 1] - b.offsets[rm]);
-              for (size_t j = 0; j < mu; j++) { const int x = (int)mq[j] - '!'; mqs += x >= 15 ? (x != 255) * x : 0; } }
-            if (w.bam) {
-                const int mate_contig = w.rnext[i] == -2 ? w.contig[i] : w.rnext[i];
-                put_bam_record(o, contigs, nm, qn, w.flag[i], w.contig[i], w.pos[i], w.mapq[i], w.ops.data() + i * (size_t)w.ops_stride, w.n_ops[i],
-                               mate_contig, w.pnext[i], w.tlen[i], s, q, U, w.nm[i], true, mqs);
-                w.mapped += (w.flag[i] & 0x4) == 0;
-                continue;
-            }
-            o.append(nm, qn); o.push_back('\t'); put_int(o, w.flag[i]); o.push_back('\t');
-            if (w.contig[i] >= 0) o += contigs[(size_t)w.contig[i]].name; else o.push_back('*');
-            o.push_back('\t'); put_int(o, w.pos[i]); o.push_back('\t'); put_int(o, w.mapq[i]); o.push_back('\t');
-            put_cigar(o, w, i); o.push_back('\t');
-            if (w.rnext[i] == -2) o.push_back('='); else if (w.rnext[i] >= 0) o += contigs[(size_t)w.rnext[i]].name; else o.push_back('*');
-            o.push_back('\t'); put_int(o, w.pnext[i]); o.push_back('\t'); put_int(o, (int)w.tlen[i]); o.push_back('\t');
-            put_seq_qual(o, s, q, U, (w.flag[i] & 0x10) != 0);
-            o += "\tPG:Z:SNAP\tNM:i:"; put_int(o, w.nm[i]); o += AUX_TAIL; o += "\tQS:i:"; put_int(o, mqs); o.push_back('\n');
-            w.mapped += (w.flag[i] & 0x4) == 0;
-        }
+    const size_t n = b.n();
+    w.max_len = 0;
+    for (size_t i = 0; i < n; i++) { const uint32_t U = (uint32_t)(b.offsets[i + 1] - b.offsets[i]); if (U > w.max_len) w.max_len = U; }
+    PairedBatch pb(o, ctx_for(o, fc, w.max_len), w);
+    if (o.paths.paired_one_call && pb.np > 0 && pb.one_call()) return;
+    pb.align_calls(); pb.emit_list();
+    const std::vector<snapgpu_paired_result> &pu_res = pb.pu_res;
+    const size_t nu = pu_res.size(), nrec = 2 * nu;
+    size_pair_fields(o, w, nu, pb.su_res.size());
+    if (nu == pb.np && pb.su_res.empty()) {                                 // one result per pair: one call over the batch as it is
+        std::vector<int32_t> stale(nrec);
+        with_growing_stride(w.rec, nrec, [&] {
+            int rc = snapgpu_sam_fields_paired(pb.ctx, (uint32_t)nu, b.bases.data(), b.quals.data(), b.offsets.data(), pb.front_clip.data(), pb.data_len.data(), pu_res.data(),
+                                               o.use_m ? 1 : 0, w.rec.flag.data(), w.rec.contig.data(), w.rec.pos.data(), w.rec.mapq.data(), w.rec.ops.data(), w.rec.ops_stride, w.rec.n_ops.data(),
+                                               w.rec.nm.data(), w.rnext.data(), w.pnext.data(), w.tlen.data(), w.first_written.data(), stale.data());
+            if (rc != SNAPGPU_OK) fail_rc(pb.ctx, "snapgpu_sam_fields_paired", rc);
+        });
+        return;
     }
+    pb.rounds();
 }
 
 // ---------------------------------------------------------------------------------------- BAM (SNAPLib/Bam.cpp)
@@ -1509,6 +1397,101 @@ static void bgzf_append(std::string &out, const char *data, size_t n)
     }
 }
 
+// ---------------------------------------------------------------------------------------- formatting stage
+static inline void put_cigar(std::string &o, const Records &r, size_t i)
+{
+    if (r.n_ops[i] < 0) { o.push_back('*'); return; }
+    const uint32_t *ops = r.cigar(i);
+    for (int c = 0; c < r.n_ops[i]; c++) { put_uint(o, ops[c] >> 4); o.push_back("MIDNSHP=X"[ops[c] & 15]); }
+}
+static inline void put_seq_qual(std::string &o, const char *s, const char *q, size_t U, bool rc)
+{
+    const size_t at = o.size();
+    o.resize(at + 2 * U + 1);
+    char *d = &o[at];
+    if (rc) { for (size_t j = 0; j < U; j++) { d[U - 1 - j] = complement(s[j]); d[U + 1 + U - 1 - j] = q[j]; } }
+    else { memcpy(d, s, U); memcpy(d + U + 1, q, U); }
+    d[U] = '\t';
+}
+static const char AUX_TAIL[] = "\tRG:Z:FASTQ\tPL:Z:Illumina\tPU:Z:pu\tLB:Z:lb\tSM:Z:sm";
+struct ReadText { const char *s, *q; size_t U; const char *name; size_t name_len; };      // a read of the batch as it was parsed
+static inline ReadText read_text(const Batch &b, size_t rd)
+{
+    return ReadText{b.bases.data() + b.offsets[rd], b.quals.data() + b.offsets[rd], (size_t)(b.offsets[rd + 1] - b.offsets[rd]), b.names.data() + b.name_off[rd], (size_t)(b.name_off[rd + 1] - b.name_off[rd])};
+}
+struct MateFields { int rnext; long long pnext, tlen; int qs; };          // what a mate's record has beyond a single-end one (rnext: -1 "*", -2 "=", else a contig)
+// record i of `r` for read `rd`, as a SAM line or a BAM record; QNAME: the first qn bytes of the read's name, cut at a space ("illegal in
+// SAM: truncate at the space", SAM.cpp:2001-2004); m: the mate fields and QS of a pair's record, NULL for a record without a mate
+static inline void put_record(std::string &o, const std::vector<Contig> &contigs, bool bam, const Records &r, size_t i, const ReadText &rd, size_t qn, const MateFields *m)
+{
+    const void *sp = memchr(rd.name, ' ', qn);
+    if (sp) qn = (size_t)((const char *)sp - rd.name);
+    if (bam) {
+        put_bam_record(o, contigs, rd.name, qn, r.flag[i], r.contig[i], r.pos[i], r.mapq[i], r.cigar(i), r.n_ops[i], m ? (m->rnext == -2 ? r.contig[i] : m->rnext) : -1,
+                       m ? m->pnext : 0, m ? m->tlen : 0, rd.s, rd.q, rd.U, r.nm[i], m != NULL, m ? m->qs : 0);
+        return;
+    }
+    o.append(rd.name, qn); o.push_back('\t'); put_int(o, r.flag[i]); o.push_back('\t');
+    if (r.contig[i] >= 0) o += contigs[(size_t)r.contig[i]].name; else o.push_back('*');
+    o.push_back('\t'); put_int(o, r.pos[i]); o.push_back('\t'); put_int(o, r.mapq[i]); o.push_back('\t');
+    put_cigar(o, r, i);
+    if (m) {
+        o.push_back('\t');
+        if (m->rnext == -2) o.push_back('='); else if (m->rnext >= 0) o += contigs[(size_t)m->rnext].name; else o.push_back('*');
+        o.push_back('\t'); put_int(o, m->pnext); o.push_back('\t'); put_int(o, (int)m->tlen); o.push_back('\t');
+    } else o += "\t*\t0\t0\t";
+    put_seq_qual(o, rd.s, rd.q, rd.U, (r.flag[i] & 0x10) != 0);
+    o += "\tPG:Z:SNAP\tNM:i:"; put_int(o, r.nm[i]); o += AUX_TAIL;
+    if (m) { o += "\tQS:i:"; put_int(o, m->qs); }
+    o.push_back('\n');
+}
+
+static void format_single(const std::vector<Contig> &contigs, Work &w)
+{
+    std::string &o = w.text;
+    o.clear(); o.reserve(w.rec_read.size() * 420);
+    for (size_t i = 0; i < w.rec_read.size(); i++) {
+        const ReadText rd = read_text(w.b, w.rec_read[i]);
+        put_record(o, contigs, w.bam, w.rec, i, rd, rd.name_len, NULL);
+        w.mapped += (w.rec.flag[i] & 0x4) == 0;
+    }
+}
+
+static void format_paired(const std::vector<Contig> &contigs, Work &w)
+{
+    const Batch &b = w.b;
+    std::string &o = w.text;
+    o.clear(); o.reserve(w.emit.size() * 880);
+    for (const Work::Emit &e : w.emit) {
+        if (e.single) {
+            // a mate's single-end secondary result: SAMFormat::writeRead without a mate -- the whole read id (the "/1" stays: the call is given
+            // getIdLength(), ReadWriter.cpp:521), no mate fields, no QS
+            const ReadText rd = read_text(b, w.su_read[e.unit]);
+            put_record(o, contigs, w.bam, w.srec, e.unit, rd, rd.name_len, NULL);
+            w.mapped += (w.srec.flag[e.unit] & 0x4) == 0;
+            continue;
+        }
+        const size_t u = e.unit, k = w.pu_pair[u];
+        // QNAME: the /1 /2 suffixes go when both names carry them (ReadWriter.cpp:392-404)
+        const char *n0 = b.names.data() + b.name_off[2 * k], *n1 = b.names.data() + b.name_off[2 * k + 1];
+        size_t idl[2] = { (size_t)(b.name_off[2 * k + 1] - b.name_off[2 * k]), (size_t)(b.name_off[2 * k + 2] - b.name_off[2 * k + 1]) };
+        if (idl[0] == idl[1] && idl[0] > 2 && n0[idl[0] - 2] == '/' && n1[idl[0] - 2] == '/') {
+            const char c0 = n0[idl[0] - 1], c1 = n1[idl[1] - 1];
+            if ((c0 == '1' || c0 == '2') && (c1 == '1' || c1 == '2') && c0 != c1) { idl[0] -= 2; idl[1] -= 2; }
+        }
+        for (int ord = 0; ord < 2; ord++) {
+            const int v = ord == 0 ? w.first_written[u] : 1 - w.first_written[u];
+            const size_t i = 2 * u + (size_t)v;                                             // fields
+            const ReadText rd = read_text(b, 2 * k + (size_t)v), mate = read_text(b, 2 * k + (size_t)(1 - v));
+            int mqs = 0;                                                // QS: the mate's qualities >= 15, summed (SAM.cpp:1826-1837)
+            for (size_t j = 0; j < mate.U; j++) { const int x = (int)(unsigned char)mate.q[j] - '!'; mqs += x >= 15 ? (x != 255) * x : 0; }
+            const MateFields m = {w.rnext[i], w.pnext[i], w.tlen[i], mqs};
+            put_record(o, contigs, w.bam, w.rec, i, rd, idl[v], &m);
+            w.mapped += (w.rec.flag[i] & 0x4) == 0;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------- main
 int main(int argc, char **argv)
 {
@@ -1554,6 +1537,7 @@ int main(int argc, char **argv)
     if (o.ae && o.paired) die("-ae is implemented for `single` only (the paired-end aligners' use of AlignmentAdjuster is not: DESIGN.md section 16)");
     if (o.ae && o.clip_front) die("-ae with front clipping (-C+x) is not supported: the adjuster is restated for reads the reader has not clipped at the front");
     o.bam = out_path.size() > 4 && out_path.compare(out_path.size() - 4, 4, ".bam") == 0;     // by extension, like the reference (AlignerOptions.cpp)
+    choose_paths(o);
     const bool batch_auto = o.batch_reads == 0;
     if (batch_auto) o.batch_reads = 262144;                                // (the mapped reader, which knows the file's size, picks below)
     if (o.batch_reads < (o.paired ? 2u : 1u)) die("-b must be at least 1 (2 for paired)");
@@ -1675,7 +1659,7 @@ int main(int argc, char **argv)
         const auto t0 = std::chrono::steady_clock::now();
         use_map = mf.index(o.n_parse) && (!o.paired || mf2.index(o.n_parse));
         if (use_map && o.paired && mf.n_lines != mf2.n_lines) die(mf.n_lines > mf2.n_lines ? "the second FASTQ file has fewer reads than the first" : "the second FASTQ file has more reads than the first");
-        if (use_map && getenv("SNAPGPU_SAM_VERBOSE")) fprintf(stderr, "snapgpu-sam: %llu FASTQ records indexed in %.2f s\n", (unsigned long long)(mf.n_lines / 4), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        if (use_map && o.verbose) fprintf(stderr, "snapgpu-sam: %llu FASTQ records indexed in %.2f s\n", (unsigned long long)(mf.n_lines / 4), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     }
     if (!use_map) { mf.close(); mf2.close(); }
     std::vector<std::thread> parsers;
@@ -1794,7 +1778,7 @@ int main(int argc, char **argv)
     if (rename(partial_path.c_str(), out_path.c_str()) != 0) die("cannot rename the finished output to ", out_path.c_str());
     g_partial_path.clear();
     pass_s.push_back(std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ready).count());
-    if (getenv("SNAPGPU_SAM_VERBOSE"))
+    if (o.verbose)
         fprintf(stderr, "snapgpu-sam: pass %d timeline: pipeline up at %.3f s, first batch written at %.3f s, last at %.3f s, threads joined at %.3f s, file closed and renamed at %.3f s\n", pass + 1,
                 std::chrono::duration<double>(t_pipe - t_ready).count(), t_first_s, std::chrono::duration<double>(t_written - t_ready).count(),
                 std::chrono::duration<double>(t_joined - t_ready).count(), pass_s.back());
@@ -1810,16 +1794,16 @@ int main(int argc, char **argv)
     }
     for (size_t g = primary.size(); g-- > 0;) snapgpu_destroy(primary[g]);
     fprintf(stderr, "snapgpu-sam: %llu reads, %llu mapped records, %d GPU(s) x %d feeder(s), %d formatter thread(s)\n", total, mapped, o.n_gpus, o.ctx_per_gpu, o.n_format);
-    if (device_bam_switch(o) && (!o.paired || o.om < 0))                     // (the last pass's, like the counts above)
+    if (o.paths.output == Options::DeviceBam || o.paths.output == Options::DeviceBgzf)                     // (the last pass's, like the counts above)
         fprintf(stderr, "snapgpu-sam: BAM records from the device: %llu batches, %llu records\n", g_bam_batches.load(), g_bam_records.load());
-    if (device_bgzf_switch(o) && (!o.paired || o.om < 0))
+    if (o.paths.output == Options::DeviceBgzf)
         fprintf(stderr, "snapgpu-sam: BGZF blocks from the device: %llu batches, %llu blocks, %llu -> %llu bytes\n", g_bgzf_batches.load(), g_bgzf_members.load(),
                 g_bgzf_in.load(), g_bgzf_out.load());
     {   // (AlignerContext.cpp:489-543 prints reads/s over the alignment phase, the index load apart: the same split here)
         const double s_stream = pass_s.back();                              // (the last pass; with -passes N each pass printed its own line above)
         fprintf(stderr, "snapgpu-sam: index resident after %.2f s; FASTQ -> %s in %.2f s = %.0f reads/s (%s reader, %d parser thread(s))\n", s_load, o.bam ? "BAM" : "SAM", s_stream,
                 s_stream > 0 ? (double)total / s_stream : 0.0, use_map ? "mapped" : "sequential", use_map ? o.n_parse : 1);
-        if (getenv("SNAPGPU_SAM_VERBOSE")) {
+        if (o.verbose) {
             fprintf(stderr, "snapgpu-sam: thread-seconds: parse %.2f | feeders: prepare %.2f, align call %.2f, records %.2f, SAM-fields call %.2f | format %.2f | write %.2f\n",
                     g_ns_parse.load() * 1e-9, g_ns_prep.load() * 1e-9, g_ns_align.load() * 1e-9, g_ns_mid.load() * 1e-9, g_ns_samcall.load() * 1e-9, g_ns_format.load() * 1e-9, g_ns_write.load() * 1e-9);
             // the same per THREAD and per PASS: the wall time each stage would take alone with its threads (a stage near the pass's own time is the pipeline's limit)
