@@ -10,6 +10,7 @@ import zlib
 
 import numpy as np
 
+from tests import deflate_util as du
 from tests import util
 
 SYMBOLS = ("snapgpu_bgzf_compress", "snapgpu_bgzf_compress_device", "snapgpu_align_sam_single_bgzf", "snapgpu_align_sam_paired_bgzf")
@@ -35,8 +36,9 @@ def as_bytes(x):
     return x if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8).tobytes()
 
 
-def check_output(data, block_input, bgzf, member_begin, n_members=None, bgzf_bytes=None):
-    """every member of `bgzf` against zlib / gzip / struct; returns the members' sizes"""
+def check_output(data, block_input, bgzf, member_begin, n_members=None, bgzf_bytes=None, blocks=None):
+    """every member of `bgzf` against zlib / gzip / struct; returns the members' sizes.  blocks: a list that receives every member's parsed
+    block (check_coded_member)"""
     data = as_bytes(data); out = as_bytes(bgzf)
     mb = [int(x) for x in member_begin]
     nm = max(1, -(-len(data) // block_input))
@@ -59,9 +61,65 @@ def check_output(data, block_input, bgzf, member_begin, n_members=None, bgzf_byt
         assert len(d.unused_data) == 8 and d.unused_data == mem[-8:], (m, len(d.unused_data))      # the payload ends exactly at the trailer
         crc, isize = struct.unpack("<II", mem[-8:])
         assert crc == zlib.crc32(src) and isize == len(src), m
+        parsed = check_coded_member(src, mem)
+        if blocks is not None:
+            blocks.append(parsed)
         sizes.append(e - b)
     assert gzip.decompress(out[:mb[-1]]) == data
     return sizes
+
+
+def check_coded_member(src, member):
+    """what the DEFLATE payload of one member is made of, read by tests/deflate_util.py (the RFC, not zlib and not the code under test): one
+    final block that replays to src and ends in the payload's last byte.  A stored block: LEN, NLEN and the bytes.  A dynamic block: matches
+    of 4 .. 258 bytes within 32768, 258 as symbol 285 alone; the three codes complete, within 15 / 15 / 7 bits, coding exactly the used
+    symbols and never giving a larger count a longer code (the exceptions are those bgzf.h names: one used distance symbol has one bit, no
+    match at all sends one distance length of zero, a code-length code with one used symbol gets a second one-bit symbol); HLIT, HDIST and
+    HCLEN minimal; the header's symbols those of a greedy run-length coder; and a payload below len + 5 bytes, what the stored block
+    would take.  Returns the parsed block."""
+    src = as_bytes(src); payload = as_bytes(member)[18:-8]
+    blocks, out, end = du.read_stream(payload)
+    assert len(blocks) == 1 and blocks[0].final == 1 and out == src
+    assert (end + 7) // 8 == len(payload), (end, len(payload))
+    b = blocks[0]
+    if not src:
+        assert payload == b"\x03\x00"
+        return b
+    if b.btype == 0:
+        assert payload[0] == 1 and b.stored_len == len(src) and b.stored_nlen == len(src) ^ 0xffff and b.stored_at == 5
+        assert payload[5:] == src and len(payload) == len(src) + 5
+        return b
+    assert b.btype == 2, b.btype
+    for length, lsym, dist, dsym in b.matches():
+        assert 4 <= length <= 258 and 1 <= dist <= 32768, (length, dist)
+        assert (length == 258) == (lsym == 285), (length, lsym)
+        assert du.LEN_BASE[lsym - 257] <= length and du.DIST_BASE[dsym] <= dist
+    ll_counts = [0] * 286; d_counts = [0] * 30; cl_counts = [0] * 19
+    ll_counts[256] = 1
+    for t in b.tokens:
+        if isinstance(t, int):
+            ll_counts[t] += 1
+        else:
+            ll_counts[t[1]] += 1; d_counts[t[3]] += 1
+    for s, _ in b.header_seq:
+        cl_counts[s] += 1
+    du.check_code_for_counts(ll_counts, b.ll_lengths, 15, "lit/len")
+    if any(d_counts):
+        du.check_code_for_counts(d_counts, b.d_lengths, 15, "distance", incomplete_single=True)
+    else:
+        assert b.d_lengths == [0], b.d_lengths
+    du.check_code_for_counts(cl_counts, b.cl_lengths, 7, "code-length", filler_ok=True)
+    assert du.kraft(b.cl_lengths, 7) == 128                                # (with the filler, complete in every case)
+    assert b.hlit == 257 or b.ll_lengths[-1], b.hlit
+    assert b.hdist == 1 or b.d_lengths[-1], b.hdist
+    assert b.hclen == 4 or b.cl_lengths[du.CL_ORDER[b.hclen - 1]], b.hclen
+    want = du.greedy_header_seq(b.ll_lengths + b.d_lengths)
+    assert len(b.header_seq) == len(want), (len(b.header_seq), len(want))
+    for i, (g, w) in enumerate(zip(b.header_seq, want)):
+        assert g == w, (i, g, w)
+    assert all(not (s == 16 and b.header_seq[i - 1][0] in (0, 17, 18)) for i, (s, _) in enumerate(b.header_seq) if i)
+    assert len(payload) < len(src) + 5, (len(payload), len(src))
+    return b
 
 
 def compress(a, data, block_input=MAX_BLOCK, **kw):
@@ -428,3 +486,384 @@ def check_tool(tool, d, mode, index_dir, fqs, opts, env=None, tool_opts=()):
     assert files[0][:sum(len(x) for x, _ in on[:header])] == files[1][:sum(len(x) for x, _ in off[:header])]      # the header block stays host-made
     assert any(x != y for (x, _), (y, _) in zip(on[header:-1], off[header:-1]))      # (and the payloads are the device's, not zlib's)
     return n, batches
+
+
+# ---- inputs that exist to reach one path of the coder each (tests/test_emu_bgzf_coder.py, tests/test_zz_gpu_bgzf_coder.py).  The lever is
+# window_input's: an all-equal filler touches one entry of the hash table, so a planted word keeps its entry and its second copy is matched
+# at exactly the gap it was planted at.  Every check asserts from the parsed stream that its path was reached, so a change to the matcher
+# that steers an input elsewhere fails with a message that says so.  The seeds were found with scripts/bgzf_find_inputs.py on the emulator.
+FILL, RUN, TERM = 0x61, 0x62, 0x7c
+
+
+def planted_input(size, pairs, seed, plain=False):
+    """`size` filler bytes and, for every (distance, length) of pairs, a word at a position q that is a multiple of 64 (lane 0 of its step)
+    with its one earlier copy `distance` back; the byte behind the earlier copy differs from the one behind the later copy, so the match is
+    `length` long.  A word is four random bytes and a run of one value (plain: random bytes throughout); a distance below the length
+    makes it periodic.  Returns (bytes, [q])."""
+    rng = np.random.default_rng(seed)
+    x = bytearray([FILL]) * size
+    busy = np.zeros(size + 8, bool)
+    values = np.array([v for v in range(256) if v not in (FILL, RUN, TERM)], np.uint8)
+    where = []
+    for d, L in pairs:
+        for _ in range(10000):
+            q = 64 * int(rng.integers((d + 8) // 64 + 1, (size - L - 8) // 64 + 1))
+            spans = [(q - d - 4, q + L + 4)] if d <= L + 8 else [(q - d - 4, q - d + L + 4), (q - 4, q + L + 4)]
+            if q + L + 4 <= size and not any(busy[a:b].any() for a, b in spans):
+                break
+        else:
+            raise AssertionError("no room for (%d, %d)" % (d, L))
+        for a, b in spans:
+            busy[a:b] = True
+        word = bytes(rng.choice(values, L if plain else 4)) + bytes([RUN]) * (0 if plain else L - 4)
+        n1 = min(d, L)
+        x[q - d:q - d + n1] = word[:n1]
+        if d > L:
+            x[q - d + L] = TERM
+        for i in range(L):
+            x[q + i] = x[q - d + i]
+        where.append(q)
+    return bytes(x), where
+
+
+def token_map(block):
+    """{position in the member: token} of a parsed block"""
+    out = {}; pos = 0
+    for t in block.tokens:
+        out[pos] = t
+        pos += 1 if isinstance(t, int) else t[0]
+    return out
+
+
+def compress_members(a, data, block_input=MAX_BLOCK):
+    """compress (every member through check_output) and the parsed block of every member"""
+    r = a.bgzfCompress(data, block_input)
+    assert not r["truncated"]
+    blocks = []
+    check_output(data, block_input, r["bgzf"][:r["bgzf_bytes"]], r["member_begin"], r["n_members"], r["bgzf_bytes"], blocks)
+    return blocks
+
+
+# (symbol 284 with extra value 31 would be 258 bytes, which is symbol 285's: its highest extra value is 30)
+LENGTH_SYMBOLS_LOW_HIGH = sorted({(257 + i, min(e, 30) if i == 27 else e) for i in range(1, 29) for e in (0, (1 << du.LEN_EXTRA[i]) - 1)})
+LENGTHS_LOW_HIGH = sorted(du.LEN_BASE[s - 257] + e for s, e in LENGTH_SYMBOLS_LOW_HIGH)                                  # 4 .. 258: 49 lengths
+DISTANCES_LOW_HIGH = sorted({du.DIST_BASE[i] + e for i in range(30) for e in (0, (1 << du.DIST_EXTRA[i]) - 1)})          # 1 .. 32768: 56 distances
+SYMBOL_SEEDS = (0, 0, 0, 1)                                                # one member each, 14 (distance, length) pairs a member
+
+
+def symbol_pairs():
+    """56 (distance, length): every distance once, and the 49 lengths taken in steps of five (5 and 49 have no common factor), so all occur"""
+    return [(d, LENGTHS_LOW_HIGH[(5 * i) % len(LENGTHS_LOW_HIGH)]) for i, d in enumerate(DISTANCES_LOW_HIGH)]
+
+
+def symbols_member(m, seed):
+    pairs = symbol_pairs()
+    per = -(-len(pairs) // len(SYMBOL_SEEDS))
+    return planted_input(MAX_BLOCK, pairs[m * per:(m + 1) * per], seed)[0], pairs[m * per:(m + 1) * per]
+
+
+def check_every_symbol(index, seeds=SYMBOL_SEEDS):
+    """every length symbol that the matcher can emit (258 .. 285: 257 is a match of three bytes, below its minimum of four) and every
+    distance symbol 0 .. 29, each with its lowest and its highest extra-bits value"""
+    a = make_aligner(index)
+    try:
+        data = b"".join(symbols_member(m, s)[0] for m, s in enumerate(seeds))
+        blocks = compress_members(a, data)
+        assert all(b.btype == 2 for b in blocks)
+        ms = [t for b in blocks for t in b.matches()]
+        got_l = {(t[1], t[0] - du.LEN_BASE[t[1] - 257]) for t in ms}; got_d = {(t[3], t[2] - du.DIST_BASE[t[3]]) for t in ms}
+        want_l = set(LENGTH_SYMBOLS_LOW_HIGH)
+        want_d = {(i, e) for i in range(30) for e in (0, (1 << du.DIST_EXTRA[i]) - 1)}
+        assert not want_l - got_l, ("length symbols / extra values not reached", sorted(want_l - got_l))
+        assert not want_d - got_d, ("distance symbols / extra values not reached", sorted(want_d - got_d))
+        assert not any(t[1] == 257 for t in ms)
+        return blocks
+    finally:
+        a.close()
+
+
+WINDOW_EDGE_SEED = 0
+
+
+def window_edge_input(seed=WINDOW_EDGE_SEED):
+    return planted_input(MAX_BLOCK, [(32768, 40), (32769, 40)], seed, plain=True)
+
+
+def check_window_edge(index, seed=WINDOW_EDGE_SEED):
+    """a word whose only earlier copy is 32768 back: one match, distance symbol 29 with extra value 8191.  32769 back: literals."""
+    a = make_aligner(index)
+    try:
+        data, (q_in, q_out) = window_edge_input(seed)
+        b, = compress_members(a, data)
+        at = token_map(b)
+        assert b.btype == 2 and at.get(q_in) == (40, 273, 32768, 29), ("the copy 32768 back was not matched", at.get(q_in))
+        assert du.DIST_BASE[29] + 8191 == 32768 and du.LEN_BASE[273 - 257] + 5 == 40
+        assert all(at.get(q_out + i) == data[q_out + i] for i in range(40)), "the copy 32769 back is not 40 literals"
+        assert max(t[2] for t in b.matches()) == 32768
+        return b
+    finally:
+        a.close()
+
+
+CUT_REST = (1, 2, 3, 4, 5, 257, 258, 259)
+CUT_BLOCK = 1024
+CUT_SEED = 1
+
+
+def cut_match_input(seed=CUT_SEED):
+    """members of CUT_BLOCK bytes: 300 random bytes, filler, and the first `rest` of the same bytes again in front of the member's end"""
+    out = b""
+    for k, rest in enumerate(CUT_REST):
+        w = rng_bytes(1000 * seed + k, 300).replace(bytes([FILL]), b"\x00")
+        out += w + bytes([FILL]) * (CUT_BLOCK - 300 - rest) + w[:rest]
+    return out
+
+
+def check_cut_match(index, seed=CUT_SEED):
+    """a match that the member's end cuts short, len - pos = 1 .. 5 and 257 .. 259 where it starts: below four bytes literals, then a match
+    of exactly what is left, and at 259 a match of 258 with one literal behind it"""
+    a = make_aligner(index)
+    try:
+        data = cut_match_input(seed)
+        blocks = compress_members(a, data, CUT_BLOCK)
+        assert len(blocks) == len(CUT_REST)
+        for k, (b, rest) in enumerate(zip(blocks, CUT_REST)):
+            q = CUT_BLOCK - rest; src = data[k * CUT_BLOCK:(k + 1) * CUT_BLOCK]
+            at = token_map(b)
+            assert b.btype == 2, rest
+            if rest < 4:
+                assert [at.get(q + i) for i in range(rest)] == list(src[q:]), (rest, "literals expected")
+            else:
+                t = at.get(q)
+                assert t is not None and not isinstance(t, int) and t[0] == min(rest, 258) and t[2] == q, (rest, t)
+                if rest == 259:
+                    assert at.get(q + 258) == src[-1] and b.tokens[-1] == src[-1]
+                else:
+                    assert b.tokens[-1] == t
+        return blocks
+    finally:
+        a.close()
+
+
+def short_inputs(k):
+    """the inputs of k bytes of check_short_members"""
+    rng = np.random.default_rng(7000 + k)
+    return {"run": b"a" * k, "alternating": (b"ab" * k)[:k], "two_values": bytes(rng.choice(np.array([0x30, 0x31], np.uint8), k, p=[0.8, 0.2]))}
+
+
+def check_short_members(index):
+    """one to two distinct bytes, 1 .. 130 of them: dynamic blocks of fewer than 64 tokens (lanes without a token in the emission), and of
+    exactly 64 and 65 (the step from one token a lane to two).  Returns {token count with end-of-block: number of dynamic blocks}."""
+    a = make_aligner(index)
+    try:
+        seen = {}
+        for k in range(1, 131):
+            for name, data in short_inputs(k).items():
+                b, = compress_members(a, data)
+                if b.btype == 2:
+                    seen[len(b.tokens) + 1] = seen.get(len(b.tokens) + 1, 0) + 1
+        assert any(n < 64 for n in seen) and 64 in seen and 65 in seen, ("token counts reached", sorted(seen))
+        assert min(seen) <= 16, sorted(seen)                                  # (most lanes without a token)
+        return seen
+    finally:
+        a.close()
+
+
+def check_crc_slices(index, pairs=tuple(range(2, 201, 2)), singles=(4095, 4096, 4097, 65279, 65280)):
+    """random bytes of every length 1 .. 200 (a call holds the members L and L - 1), around 4096 and at the largest member: the CRC's lane
+    slices of (len + 63) / 64 bytes leave lanes empty at most of them.  Stored blocks: it is the CRC, which check_output compares with
+    zlib's, that is under test."""
+    a = make_aligner(index)
+    try:
+        lengths = set()
+        for L in pairs:
+            blocks = compress_members(a, rng_bytes(300 + L, 2 * L - 1), L)
+            lengths |= {L, L - 1}
+            assert len(blocks) == 2
+        for L in singles:
+            b, = compress_members(a, rng_bytes(300 + L, L), L)
+            assert b.btype == 0
+            lengths.add(L)
+        return lengths
+    finally:
+        a.close()
+
+
+def literal_input(groups, count, seed):
+    """count bytes of every value of groups (a list of ranges), shuffled"""
+    x = np.repeat(np.array([v for g in groups for v in g], np.uint8), count)
+    np.random.default_rng(seed).shuffle(x)
+    return x.tobytes()
+
+
+# (what the case is for, the input); the run lengths are asserted from the parsed lengths
+def header_run_cases():
+    return {
+        # 31 values of equal counts and end-of-block: 32 codes of five bits; the values stand in groups of 4, 7, 8 and 10 with zeros between
+        "nonzero_4_7_8_10": literal_input([range(10, 14), range(20, 27), range(30, 38), range(40, 50), (60,), (70,)], 8, 1),
+        # zeros between the used values: 3, 10, 11, 138; and 139 from the last used value to end-of-block
+        "zero_3_10_11_138": literal_input([(0,), (4,), (15,), (27,), (166,)], 400, 2),
+        "zero_139": literal_input([(5,), (116,)], 600, 3),
+    }
+
+
+HEADER_RUNS_WANTED = {"nonzero_4_7_8_10": [("nonzero", 4), ("nonzero", 7), ("nonzero", 8), ("nonzero", 10)],
+                      "zero_3_10_11_138": [(0, 3), (0, 10), (0, 11), (0, 138)], "zero_139": [(0, 139)]}
+
+
+def spans_boundary(block):
+    """the header symbols (16, 17, 18) whose repeats cover lengths on both sides of the lit/len | distance boundary"""
+    at = 0; out = []
+    for s, n in block.header_seq:
+        if n and at - (1 if s == 16 else 0) < block.hlit < at + n:
+            out.append((s, n, at))
+        at += n or 1
+    return out
+
+
+def check_header_runs(index):
+    """the run-length coder of the block header at its edges: zero runs of exactly 3, 10 (one 17), 11, 138 (one 18) and 139 (an 18 and a plain
+    zero), non-zero runs of exactly 4 (length, 16 x 3), 7 (length, 16 x 6), 8 (one more plain length) and 10 (16 x 6, 16 x 3); a run that
+    goes on from the lit/len lengths into the distance lengths.  check_coded_member has compared each sequence with the greedy coder's."""
+    a = make_aligner(index)
+    try:
+        reached = {}
+        for name, data in header_run_cases().items():
+            b, = compress_members(a, data)
+            assert b.btype == 2, name
+            runs = du.header_runs(b.ll_lengths + b.d_lengths)
+            for v, n in HEADER_RUNS_WANTED[name]:
+                assert any(rn == n and (rv == 0 if v == 0 else rv != 0) for rv, rn in runs), (name, "run not reached", (v, n), runs)
+            reached[name] = runs
+        # the first member of a fixture array: lit/len lengths that end in 9, 9, 9 and a first distance length of 9, one 16 over the boundary
+        b, = compress_members(a, fixture_arrays()["single_ae_om1"][:MAX_BLOCK])
+        assert b.btype == 2 and spans_boundary(b), ("no run crosses from the lit/len lengths into the distance lengths", b.header_seq[-40:])
+        reached["crossing"] = spans_boundary(b)
+        return reached
+    finally:
+        a.close()
+
+
+def check_code_length_code_limited(index):
+    """the code-length code limited at 7 bits by the fold-and-repair loop of bgzf_build_code: over the header of a fixture array's first member
+    a plain Huffman code is 8 deep, and the code that was sent has a length of exactly 7 (and, by check_coded_member, is complete and ordered)"""
+    a = make_aligner(index)
+    try:
+        b, = compress_members(a, fixture_arrays()["single_om1_omax4"][:MAX_BLOCK])
+        counts = [0] * 19
+        for s, _ in b.header_seq:
+            counts[s] += 1
+        deep = max(du.huffman_lengths(counts).values())
+        assert deep > 7, ("the header's histogram no longer needs the limit: Huffman depth", deep, counts)
+        assert max(b.cl_lengths) == 7, b.cl_lengths
+        return deep, counts
+    finally:
+        a.close()
+
+
+# ---- the distance code limited at 15: 4180 matches of four bytes over the 17 distance symbols 12 .. 28 in Fibonacci proportions, one member
+DISTANCE_LIMIT_COUNTS = {12 + i: c for i, c in enumerate((1597, 987, 610, 377, 233, 144, 89, 55, 34, 21, 13, 8, 5, 3, 2, 1, 1))}
+DISTANCE_LIMIT_SEED = 0
+
+
+def distance_symbol(d):
+    return max(s for s in range(30) if du.DIST_BASE[s] <= d)
+
+
+def distance_limit_layout():
+    """the member as a sequence of word numbers (a word is four bytes).  A section S(K, m): K new words, then the same K words again and
+    again, adjacent words swapped in every other period, until m words have been repeated -- every repeat lies 4 K - 4 or 4 K + 4 bytes
+    behind its word's last place.  A group G(n, inner): n new words, the inner sequence, the n words with adjacent ones swapped -- every
+    repeat lies 4 (n + len(inner)) bytes, give or take four, behind.  Filler: new words that stand once.  The groups are nested so that
+    every distance falls into the range of its symbol; every distance is 68 or more, so a word's earlier place belongs to an earlier
+    64-byte step of the matcher."""
+    n_words = [0]
+
+    def new(k):
+        n_words[0] += k
+        return list(range(n_words[0] - k, n_words[0]))
+
+    def swapped(w):
+        out = list(w)
+        for i in range(0, len(out) - 1, 2):
+            out[i], out[i + 1] = out[i + 1], out[i]
+        return out
+
+    def S(K, m):
+        w = new(K); out = list(w); t = 1
+        while m:
+            part = (swapped(w) if t & 1 else w)[:m]
+            out += part; m -= len(part); t += 1
+        return out
+
+    def G(n, *inner):
+        w = new(n)
+        return w + [x for part in inner for x in part] + swapped(w)
+
+    c = DISTANCE_LIMIT_COUNTS
+    g25 = G(c[25], S(18, c[12]))
+    g24 = G(c[24], G(c[21], S(50, c[15])), G(c[20], S(66, c[16])), S(98, c[17]))
+    g26 = G(c[26], g25, G(c[18], new(50)), G(c[19], new(150)))
+    g27 = G(c[27], g26, g24)
+    return G(c[28], g27, G(c[23], S(26, c[13])), G(c[22], S(34, c[14])))
+
+
+def distance_limit_input(seed=DISTANCE_LIMIT_SEED):
+    """the bytes of distance_limit_layout() with random words, drawn again until, for every repeat of a word, (a) no four bytes between the
+    word's last place and this one fall into the same one of 4096 hash classes -- otherwise the matcher's table no longer points at the last
+    place, the word goes out as literals, the cursor leaves the word grid and 258-byte matches two periods back take over -- and (b) the
+    byte behind the word differs from the byte behind its last place, so that the match is four bytes long.  (a) uses the matcher's hash,
+    the top 12 bits of the little-endian word times 2654435761: should bgzf.h hash otherwise, check_distance_code_limited says that the
+    input no longer reaches its path.  Returns (bytes, {distance symbol: planned matches})."""
+    rng = np.random.default_rng(seed)
+    layout = np.array(distance_limit_layout())
+    n_words = int(layout.max()) + 1
+    last = {}; plan = []                                                       # (slot, the word's last slot)
+    for j, w in enumerate(layout.tolist()):
+        if w in last:
+            plan.append((j, last[w]))
+        last[w] = j
+    planned = {}
+    for j, q in plan:
+        s = distance_symbol(4 * (j - q)); planned[s] = planned.get(s, 0) + 1
+    assert planned == DISTANCE_LIMIT_COUNTS and min(j - q for j, q in plan) >= 17, planned
+    words = rng.integers(0, 256, (n_words, 4), dtype=np.uint8)
+    p = np.array([4 * j for j, _ in plan]); q = np.array([4 * k for _, k in plan])
+    for _ in range(5000):
+        x = words[layout].reshape(-1)
+        v = x[:-3].astype(np.uint64) | (x[1:-2].astype(np.uint64) << 8) | (x[2:-1].astype(np.uint64) << 16) | (x[3:].astype(np.uint64) << 24)
+        h = ((v * 2654435761) & 0xffffffff) >> 20
+        # the last place before every position where the position's hash class occurred
+        order = np.lexsort((np.arange(h.size), h))
+        prev = np.full(h.size, -1, np.int64)
+        same = h[order][1:] == h[order][:-1]
+        prev[order[1:][same]] = order[:-1][same]
+        nxt = np.append(x, 0)[np.minimum(p + 4, x.size)]
+        bad = (prev[p] != q) | ((p + 4 < x.size) & (nxt == np.append(x, 0)[q + 4]))
+        if not bad.any():
+            return x.tobytes(), planned
+        again = np.unique(layout[p[bad] // 4])
+        words[again] = rng.integers(0, 256, (again.size, 4), dtype=np.uint8)
+    raise AssertionError("no clean set of words")
+
+
+def check_distance_code_limited(index, seed=DISTANCE_LIMIT_SEED):
+    """the distance code limited at 15 bits by the fold-and-repair loop of bgzf_build_code: the parsed distance histogram is the planned one
+    (4180 matches, Fibonacci counts over 17 symbols), a plain Huffman code over it is 16 deep, and the code that was sent has a length of
+    exactly 15 (and, by check_coded_member, is complete and ordered)"""
+    a = make_aligner(index)
+    try:
+        data, planned = distance_limit_input(seed)
+        b, = compress_members(a, data)
+        counts = [0] * 30
+        for t in b.matches():
+            counts[t[3]] += 1
+        got = {s: c for s, c in enumerate(counts) if c}
+        deep = max(du.huffman_lengths(counts).values())
+        assert b.btype == 2 and deep > 15, ("the input no longer reaches the limit of the distance code: Huffman depth, histogram", deep, got)
+        assert max(b.d_lengths) == 15, b.d_lengths
+        assert got == planned, ("the matcher no longer finds the planned matches", got)
+        return deep, got
+    finally:
+        a.close()
+

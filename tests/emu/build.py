@@ -71,5 +71,20 @@ def build(verbose=False):
     return LIB
 
 
+def build_coder_harness():
+    """tests/emu/bgzf_coder_harness.cpp (a test kernel around bgzf.h's bgzf_build_code) with wave_emu.o into a shared object of its own:
+    neither libsnapgpu_emu.so nor the product holds it"""
+    os.makedirs(BDIR, exist_ok=True)
+    src, emu_src = os.path.join(HERE, "bgzf_coder_harness.cpp"), os.path.join(HERE, "wave_emu.cpp")
+    lib, obj, emu_obj = os.path.join(BDIR, "libbgzf_coder_harness.so"), os.path.join(BDIR, "bgzf_coder_harness.o"), os.path.join(BDIR, "wave_emu_coder.o")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [src, emu_src, os.path.join(HERE, "include", "hip", "hip_runtime.h"),
+                                                                                    os.path.abspath(__file__)]
+    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(d) for d in deps):
+        _run([CXX] + FLAGS + ["-I", CSRC, "-fsanitize=thread", "--param", "tsan-instrument-func-entry-exit=0", "-c", src, "-o", obj])
+        _run([CXX] + FLAGS + ["-c", emu_src, "-o", emu_obj])
+        _run([CXX, "-shared", "-fPIC", "-o", lib, obj, emu_obj, "-lpthread"])
+    return lib
+
+
 if __name__ == "__main__":
     print(build(verbose=True))
