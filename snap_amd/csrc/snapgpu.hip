@@ -2758,16 +2758,24 @@ extern "C" int snapgpu_set_contig_bam_ids(snapgpu_ctx *ctx, uint32_t n_contigs, 
     return SNAPGPU_OK;
 }
 
-// What the three text calls share once every array is in HBM: the length pass, the scan, the write pass (sam_text.h), all on the call's
-// stream, and the summary read back -- the stream is synchronised when this returns.  n_records > 0.
+// The records of a call, in host memory or in HBM alike: n records over the n_batch reads of the batch (rec_read NULL: record i is read i).
+// pairs: n pair units of two lines each over n_batch pairs; rec_read is then unit_pair, and rnext .. first_written are there.
 struct SamTextIO {
+    uint64_t n; uint32_t n_batch;
     const void *bases, *quals, *offsets, *names, *name_off, *rec_read;
     const void *flag, *contig, *pos, *mapq, *ops; uint32_t ops_stride; const void *n_ops, *nm;
-    uint64_t cap; void *text, *line_begin;
+    bool pairs; const void *rnext, *pnext, *tlen, *first_written;
+    uint64_t lines() const { return pairs ? 2 * n : n; }
+    uint32_t reads() const { return pairs ? 2 * n_batch : n_batch; }
 };
-// (bam: the same calls over the BAM-record kernels, sam_bam.h -- `text` is then the record bytes, line_begin block_begin, and the contigs'
-// BAM numbers are needed in place of their names)
-static int sam_text_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_records, uint32_t ops_stride, bool bam = false)
+// Where their bytes go.  SAM lines (sam_text.h) or BAM records (sam_bam.h, which needs the contigs' BAM numbers in place of their names): up to
+// cap bytes at `bytes`, the offset of every line or record in `begin`.  SAM_OUT_BGZF (the fused calls): the BAM records stay in a buffer of the
+// library's own and their blocks go to z.  *total: the bytes of all the lines or records, written or not.
+enum SamOutKind { SAM_OUT_TEXT, SAM_OUT_BAM, SAM_OUT_BGZF };
+struct BgzfOut { uint32_t block_input; uint64_t cap; uint8_t *bgzf; uint64_t *member_begin; uint64_t member_capacity; uint64_t *n_members, *bgzf_bytes; };
+struct SamOut { SamOutKind kind; uint64_t cap; void *bytes, *begin; uint64_t *total; BgzfOut z; };
+
+static int sam_text_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_records, uint32_t ops_stride, bool bam)
 {
     if (bam && !ctx->d_contig_bam_id) return fail(ctx, SNAPGPU_E_INVALID, w + ": no contig BAM numbers (call snapgpu_set_contig_bam_ids first)");
     if (!bam && !ctx->d_contig_names) return fail(ctx, SNAPGPU_E_INVALID, w + ": no contig names (call snapgpu_set_contig_names first)");
@@ -2775,11 +2783,13 @@ static int sam_text_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_rec
     if (n_records > 0xFFFFFFFFull - SAMREC_CHUNK) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^32 - 1 records in one call");
     return SNAPGPU_OK;
 }
-// the arrays only pair lines have (snapgpu_sam_text_paired*): with them n_records counts LINES, two per pair unit, and io.rec_read is unit_pair
-struct SamTextPairIO { const void *rnext, *pnext, *tlen, *first_written; };
-static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, const SamTextIO &io, SamTextSummary *sum, const SamTextPairIO *pair = nullptr,
-                         bool bam = false)
+// What every text and BAM call shares once the arrays of io are in HBM: the length pass, the scan, the write pass, all on the call's stream, and
+// the summary read back -- the stream is synchronised when this returns.  io.n > 0.
+static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, const SamTextIO &io, bool bam, uint64_t cap, void *d_bytes, void *d_begin,
+                         SamTextSummary *sum)
 {
+    const uint64_t n_records = io.lines();
+    const bool pair = io.pairs;
     SamBamArgs a; memset(&a, 0, sizeof(a));
     a.ref_id = ctx->d_contig_bam_id;
     a.n = (uint32_t)n_records; a.n_chunks = (uint32_t)((n_records + SAMREC_CHUNK - 1) / SAMREC_CHUNK); a.ops_stride = io.ops_stride; a.n_contigs = ctx->ix.n_contigs;
@@ -2788,11 +2798,11 @@ static int sam_text_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint
     a.flag = (const int32_t *)io.flag; a.contig = (const int32_t *)io.contig; a.pos = (const int64_t *)io.pos; a.mapq = (const int32_t *)io.mapq;
     a.ops = (const uint32_t *)io.ops; a.n_ops = (const int32_t *)io.n_ops; a.nm = (const int32_t *)io.nm;
     a.contig_names = ctx->d_contig_names; a.contig_name_off = ctx->d_contig_name_off;
-    a.cap = io.cap; a.text = (uint8_t *)io.text; a.line_begin = (uint64_t *)io.line_begin;
+    a.cap = cap; a.text = (uint8_t *)d_bytes; a.line_begin = (uint64_t *)d_begin;
     a.len = st.scratch((size_t)a.n * 4 + 4); a.partial = st.scratch((size_t)a.n_chunks * 8); a.summary = st.scratch(sizeof(SamTextSummary));
     if (pair) {
-        a.rnext = (const int32_t *)pair->rnext; a.pnext = (const int64_t *)pair->pnext; a.tlen = (const int64_t *)pair->tlen;
-        a.first_written = (const int32_t *)pair->first_written; a.qs = st.scratch((size_t)a.n * 4);
+        a.rnext = (const int32_t *)io.rnext; a.pnext = (const int64_t *)io.pnext; a.tlen = (const int64_t *)io.tlen;
+        a.first_written = (const int32_t *)io.first_written; a.qs = st.scratch((size_t)a.n * 4);
     }
     if (st.rc) return st.rc;
     uint32_t scan_blocks = (uint32_t)ctx->num_cus * 8, write_blocks = scan_blocks;
@@ -2828,100 +2838,135 @@ static int sam_text_empty(snapgpu_ctx *ctx, bool host, void *line_begin, uint64_
     return SNAPGPU_OK;
 }
 
-static int sam_text_single_device_call(snapgpu_ctx *ctx, const char *who, bool bam, uint64_t n_records, const void *d_bases, const void *d_quals, const void *d_offsets,
-                                              const void *d_names, const void *d_name_off, const void *d_rec_read, const void *d_flag, const void *d_contig,
-                                              const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
-                                              uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
+// snapgpu_sam_text_* and snapgpu_bam_records_*, single and paired.  host: every pointer of io and out but out.total is a host array; they are
+// checked, staged in one upload, and only the lines that were written and `begin` come down.  Otherwise everything is in HBM and stays there
+// (the two lines of a pair unit: SAMFormat::writePairs' snprintf, SAM.cpp:1854-1875; QNAME: ReadWriter.cpp:405-420; QS: SAM.cpp:1826-1834).
+static int sam_out_call(snapgpu_ctx *ctx, const char *who, SamTextIO io, const SamOut &out, bool host, void *stream)
 {
     const std::string w(who);
-    if (!ctx || !text_bytes || !d_line_begin || (text_capacity && !d_text) ||
-        (n_records && (!d_bases || !d_quals || !d_offsets || !d_names || !d_name_off || !d_flag || !d_contig || !d_pos || !d_mapq || !d_ops || !d_n_ops || !d_nm)))
+    if (!ctx || !out.total || !out.begin || (out.cap && !out.bytes) ||
+        (io.n && (!io.bases || !io.quals || !io.offsets || !io.names || !io.name_off || !io.flag || !io.contig || !io.pos || !io.mapq || !io.ops || !io.n_ops || !io.nm ||
+                  (io.pairs && (!io.rnext || !io.pnext || !io.tlen || !io.first_written)))))
         return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    int rc = sam_text_check(ctx, w, n_records, ops_stride, bam);
+    if (io.pairs && io.n > 0x7fffffffull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^31 - 1 pair units in one call");
+    if (io.pairs && host && io.n_batch > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, w + ": too many pairs");
+    int rc = sam_text_check(ctx, w, io.lines(), io.ops_stride, out.kind != SAM_OUT_TEXT);
     if (rc) return rc;
-    if (n_records == 0) return sam_text_empty(ctx, false, d_line_begin, text_bytes, stream);
+    if (io.n == 0) return sam_text_empty(ctx, host, out.begin, out.total, stream);
+    if (host) {
+        const uint64_t *offsets = (const uint64_t *)io.offsets, *name_off = (const uint64_t *)io.name_off;
+        const uint32_t *map = (const uint32_t *)io.rec_read;
+        if (!map && io.n != io.n_batch)
+            return fail(ctx, SNAPGPU_E_INVALID, w + (io.pairs ? ": without unit_pair there is one unit per pair (n_units == n_pairs)"
+                                                              : ": without rec_read there is one record per read (n_records == n_reads)"));
+        for (uint32_t i = 0; i < io.reads(); i++)
+            if (offsets[i + 1] < offsets[i] || name_off[i + 1] < name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": offsets and name_off must be non-decreasing");
+        for (uint64_t r = 0; map && r < io.n; r++)
+            if (map[r] >= io.n_batch)
+                return fail(ctx, SNAPGPU_E_INVALID, w + (io.pairs ? ": unit_pair names a pair the batch does not have" : ": rec_read names a read the batch does not have"));
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
     Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
-    const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
-                       text_capacity, d_text, d_line_begin};
+    void *d_bytes = out.bytes, *d_begin = out.begin;
+    if (host) {
+        const size_t n_reads = io.reads(), nb = (size_t)((const uint64_t *)io.offsets)[n_reads], nn = (size_t)((const uint64_t *)io.name_off)[n_reads];
+        const size_t r4 = (size_t)io.lines() * 4, r8 = (size_t)io.lines() * 8;
+        io.bases = st.in(io.bases, nb); io.quals = st.in(io.quals, nb); io.offsets = st.in(io.offsets, (n_reads + 1) * 8);
+        io.names = st.in(io.names, nn); io.name_off = st.in(io.name_off, (n_reads + 1) * 8);
+        io.rec_read = io.rec_read ? (const void *)st.in(io.rec_read, (size_t)io.n * 4) : nullptr;
+        io.flag = st.in(io.flag, r4); io.contig = st.in(io.contig, r4); io.pos = st.in(io.pos, r8); io.mapq = st.in(io.mapq, r4);
+        io.ops = st.in(io.ops, r4 * io.ops_stride); io.n_ops = st.in(io.n_ops, r4); io.nm = st.in(io.nm, r4);
+        if (io.pairs) { io.rnext = st.in(io.rnext, r4); io.pnext = st.in(io.pnext, r8); io.tlen = st.in(io.tlen, r8); io.first_written = st.in(io.first_written, (size_t)io.n * 4); }
+        d_bytes = st.out(out.bytes, (size_t)out.cap); d_begin = st.out(out.begin, r8 + 8);
+        if (st.rc) return st.rc;
+    }
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, n_records, io, &sum, nullptr, bam))) return rc;
-    *text_bytes = sum.total;
-    return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+    if ((rc = sam_text_core(ctx, w, st, io, out.kind != SAM_OUT_TEXT, out.cap, d_bytes, d_begin, &sum))) return rc;
+    if (host) {
+        st.limit(d_bytes, (size_t)sum.written);                              // only the lines that were written come down
+        if ((rc = st.download())) return rc;
+    }
+    *out.total = sum.total;
+    return sum.total > out.cap ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
-static int sam_text_single_call(snapgpu_ctx *ctx, const char *who, bool bam, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
-                                       const char *names, const uint64_t *name_off, const uint32_t *rec_read, const int32_t *flag, const int32_t *contig,
-                                       const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
-                                       uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+// ---- bytes -> BGZF blocks (bgzf.h): what bgzf_append of the tool (host/snapgpu_sam.cpp) does with zlib, and on the reference's side the BGZF writer
+// of SNAPLib/Bam.cpp behind DataWriter's gzip filter.  Everything in HBM; the stream is synchronised when bgzf_core returns.
+static uint64_t bgzf_members(uint64_t n_bytes, uint32_t block_input) { return n_bytes ? (n_bytes + block_input - 1) / block_input : 1; }
+static int bgzf_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_bytes, uint32_t block_input)
 {
-    const std::string w(who);
-    if (!ctx || !text_bytes || !line_begin || (text_capacity && !text) ||
-        (n_records && (!bases || !quals || !offsets || !names || !name_off || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm)))
-        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    int rc = sam_text_check(ctx, w, n_records, ops_stride, bam);
+    if (block_input == 0 || block_input > BGZF_MAX_BLOCK_INPUT) return fail(ctx, SNAPGPU_E_INVALID, w + ": block_input must be between 1 and 0xff00");
+    if (bgzf_members(n_bytes, block_input) > 0xFFFFFFFFull - SAMREC_CHUNK) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^32 - 1 blocks in one call");
+    return SNAPGPU_OK;
+}
+static int bgzf_core(snapgpu_ctx *ctx, Stage &st, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t cap, void *d_out, void *d_member_begin,
+                     SamTextSummary *sum)
+{
+    BgzfArgs a; memset(&a, 0, sizeof(a));
+    a.n_bytes = n_bytes; a.block_input = block_input; a.n_members = (uint32_t)bgzf_members(n_bytes, block_input);
+    a.in = (const uint8_t *)d_in; a.cap = cap; a.out = (uint8_t *)d_out; a.member_begin = (uint64_t *)d_member_begin;
+    // a wavefront of the deflate launch holds BGZF_LDS_WORDS dwords of LDS: eight to a CU
+    uint32_t deflate_blocks = (uint32_t)ctx->num_cus * 4, scan_blocks = (uint32_t)ctx->num_cus * 8, place_blocks = scan_blocks;
+    if (deflate_blocks > a.n_members) deflate_blocks = a.n_members;
+    { const uint32_t need = (a.n_members + SAMREC_CHUNK - 1) / SAMREC_CHUNK; if (scan_blocks > (need + 3) / 4) scan_blocks = (need + 3) / 4; }
+    { const uint32_t need = (a.n_members + 3) / 4; if (place_blocks > need) place_blocks = need; }
+    a.tok_stride = (uint64_t)block_input + 1; a.slot_stride = ((uint64_t)block_input + 31 + 3) & ~(uint64_t)3;
+    a.tok = st.scratch((size_t)deflate_blocks * a.tok_stride * 4); a.slots = st.scratch((size_t)a.n_members * a.slot_stride);
+    a.size = st.scratch((size_t)a.n_members * 4 + 4); a.partial = st.scratch((size_t)((a.n_members + SAMREC_CHUNK - 1) / SAMREC_CHUNK) * 8);
+    a.summary = st.scratch(sizeof(SamTextSummary));
+    if (st.rc) return st.rc;
+    HIPCHK(ctx, hipMemsetAsync(a.summary, 0, sizeof(SamTextSummary), st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemsetAsync(a.slots, 0, (size_t)a.n_members * a.slot_stride, st.s), SNAPGPU_E_LAUNCH);      // (the bits of a member are ORed into its slot)
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
+    snapgpu_launch_bgzf(&a, deflate_blocks, scan_blocks, place_blocks, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemcpyAsync(sum, a.summary, sizeof(SamTextSummary), hipMemcpyDeviceToHost, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    return finish_timing(ctx);
+}
+extern "C" int snapgpu_bgzf_compress_device(snapgpu_ctx *ctx, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t out_capacity, void *d_out,
+                                            void *d_member_begin, uint64_t *n_members, uint64_t *out_bytes, void *stream)
+{
+    const std::string w("snapgpu_bgzf_compress_device");
+    if (!ctx || !n_members || !out_bytes || !d_member_begin || (out_capacity && !d_out) || (n_bytes && !d_in)) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    int rc = bgzf_check(ctx, w, n_bytes, block_input);
     if (rc) return rc;
-    if (n_records == 0) return sam_text_empty(ctx, true, line_begin, text_bytes, nullptr);
-    if (!rec_read && n_records != n_reads) return fail(ctx, SNAPGPU_E_INVALID, w + ": without rec_read there is one record per read (n_records == n_reads)");
-    for (uint32_t i = 0; i < n_reads; i++)
-        if (offsets[i + 1] < offsets[i] || name_off[i + 1] < name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": offsets and name_off must be non-decreasing");
-    for (uint64_t r = 0; rec_read && r < n_records; r++)
-        if (rec_read[r] >= n_reads) return fail(ctx, SNAPGPU_E_INVALID, w + ": rec_read names a read the batch does not have");
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    if ((rc = bgzf_core(ctx, st, n_bytes, d_in, block_input, out_capacity, d_out, d_member_begin, &sum))) return rc;
+    *n_members = bgzf_members(n_bytes, block_input); *out_bytes = sum.total;
+    return sum.total > out_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+}
+extern "C" int snapgpu_bgzf_compress(snapgpu_ctx *ctx, uint64_t n_bytes, const uint8_t *in, uint32_t block_input, uint64_t out_capacity, uint8_t *out,
+                                     uint64_t *member_begin, uint64_t *n_members, uint64_t *out_bytes)
+{
+    const std::string w("snapgpu_bgzf_compress");
+    if (!ctx || !n_members || !out_bytes || !member_begin || (out_capacity && !out) || (n_bytes && !in)) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    int rc = bgzf_check(ctx, w, n_bytes, block_input);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
     Stage st(ctx, ctx->stream);
-    const size_t nb = (size_t)offsets[n_reads], r4 = (size_t)n_records * 4;
-    SamTextIO io;
-    io.bases = st.in(bases, nb); io.quals = st.in(quals, nb); io.offsets = st.in(offsets, ((size_t)n_reads + 1) * 8);
-    io.names = st.in(names, (size_t)name_off[n_reads]); io.name_off = st.in(name_off, ((size_t)n_reads + 1) * 8);
-    io.rec_read = rec_read ? (const void *)st.in(rec_read, r4) : nullptr;
-    io.flag = st.in(flag, r4); io.contig = st.in(contig, r4); io.pos = st.in(pos, (size_t)n_records * 8); io.mapq = st.in(mapq, r4);
-    io.ops = st.in(ops, r4 * ops_stride); io.ops_stride = ops_stride; io.n_ops = st.in(n_ops, r4); io.nm = st.in(nm, r4);
-    io.cap = text_capacity; io.text = st.out(text, (size_t)text_capacity); io.line_begin = st.out(line_begin, ((size_t)n_records + 1) * 8);
+    const uint64_t nm = bgzf_members(n_bytes, block_input);
+    const void *d_in = st.in(in, (size_t)n_bytes, 16);
+    void *d_out = st.out(out, (size_t)out_capacity), *d_member_begin = st.out(member_begin, ((size_t)nm + 1) * 8);
     if (st.rc) return st.rc;
     SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, n_records, io, &sum, nullptr, bam))) return rc;
-    st.limit(io.text, (size_t)sum.written);                              // only the lines that were written come down
+    if ((rc = bgzf_core(ctx, st, n_bytes, d_in, block_input, out_capacity, d_out, d_member_begin, &sum))) return rc;
+    st.limit(d_out, (size_t)sum.written);                                // only the members that were written come down
     if ((rc = st.download())) return rc;
-    *text_bytes = sum.total;
-    return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+    *n_members = nm; *out_bytes = sum.total;
+    return sum.total > out_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
-// ---- the BGZF end of the fused BAM calls (snapgpu_align_sam_single_bgzf / _paired_bgzf): the record bytes and block_begin stay in buffers of the
-// library's own and the blocks come down in their place
-struct BgzfOut { uint32_t block_input; uint64_t cap; uint8_t *bgzf; uint64_t *member_begin; uint64_t member_capacity; uint64_t *n_members, *bgzf_bytes; };
-static uint64_t bgzf_members(uint64_t n_bytes, uint32_t block_input);
-static int bgzf_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_bytes, uint32_t block_input);
-static int bgzf_core(snapgpu_ctx *ctx, Stage &st, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t cap, void *d_out, void *d_member_begin,
-                     SamTextSummary *sum);
+// ---- the sink of the fused calls (snapgpu_align_sam_single_text / _bam / _bgzf and their paired forms): the records of the batch are in HBM,
+// and their bytes go where a SamOut says
 static int bgzf_out_check(snapgpu_ctx *ctx, const std::string &w, const BgzfOut &z)
 {
     if (!z.member_begin || !z.n_members || !z.bgzf_bytes || (z.cap && !z.bgzf)) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
     if (const int rc = bgzf_check(ctx, w, 0, z.block_input)) return rc;
     *z.n_members = 0; *z.bgzf_bytes = 0; *z.member_begin = 0;
-    return SNAPGPU_OK;
-}
-// The BAM records of a call into a buffer of the library's (io.cap / io.text / io.line_begin are set here).  Its size is an estimate from the longest
-// name, the longest read (RL) and eight cigar operations a record; records that need more are written by a second pass into a buffer of the exact size.
-static int bam_bytes_in_hbm(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, uint32_t n_reads, const uint64_t *name_off, uint32_t RL,
-                            SamTextIO io, const SamTextPairIO *pair, SamTextSummary *sum, void **d_bytes)
-{
-    uint64_t longest = 0;
-    for (uint32_t i = 0; i < n_reads; i++) if (name_off[i + 1] - name_off[i] > longest) longest = name_off[i + 1] - name_off[i];
-    if (longest > 254) longest = 254;                                    // (a longer QNAME fails the call)
-    const uint32_t ops = io.ops_stride < 8 ? io.ops_stride : 8;
-    io.cap = n_records * (36 + longest + 1 + 4ull * ops + (RL + 1) / 2 + RL + 58);      // (sam_bam.h: 36 fixed bytes, 50 + 1 + 7 of aux)
-    io.line_begin = st.scratch((size_t)(n_records + 1) * 8);
-    for (int pass = 0;; pass++) {
-        io.text = st.scratch((size_t)io.cap);
-        if (st.rc) return st.rc;
-        memset(sum, 0, sizeof(*sum));
-        if (const int rc = sam_text_core(ctx, w, st, n_records, io, sum, pair, true)) return rc;
-        if (sum->flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
-        if (sum->total <= io.cap) break;
-        if (pass) return fail(ctx, SNAPGPU_E_LAUNCH, w + ": the BAM records changed size between two passes");
-        io.cap = sum->total;
-    }
-    *d_bytes = io.text;
     return SNAPGPU_OK;
 }
 // bam_total bytes at d_bytes -> the blocks, registered for the call's one download.  *truncated: SNAPGPU_W_TEXT_TRUNCATED is due.
@@ -2940,23 +2985,68 @@ static int bgzf_tail(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t
     return SNAPGPU_OK;
 }
 
-static int align_sam_single_text_call(snapgpu_ctx *ctx, const char *who, bool bam, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
-                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
-                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
-                                             uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
-                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes, const BgzfOut *z = nullptr)
+// The lines or records of io, every array of it in HBM, into the sink, registered with st for the call's one download.  d_bytes / d_begin: out.bytes
+// and out.begin as the call staged them.  SAM_OUT_BGZF has neither: the BAM records go into a buffer of the library's, sized by an estimate from
+// the longest name (name_off: the host's copy), the longest read (RL) and eight cigar operations a record -- records that need more are written by
+// a second pass into a buffer of the exact size -- and bgzf_tail follows.  *total: the bytes of text or of BAM records.
+static int sam_out_in_hbm(snapgpu_ctx *ctx, const std::string &w, Stage &st, const SamTextIO &io, const uint64_t *name_off, uint32_t RL, const SamOut &out,
+                          void *d_bytes, void *d_begin, uint64_t *total, bool *truncated)
+{
+    const bool keep = out.kind == SAM_OUT_BGZF;
+    uint64_t cap = out.cap;
+    if (keep && io.n) {
+        uint64_t longest = 0;
+        for (uint32_t i = 0; i < io.reads(); i++) if (name_off[i + 1] - name_off[i] > longest) longest = name_off[i + 1] - name_off[i];
+        if (longest > 254) longest = 254;                                    // (a longer QNAME fails the call)
+        const uint32_t ops = io.ops_stride < 8 ? io.ops_stride : 8;
+        cap = io.lines() * (36 + longest + 1 + 4ull * ops + (RL + 1) / 2 + RL + 58);      // (sam_bam.h: 36 fixed bytes, 50 + 1 + 7 of aux)
+        d_begin = st.scratch((size_t)(io.lines() + 1) * 8);
+    }
+    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
+    for (int pass = 0; io.n; pass++) {
+        if (keep) d_bytes = st.scratch((size_t)cap);
+        if (st.rc) return st.rc;
+        memset(&sum, 0, sizeof(sum));
+        if (const int rc = sam_text_core(ctx, w, st, io, out.kind != SAM_OUT_TEXT, cap, d_bytes, d_begin, &sum)) return rc;
+        if (sum.flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
+        if (!keep || sum.total <= cap) break;
+        if (pass) return fail(ctx, SNAPGPU_E_LAUNCH, w + ": the BAM records changed size between two passes");
+        cap = sum.total;
+    }
+    *total = sum.total;
+    if (keep) return bgzf_tail(ctx, w, st, sum.total, d_bytes, out.z, truncated);
+    if (!io.n) HIPCHK(ctx, hipMemsetAsync(d_begin, 0, 8, st.s), SNAPGPU_E_LAUNCH);
+    st.limit(d_begin, (size_t)(io.lines() + 1) * 8); st.limit(d_bytes, (size_t)sum.written);      // only the lines that were written come down
+    *truncated = sum.total > out.cap;
+    return SNAPGPU_OK;
+}
+// the null check of both fused bodies: the sink's pointers, and the call's other required ones (rest: all of them are there)
+static int sam_out_begin(snapgpu_ctx *ctx, const std::string &w, const SamOut &out, bool rest)
+{
+    if (!rest || !out.total || (out.kind != SAM_OUT_BGZF && (!out.begin || (out.cap && !out.bytes)))) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    return SNAPGPU_OK;
+}
+
+// Single-end reads to the bytes of all their SAM records in one call: snapgpu_align_sam_single_records_device over one upload of the batch and its
+// names, with the record arrays in buffers of the library's own, then the sink; rec_begin, the flags of the formatted records and what the sink
+// registered come down in one download
+static int align_sam_single_out_call(snapgpu_ctx *ctx, const char *who, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                     const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                     const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                     uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag, const SamOut &out)
 {
     const std::string w(who);
-    uint64_t no_line_begin = 0;
-    if (z) { if (const int rc = bgzf_out_check(ctx, w, *z)) return rc; line_begin = &no_line_begin; }
-    if (!ctx || !n_records || !rec_begin || !line_begin || !text_bytes || (text_capacity && !text) || (record_capacity && !flag) ||
-        (n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off)))
-        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    int rc = sam_text_check(ctx, w, record_capacity, ops_stride, bam);
-    if (rc) return rc;
+    const bool z = out.kind == SAM_OUT_BGZF;
+    int rc;
+    if (!ctx) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    if (z && (rc = bgzf_out_check(ctx, w, out.z))) return rc;
+    if ((rc = sam_out_begin(ctx, w, out, n_records && rec_begin && !(record_capacity && !flag) &&
+                                         !(n && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off))))) return rc;
+    if ((rc = sam_text_check(ctx, w, record_capacity, ops_stride, out.kind != SAM_OUT_TEXT))) return rc;
     if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, w + ": ops_stride must be at least 3");
     if (ctx->paired) return fail(ctx, SNAPGPU_E_INVALID, w + ": a single-end context is needed (no snapgpu_enable_paired)");
-    *n_records = 0; *rec_begin = 0; *line_begin = 0; *text_bytes = 0;
+    *n_records = 0; *rec_begin = 0; *out.total = 0;
+    if (!z) *(uint64_t *)out.begin = 0;
     if (n == 0) return SNAPGPU_OK;
     uint32_t RL = 64;
     if ((rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
@@ -2969,45 +3059,31 @@ static int align_sam_single_text_call(snapgpu_ctx *ctx, const char *who, bool ba
     // ---- one upload: the batch and its names; the record arrays are the library's own
     Stage st(ctx, ctx->stream);
     const size_t n4 = (size_t)n * 4, c4 = (size_t)record_capacity * 4;
-    const void *d_bases = bases, *d_quals = quals, *d_offsets = offsets;
-    stage_reads(st, d_bases, d_quals, d_offsets, n);
+    SamTextIO io{}; io.n_batch = n; io.ops_stride = ops_stride;
+    io.bases = bases; io.quals = quals; io.offsets = offsets;
+    stage_reads(st, io.bases, io.quals, io.offsets, n);
     const void *d_fc = st.in(front_clip, n4), *d_dl = st.in(data_len, n4), *d_skip = st.in(skip, n);
-    const void *d_names = st.in(names, (size_t)name_off[n]), *d_name_off = st.in(name_off, ((size_t)n + 1) * 8);
+    io.names = st.in(names, (size_t)name_off[n]); io.name_off = st.in(name_off, ((size_t)n + 1) * 8);
     void *d_rec_begin = st.out(rec_begin, ((size_t)n + 1) * 8), *d_rec_read = st.scratch(c4), *d_rec_kind = st.scratch((size_t)record_capacity);
     void *d_flag = st.out(flag, c4), *d_contig = st.scratch(c4), *d_pos = st.scratch((size_t)record_capacity * 8), *d_mapq = st.scratch(c4);
     void *d_ops = st.scratch(c4 * ops_stride), *d_n_ops = st.scratch(c4), *d_nm = st.scratch(c4), *d_stale = st.scratch(c4);
-    void *d_text = z ? nullptr : (void *)st.out(text, (size_t)text_capacity), *d_line_begin = z ? nullptr : (void *)st.out(line_begin, ((size_t)record_capacity + 1) * 8);
+    void *d_bytes = z ? nullptr : (void *)st.out(out.bytes, (size_t)out.cap), *d_begin = z ? nullptr : (void *)st.out(out.begin, ((size_t)record_capacity + 1) * 8);
     if (st.rc) return st.rc;
+    io.rec_read = d_rec_read; io.flag = d_flag; io.contig = d_contig; io.pos = d_pos; io.mapq = d_mapq; io.ops = d_ops; io.n_ops = d_n_ops; io.nm = d_nm;
     // ---- the records, where snapgpu_align_sam_single_records_device leaves them (RL: the longest unclipped read, as check_sam_reads found it)
-    uint64_t total = 0;
-    rc = sam_records_call(ctx, who, false, n, RL, d_bases, d_quals, d_offsets, d_fc, d_dl, d_skip, use_m, adjust_primary, nullptr, nullptr, nullptr, 0, nullptr,
+    uint64_t total = 0, bytes = 0;
+    rc = sam_records_call(ctx, who, false, n, RL, io.bases, io.quals, io.offsets, d_fc, d_dl, d_skip, use_m, adjust_primary, nullptr, nullptr, nullptr, 0, nullptr,
                           record_capacity, &total, d_rec_begin, d_rec_read, d_rec_kind, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_stale, st.s);
     if (rc != SNAPGPU_OK && rc != SNAPGPU_W_RECORDS_TRUNCATED) return rc;
     const bool rec_truncated = rc == SNAPGPU_W_RECORDS_TRUNCATED;
-    const uint64_t f = total < record_capacity ? total : record_capacity;                            // the records that were formatted
-    // ---- their lines
-    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if (z) {                                                             // ---- their BAM records, left in HBM, and the blocks of those
-        void *d_bytes = nullptr; bool z_truncated = false;
-        const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, 0, nullptr, nullptr};
-        if (f && (rc = bam_bytes_in_hbm(ctx, w, st, f, n, name_off, RL, io, nullptr, &sum, &d_bytes))) return rc;
-        if ((rc = bgzf_tail(ctx, w, st, sum.total, d_bytes, *z, &z_truncated))) return rc;
-        st.limit(d_flag, (size_t)f * 4);
-        if ((rc = st.download())) return rc;
-        *n_records = total; *text_bytes = sum.total;
-        return rec_truncated ? SNAPGPU_W_RECORDS_TRUNCATED : (z_truncated ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK);
-    }
-    if (f) {
-        const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
-                           text_capacity, d_text, d_line_begin};
-        if ((rc = sam_text_core(ctx, w, st, f, io, &sum, nullptr, bam))) return rc;
-        if (sum.flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
-    } else HIPCHK(ctx, hipMemsetAsync(d_line_begin, 0, 8, st.s), SNAPGPU_E_LAUNCH);
-    // ---- one download: rec_begin, the flags and line offsets of the formatted records, the lines that were written
-    st.limit(d_flag, (size_t)f * 4); st.limit(d_line_begin, ((size_t)f + 1) * 8); st.limit(d_text, (size_t)sum.written);
+    io.n = total < record_capacity ? total : record_capacity;                                        // the records that were formatted
+    // ---- their lines, BAM records or blocks; the records' warning goes before the sink's
+    bool out_truncated = false;
+    if ((rc = sam_out_in_hbm(ctx, w, st, io, name_off, RL, out, d_bytes, d_begin, &bytes, &out_truncated))) return rc;
+    st.limit(d_flag, (size_t)io.n * 4);
     if ((rc = st.download())) return rc;
-    *n_records = total; *text_bytes = sum.total;
-    return rec_truncated ? SNAPGPU_W_RECORDS_TRUNCATED : (sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK);
+    *n_records = total; *out.total = bytes;
+    return rec_truncated ? SNAPGPU_W_RECORDS_TRUNCATED : (out_truncated ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK);
 }
 
 // paired-end writer: results -> the computed fields of both SAM records of each pair (sam_fields.h, cigar_k.hip); host / max_read_len / stream as
@@ -3082,30 +3158,36 @@ extern "C" int snapgpu_sam_fields_paired_device(snapgpu_ctx *ctx, uint32_t n_pai
 // launches, the SAM fields of both mates of every pair from the results where the align kernels left them, one download.  What
 // snapgpu_align_paired on a clipped copy of the reads, a host scatter and snapgpu_sam_fields_paired do with two uploads of the reads and a
 // round trip of the results.
-// (`text`, snapgpu_align_sam_paired_text: the fields but flag and first_written stay in HBM -- a NULL output is a device-only buffer -- and the
-// lines of the batch's pairs follow them, with the names uploaded beside the batch and the lines that were written in the one download)
-struct PairedTextOut { const char *names; const uint64_t *name_off; uint64_t cap; char *text; uint64_t *line_begin; uint64_t *text_bytes; bool bam; const BgzfOut *z = nullptr; };
+// (`out`, snapgpu_align_sam_paired_text / _bam / _bgzf: the fields but flag and first_written stay in HBM -- a NULL output is a device-only
+// buffer -- and the sink follows them, with the names uploaded beside the batch and what the sink registered in the one download; the caller of
+// the form without a sink has checked its pointers)
 static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
                                  const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
                                  snapgpu_paired_result *results, snapgpu_paired_result *first_alt,
                                  int32_t *flag, int32_t *contig, int64_t *pos, int32_t *mapq, uint32_t *ops, uint32_t ops_stride,
                                  int32_t *n_ops, int32_t *nm, int32_t *rnext, int64_t *pnext, int64_t *tlen, int32_t *first_written,
-                                 int32_t *reference_history_dependent, const PairedTextOut *text)
+                                 int32_t *reference_history_dependent, const char *names, const uint64_t *name_off, const SamOut *out)
 {
     const std::string w(who);
+    const bool z = out && out->kind == SAM_OUT_BGZF;
+    int rc;
+    if (out && (rc = sam_out_begin(ctx, w, *out, ctx && !(n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off ||
+                                                                       !flag || !first_written))))) return rc;
+    if (z && (rc = bgzf_out_check(ctx, w, out->z))) return rc;
     if (ops_stride < 3) return fail(ctx, SNAPGPU_E_INVALID, w + ": ops_stride must be at least 3");
     if (!ctx->paired || ctx->secondary)
         return fail(ctx, SNAPGPU_E_INVALID, w + ": a paired-end context without secondary results is needed (snapgpu_enable_paired, no snapgpu_enable_secondary)");
-    if (text) {
-        if (const int rc = sam_text_check(ctx, w, 2 * (uint64_t)n_pairs, ops_stride, text->bam)) return rc;
-        *text->line_begin = 0; *text->text_bytes = 0;
+    if (out) {
+        if ((rc = sam_text_check(ctx, w, 2 * (uint64_t)n_pairs, ops_stride, out->kind != SAM_OUT_TEXT))) return rc;
+        *out->total = 0;
+        if (!z) *(uint64_t *)out->begin = 0;
     }
     if (n_pairs == 0) return SNAPGPU_OK;
     if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, w + ": too many pairs");
     const uint32_t n = 2 * n_pairs;
-    for (uint32_t i = 0; text && i < n; i++) if (text->name_off[i + 1] < text->name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": name_off must be non-decreasing");
+    for (uint32_t i = 0; out && i < n; i++) if (name_off[i + 1] < name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": name_off must be non-decreasing");
     SamfGeom g; uint32_t RL;
-    int rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
+    rc = check_sam_reads(ctx, who, n, offsets, front_clip, data_len, &RL, [&](uint32_t i) {
         if (!skip[i >> 1] && (uint32_t)data_len[i] > ctx->params.max_read_len)
             return fail(ctx, SNAPGPU_E_INVALID, "read longer than max_read_len given at snapgpu_create (IntersectingPairedEndAligner.cpp:361-365)");
         return (int)SNAPGPU_OK;
@@ -3129,10 +3211,10 @@ static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_p
     a.n_ops = st.out(n_ops, n4); a.nm = st.out(nm, n4);
     a.rnext = st.out(rnext, n4); a.pnext = st.out(pnext, n8); a.tlen = st.out(tlen, n8); a.first_written = st.out(first_written, (size_t)n_pairs * 4);
     a.stale = st.out(reference_history_dependent, n4);
-    const void *d_names = nullptr, *d_name_off = nullptr; void *d_text = nullptr, *d_line_begin = nullptr;
-    if (text) {
-        d_names = st.in(text->names, (size_t)text->name_off[n]); d_name_off = st.in(text->name_off, ((size_t)n + 1) * 8);
-        if (!text->z) { d_text = st.out(text->text, (size_t)text->cap); d_line_begin = st.out(text->line_begin, ((size_t)n + 1) * 8); }
+    const void *d_names = nullptr, *d_name_off = nullptr; void *d_bytes = nullptr, *d_begin = nullptr;
+    if (out) {
+        d_names = st.in(names, (size_t)name_off[n]); d_name_off = st.in(name_off, ((size_t)n + 1) * 8);
+        if (!z) { d_bytes = st.out(out->bytes, (size_t)out->cap); d_begin = st.out(out->begin, ((size_t)n + 1) * 8); }
     }
     if (st.rc) return st.rc;
     if ((rc = launch_paired(ctx, n_pairs, d_bases, d_quals, d_offsets, d_results, d_first_alt, st.s, &clip)) || (rc = finish_timing(ctx))) return rc;      // (the align launches' own hipEvent time, before the events are reused)
@@ -3141,31 +3223,21 @@ static int align_sam_paired_call(snapgpu_ctx *ctx, const char *who, uint32_t n_p
     snapgpu_launch_collect_flagged((snapgpu_paired_result *)d_results, n_pairs, ctx->d_flag_list, d_overflowed, 0, st.s);
     HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
     if ((rc = launch_sam_fields(ctx, a, g, n, ops_stride, use_m, st))) return rc;
-    if (!text) {
+    if (!out) {
         if ((rc = st.download()) || (rc = finish_timing(ctx))) return rc;
         return h_overflowed ? fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG) : SNAPGPU_OK;
     }
-    // ---- the lines of the pairs, from the fields where the SAM-field kernel left them (pair unit u is pair u)
+    // ---- the sink, from the fields where the SAM-field kernel left them (pair unit u is pair u); a pool overflow goes before the sink's warning
     if ((rc = finish_timing(ctx))) return rc;
-    const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, nullptr, a.flag, a.contig, a.pos, a.mapq, a.ops, ops_stride, a.n_ops, a.nm,
-                       text->cap, d_text, d_line_begin};
-    const SamTextPairIO pio{a.rnext, a.pnext, a.tlen, a.first_written};
-    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if (text->z) {                                                       // the BAM records left in HBM, and the blocks of those
-        void *d_bytes = nullptr; bool z_truncated = false;
-        if ((rc = bam_bytes_in_hbm(ctx, w, st, n, n, text->name_off, RL, io, &pio, &sum, &d_bytes)) ||
-            (rc = bgzf_tail(ctx, w, st, sum.total, d_bytes, *text->z, &z_truncated)) || (rc = st.download())) return rc;
-        *text->text_bytes = sum.total;
-        if (h_overflowed) return fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG);
-        return z_truncated ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
-    }
-    if ((rc = sam_text_core(ctx, w, st, n, io, &sum, &pio, text->bam))) return rc;
-    if (sum.flags & SAMTEXT_NM_OVERFLOW) return fail(ctx, SNAPGPU_E_INVALID, w + ": a record's cigar has more operations than ops_stride (call again with a larger ops_stride)");
-    st.limit(d_text, (size_t)sum.written);                               // only the lines that were written come down
-    if ((rc = st.download())) return rc;
-    *text->text_bytes = sum.total;
+    SamTextIO io{}; io.n = n_pairs; io.n_batch = n_pairs; io.pairs = true; io.ops_stride = ops_stride;
+    io.bases = d_bases; io.quals = d_quals; io.offsets = d_offsets; io.names = d_names; io.name_off = d_name_off;
+    io.flag = a.flag; io.contig = a.contig; io.pos = a.pos; io.mapq = a.mapq; io.ops = a.ops; io.n_ops = a.n_ops; io.nm = a.nm;
+    io.rnext = a.rnext; io.pnext = a.pnext; io.tlen = a.tlen; io.first_written = a.first_written;
+    uint64_t bytes = 0; bool out_truncated = false;
+    if ((rc = sam_out_in_hbm(ctx, w, st, io, name_off, RL, *out, d_bytes, d_begin, &bytes, &out_truncated)) || (rc = st.download())) return rc;
+    *out->total = bytes;
     if (h_overflowed) return fail(ctx, SNAPGPU_E_UNSUPPORTED, POOL_OVERFLOW_MSG);
-    return sum.total > text->cap ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+    return out_truncated ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
 extern "C" int snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
@@ -3179,119 +3251,31 @@ extern "C" int snapgpu_align_sam_paired(snapgpu_ctx *ctx, uint32_t n_pairs, cons
                              !nm || !rnext || !pnext || !tlen || !first_written || !reference_history_dependent)))
         return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired: null argument");
     return align_sam_paired_call(ctx, "snapgpu_align_sam_paired", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
-                                 flag, contig, pos, mapq, ops, ops_stride, n_ops, nm, rnext, pnext, tlen, first_written, reference_history_dependent, nullptr);
+                                 flag, contig, pos, mapq, ops, ops_stride, n_ops, nm, rnext, pnext, tlen, first_written, reference_history_dependent,
+                                 nullptr, nullptr, nullptr);
 }
 
-// Paired-end reads to the TEXT of their SAM records in one call (SAMFormat::writePairs, SAM.cpp:1575-1895, after what snapgpu_align_sam_paired replaces)
-extern "C" int snapgpu_align_sam_paired_text(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
-                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
-                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
-                                             snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
-                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
-{
-    if (!ctx || !line_begin || !text_bytes || (text_capacity && !text) ||
-        (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off || !flag || !first_written)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired_text: null argument");
-    const PairedTextOut t{names, name_off, text_capacity, text, line_begin, text_bytes, false};
-    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_text", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
-                                 flag, nullptr, nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, &t);
-}
-
-// The two lines of each pair unit from fields in HBM (SAMFormat::writePairs' snprintf, SAM.cpp:1854-1875; QNAME: ReadWriter.cpp:405-420; QS: SAM.cpp:1826-1834)
-static int sam_text_paired_device_call(snapgpu_ctx *ctx, const char *who, bool bam, uint64_t n_units, const void *d_bases, const void *d_quals, const void *d_offsets,
-                                              const void *d_names, const void *d_name_off, const void *d_unit_pair, const void *d_flag, const void *d_contig,
-                                              const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
-                                              const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
-                                              uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
-{
-    const std::string w(who);
-    if (!ctx || !text_bytes || !d_line_begin || (text_capacity && !d_text) ||
-        (n_units && (!d_bases || !d_quals || !d_offsets || !d_names || !d_name_off || !d_flag || !d_contig || !d_pos || !d_mapq || !d_ops || !d_n_ops || !d_nm ||
-                     !d_rnext || !d_pnext || !d_tlen || !d_first_written)))
-        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    if (n_units > 0x7fffffffull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^31 - 1 pair units in one call");
-    int rc = sam_text_check(ctx, w, 2 * n_units, ops_stride, bam);
-    if (rc) return rc;
-    if (n_units == 0) return sam_text_empty(ctx, false, d_line_begin, text_bytes, stream);
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
-    const SamTextIO io{d_bases, d_quals, d_offsets, d_names, d_name_off, d_unit_pair, d_flag, d_contig, d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm,
-                       text_capacity, d_text, d_line_begin};
-    const SamTextPairIO pio{d_rnext, d_pnext, d_tlen, d_first_written};
-    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, 2 * n_units, io, &sum, &pio, bam))) return rc;
-    *text_bytes = sum.total;
-    return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
-}
-
-// Host-pointer form: one upload, and only the lines that were written and line_begin come down
-static int sam_text_paired_call(snapgpu_ctx *ctx, const char *who, bool bam, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
-                                       const char *names, const uint64_t *name_off, const uint32_t *unit_pair, const int32_t *flag, const int32_t *contig,
-                                       const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
-                                       const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
-                                       uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
-{
-    const std::string w(who);
-    if (!ctx || !text_bytes || !line_begin || (text_capacity && !text) ||
-        (n_units && (!bases || !quals || !offsets || !names || !name_off || !flag || !contig || !pos || !mapq || !ops || !n_ops || !nm || !rnext || !pnext || !tlen ||
-                     !first_written)))
-        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    if (n_units > 0x7fffffffull) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^31 - 1 pair units in one call");
-    if (n_pairs > 0x7fffffffu) return fail(ctx, SNAPGPU_E_INVALID, w + ": too many pairs");
-    int rc = sam_text_check(ctx, w, 2 * n_units, ops_stride, bam);
-    if (rc) return rc;
-    if (n_units == 0) return sam_text_empty(ctx, true, line_begin, text_bytes, nullptr);
-    if (!unit_pair && n_units != n_pairs) return fail(ctx, SNAPGPU_E_INVALID, w + ": without unit_pair there is one unit per pair (n_units == n_pairs)");
-    const uint32_t n_reads = 2 * n_pairs;
-    for (uint32_t i = 0; i < n_reads; i++)
-        if (offsets[i + 1] < offsets[i] || name_off[i + 1] < name_off[i]) return fail(ctx, SNAPGPU_E_INVALID, w + ": offsets and name_off must be non-decreasing");
-    for (uint64_t u = 0; unit_pair && u < n_units; u++)
-        if (unit_pair[u] >= n_pairs) return fail(ctx, SNAPGPU_E_INVALID, w + ": unit_pair names a pair the batch does not have");
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    Stage st(ctx, ctx->stream);
-    const size_t nb = (size_t)offsets[n_reads], nl = 2 * (size_t)n_units, r4 = nl * 4, r8 = nl * 8;
-    SamTextIO io; SamTextPairIO pio;
-    io.bases = st.in(bases, nb); io.quals = st.in(quals, nb); io.offsets = st.in(offsets, ((size_t)n_reads + 1) * 8);
-    io.names = st.in(names, (size_t)name_off[n_reads]); io.name_off = st.in(name_off, ((size_t)n_reads + 1) * 8);
-    io.rec_read = unit_pair ? (const void *)st.in(unit_pair, (size_t)n_units * 4) : nullptr;
-    io.flag = st.in(flag, r4); io.contig = st.in(contig, r4); io.pos = st.in(pos, r8); io.mapq = st.in(mapq, r4);
-    io.ops = st.in(ops, r4 * ops_stride); io.ops_stride = ops_stride; io.n_ops = st.in(n_ops, r4); io.nm = st.in(nm, r4);
-    pio.rnext = st.in(rnext, r4); pio.pnext = st.in(pnext, r8); pio.tlen = st.in(tlen, r8); pio.first_written = st.in(first_written, (size_t)n_units * 4);
-    io.cap = text_capacity; io.text = st.out(text, (size_t)text_capacity); io.line_begin = st.out(line_begin, (nl + 1) * 8);
-    if (st.rc) return st.rc;
-    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = sam_text_core(ctx, w, st, nl, io, &sum, &pio, bam))) return rc;
-    st.limit(io.text, (size_t)sum.written);                              // only the lines that were written come down
-    if ((rc = st.download())) return rc;
-    *text_bytes = sum.total;
-    return sum.total > text_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
-}
-
-// ---- the exported forms of the bodies above: SAM lines (sam_text.h) and BAM records (sam_bam.h) ------------------------------------------------
+// ---- the exported forms of the bodies above: SAM lines (sam_text.h), BAM records (sam_bam.h: BAMFormat::writeRead, Bam.cpp:1312-1508, and
+// writePairs, Bam.cpp:1033-1309) and, for the fused calls, BGZF blocks.  Each fills the records and the sink by name.
 extern "C" int snapgpu_sam_text_single_device(snapgpu_ctx *ctx, uint64_t n_records, const void *d_bases, const void *d_quals, const void *d_offsets,
                                               const void *d_names, const void *d_name_off, const void *d_rec_read, const void *d_flag, const void *d_contig,
                                               const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
                                               uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
 {
-    return sam_text_single_device_call(ctx, "snapgpu_sam_text_single_device", false, n_records, d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig,
-                                       d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, text_capacity, d_text, d_line_begin, text_bytes, stream);
+    SamTextIO io{}; io.n = n_records; io.ops_stride = ops_stride;
+    io.bases = d_bases; io.quals = d_quals; io.offsets = d_offsets; io.names = d_names; io.name_off = d_name_off; io.rec_read = d_rec_read;
+    io.flag = d_flag; io.contig = d_contig; io.pos = d_pos; io.mapq = d_mapq; io.ops = d_ops; io.n_ops = d_n_ops; io.nm = d_nm;
+    return sam_out_call(ctx, "snapgpu_sam_text_single_device", io, SamOut{SAM_OUT_TEXT, text_capacity, d_text, d_line_begin, text_bytes, {}}, false, stream);
 }
 extern "C" int snapgpu_sam_text_single(snapgpu_ctx *ctx, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
                                        const char *names, const uint64_t *name_off, const uint32_t *rec_read, const int32_t *flag, const int32_t *contig,
                                        const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
                                        uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
 {
-    return sam_text_single_call(ctx, "snapgpu_sam_text_single", false, n_records, n_reads, bases, quals, offsets, names, name_off, rec_read, flag, contig, pos, mapq, ops,
-                                ops_stride, n_ops, nm, text_capacity, text, line_begin, text_bytes);
-}
-extern "C" int snapgpu_align_sam_single_text(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
-                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
-                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
-                                             uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
-                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
-{
-    return align_sam_single_text_call(ctx, "snapgpu_align_sam_single_text", false, n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
-                                      ops_stride, record_capacity, n_records, rec_begin, flag, text_capacity, text, line_begin, text_bytes);
+    SamTextIO io{}; io.n = n_records; io.n_batch = n_reads; io.ops_stride = ops_stride;
+    io.bases = bases; io.quals = quals; io.offsets = offsets; io.names = names; io.name_off = name_off; io.rec_read = rec_read;
+    io.flag = flag; io.contig = contig; io.pos = pos; io.mapq = mapq; io.ops = ops; io.n_ops = n_ops; io.nm = nm;
+    return sam_out_call(ctx, "snapgpu_sam_text_single", io, SamOut{SAM_OUT_TEXT, text_capacity, text, line_begin, text_bytes, {}}, true, nullptr);
 }
 extern "C" int snapgpu_sam_text_paired_device(snapgpu_ctx *ctx, uint64_t n_units, const void *d_bases, const void *d_quals, const void *d_offsets,
                                               const void *d_names, const void *d_name_off, const void *d_unit_pair, const void *d_flag, const void *d_contig,
@@ -3299,9 +3283,11 @@ extern "C" int snapgpu_sam_text_paired_device(snapgpu_ctx *ctx, uint64_t n_units
                                               const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
                                               uint64_t text_capacity, void *d_text, void *d_line_begin, uint64_t *text_bytes, void *stream)
 {
-    return sam_text_paired_device_call(ctx, "snapgpu_sam_text_paired_device", false, n_units, d_bases, d_quals, d_offsets, d_names, d_name_off, d_unit_pair, d_flag, d_contig,
-                                       d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_rnext, d_pnext, d_tlen, d_first_written, text_capacity, d_text, d_line_begin,
-                                       text_bytes, stream);
+    SamTextIO io{}; io.n = n_units; io.pairs = true; io.ops_stride = ops_stride;
+    io.bases = d_bases; io.quals = d_quals; io.offsets = d_offsets; io.names = d_names; io.name_off = d_name_off; io.rec_read = d_unit_pair;
+    io.flag = d_flag; io.contig = d_contig; io.pos = d_pos; io.mapq = d_mapq; io.ops = d_ops; io.n_ops = d_n_ops; io.nm = d_nm;
+    io.rnext = d_rnext; io.pnext = d_pnext; io.tlen = d_tlen; io.first_written = d_first_written;
+    return sam_out_call(ctx, "snapgpu_sam_text_paired_device", io, SamOut{SAM_OUT_TEXT, text_capacity, d_text, d_line_begin, text_bytes, {}}, false, stream);
 }
 extern "C" int snapgpu_sam_text_paired(snapgpu_ctx *ctx, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
                                        const char *names, const uint64_t *name_off, const uint32_t *unit_pair, const int32_t *flag, const int32_t *contig,
@@ -3309,46 +3295,43 @@ extern "C" int snapgpu_sam_text_paired(snapgpu_ctx *ctx, uint64_t n_units, uint3
                                        const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
                                        uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
 {
-    return sam_text_paired_call(ctx, "snapgpu_sam_text_paired", false, n_units, n_pairs, bases, quals, offsets, names, name_off, unit_pair, flag, contig, pos, mapq, ops,
-                                ops_stride, n_ops, nm, rnext, pnext, tlen, first_written, text_capacity, text, line_begin, text_bytes);
+    SamTextIO io{}; io.n = n_units; io.n_batch = n_pairs; io.pairs = true; io.ops_stride = ops_stride;
+    io.bases = bases; io.quals = quals; io.offsets = offsets; io.names = names; io.name_off = name_off; io.rec_read = unit_pair;
+    io.flag = flag; io.contig = contig; io.pos = pos; io.mapq = mapq; io.ops = ops; io.n_ops = n_ops; io.nm = nm;
+    io.rnext = rnext; io.pnext = pnext; io.tlen = tlen; io.first_written = first_written;
+    return sam_out_call(ctx, "snapgpu_sam_text_paired", io, SamOut{SAM_OUT_TEXT, text_capacity, text, line_begin, text_bytes, {}}, true, nullptr);
 }
-
-// Records -> the bytes of their BAM records (BAMFormat::writeRead, Bam.cpp:1312-1508): the three forms of the single-end text calls
 extern "C" int snapgpu_bam_records_single_device(snapgpu_ctx *ctx, uint64_t n_records, const void *d_bases, const void *d_quals, const void *d_offsets,
                                                  const void *d_names, const void *d_name_off, const void *d_rec_read, const void *d_flag, const void *d_contig,
                                                  const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
                                                  uint64_t byte_capacity, void *d_bytes, void *d_block_begin, uint64_t *bam_bytes, void *stream)
 {
-    return sam_text_single_device_call(ctx, "snapgpu_bam_records_single_device", true, n_records, d_bases, d_quals, d_offsets, d_names, d_name_off, d_rec_read, d_flag, d_contig,
-                                       d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, byte_capacity, d_bytes, d_block_begin, bam_bytes, stream);
+    SamTextIO io{}; io.n = n_records; io.ops_stride = ops_stride;
+    io.bases = d_bases; io.quals = d_quals; io.offsets = d_offsets; io.names = d_names; io.name_off = d_name_off; io.rec_read = d_rec_read;
+    io.flag = d_flag; io.contig = d_contig; io.pos = d_pos; io.mapq = d_mapq; io.ops = d_ops; io.n_ops = d_n_ops; io.nm = d_nm;
+    return sam_out_call(ctx, "snapgpu_bam_records_single_device", io, SamOut{SAM_OUT_BAM, byte_capacity, d_bytes, d_block_begin, bam_bytes, {}}, false, stream);
 }
 extern "C" int snapgpu_bam_records_single(snapgpu_ctx *ctx, uint64_t n_records, uint32_t n_reads, const char *bases, const char *quals, const uint64_t *offsets,
                                           const char *names, const uint64_t *name_off, const uint32_t *rec_read, const int32_t *flag, const int32_t *contig,
                                           const int64_t *pos, const int32_t *mapq, const uint32_t *ops, uint32_t ops_stride, const int32_t *n_ops, const int32_t *nm,
                                           uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
 {
-    return sam_text_single_call(ctx, "snapgpu_bam_records_single", true, n_records, n_reads, bases, quals, offsets, names, name_off, rec_read, flag, contig, pos, mapq, ops,
-                                ops_stride, n_ops, nm, byte_capacity, (char *)bytes, block_begin, bam_bytes);
+    SamTextIO io{}; io.n = n_records; io.n_batch = n_reads; io.ops_stride = ops_stride;
+    io.bases = bases; io.quals = quals; io.offsets = offsets; io.names = names; io.name_off = name_off; io.rec_read = rec_read;
+    io.flag = flag; io.contig = contig; io.pos = pos; io.mapq = mapq; io.ops = ops; io.n_ops = n_ops; io.nm = nm;
+    return sam_out_call(ctx, "snapgpu_bam_records_single", io, SamOut{SAM_OUT_BAM, byte_capacity, bytes, block_begin, bam_bytes, {}}, true, nullptr);
 }
-extern "C" int snapgpu_align_sam_single_bam(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
-                                            const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
-                                            const char *names, const uint64_t *name_off, uint32_t ops_stride,
-                                            uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
-                                            uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
-{
-    return align_sam_single_text_call(ctx, "snapgpu_align_sam_single_bam", true, n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
-                                      ops_stride, record_capacity, n_records, rec_begin, flag, byte_capacity, (char *)bytes, block_begin, bam_bytes);
-}
-// The two BAM records of each pair unit (BAMFormat::writePairs, Bam.cpp:1033-1309): the three forms of the paired text calls
 extern "C" int snapgpu_bam_records_paired_device(snapgpu_ctx *ctx, uint64_t n_units, const void *d_bases, const void *d_quals, const void *d_offsets,
                                                  const void *d_names, const void *d_name_off, const void *d_unit_pair, const void *d_flag, const void *d_contig,
                                                  const void *d_pos, const void *d_mapq, const void *d_ops, uint32_t ops_stride, const void *d_n_ops, const void *d_nm,
                                                  const void *d_rnext, const void *d_pnext, const void *d_tlen, const void *d_first_written,
                                                  uint64_t byte_capacity, void *d_bytes, void *d_block_begin, uint64_t *bam_bytes, void *stream)
 {
-    return sam_text_paired_device_call(ctx, "snapgpu_bam_records_paired_device", true, n_units, d_bases, d_quals, d_offsets, d_names, d_name_off, d_unit_pair, d_flag, d_contig,
-                                       d_pos, d_mapq, d_ops, ops_stride, d_n_ops, d_nm, d_rnext, d_pnext, d_tlen, d_first_written, byte_capacity, d_bytes, d_block_begin,
-                                       bam_bytes, stream);
+    SamTextIO io{}; io.n = n_units; io.pairs = true; io.ops_stride = ops_stride;
+    io.bases = d_bases; io.quals = d_quals; io.offsets = d_offsets; io.names = d_names; io.name_off = d_name_off; io.rec_read = d_unit_pair;
+    io.flag = d_flag; io.contig = d_contig; io.pos = d_pos; io.mapq = d_mapq; io.ops = d_ops; io.n_ops = d_n_ops; io.nm = d_nm;
+    io.rnext = d_rnext; io.pnext = d_pnext; io.tlen = d_tlen; io.first_written = d_first_written;
+    return sam_out_call(ctx, "snapgpu_bam_records_paired_device", io, SamOut{SAM_OUT_BAM, byte_capacity, d_bytes, d_block_begin, bam_bytes, {}}, false, stream);
 }
 extern "C" int snapgpu_bam_records_paired(snapgpu_ctx *ctx, uint64_t n_units, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
                                           const char *names, const uint64_t *name_off, const uint32_t *unit_pair, const int32_t *flag, const int32_t *contig,
@@ -3356,25 +3339,33 @@ extern "C" int snapgpu_bam_records_paired(snapgpu_ctx *ctx, uint64_t n_units, ui
                                           const int32_t *rnext, const int64_t *pnext, const int64_t *tlen, const int32_t *first_written,
                                           uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
 {
-    return sam_text_paired_call(ctx, "snapgpu_bam_records_paired", true, n_units, n_pairs, bases, quals, offsets, names, name_off, unit_pair, flag, contig, pos, mapq, ops,
-                                ops_stride, n_ops, nm, rnext, pnext, tlen, first_written, byte_capacity, (char *)bytes, block_begin, bam_bytes);
-}
-extern "C" int snapgpu_align_sam_paired_bam(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
-                                            const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
-                                            const char *names, const uint64_t *name_off, uint32_t ops_stride,
-                                            snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
-                                            uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
-{
-    if (!ctx || !block_begin || !bam_bytes || (byte_capacity && !bytes) ||
-        (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off || !flag || !first_written)))
-        return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_paired_bam: null argument");
-    const PairedTextOut t{names, name_off, byte_capacity, (char *)bytes, block_begin, bam_bytes, true};
-    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bam", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
-                                 flag, nullptr, nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, &t);
+    SamTextIO io{}; io.n = n_units; io.n_batch = n_pairs; io.pairs = true; io.ops_stride = ops_stride;
+    io.bases = bases; io.quals = quals; io.offsets = offsets; io.names = names; io.name_off = name_off; io.rec_read = unit_pair;
+    io.flag = flag; io.contig = contig; io.pos = pos; io.mapq = mapq; io.ops = ops; io.n_ops = n_ops; io.nm = nm;
+    io.rnext = rnext; io.pnext = pnext; io.tlen = tlen; io.first_written = first_written;
+    return sam_out_call(ctx, "snapgpu_bam_records_paired", io, SamOut{SAM_OUT_BAM, byte_capacity, bytes, block_begin, bam_bytes, {}}, true, nullptr);
 }
 
-// The two calls above with the record bytes and block_begin left in HBM and snapgpu_bgzf_compress_device behind them on the same stream: what the
-// BGZF writer of SNAPLib/Bam.cpp behind DataWriter's gzip filter, and bgzf_append of the tool, do with the records of a batch
+// The fused calls.  _bgzf: the _bam call with the record bytes and block_begin left in HBM and snapgpu_bgzf_compress_device behind them on the same
+// stream -- what the BGZF writer of SNAPLib/Bam.cpp behind DataWriter's gzip filter, and bgzf_append of the tool, do with the records of a batch.
+extern "C" int snapgpu_align_sam_single_text(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                             uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    return align_sam_single_out_call(ctx, "snapgpu_align_sam_single_text", n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
+                                     ops_stride, record_capacity, n_records, rec_begin, flag, SamOut{SAM_OUT_TEXT, text_capacity, text, line_begin, text_bytes, {}});
+}
+extern "C" int snapgpu_align_sam_single_bam(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                            const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                            const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                            uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                            uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
+{
+    return align_sam_single_out_call(ctx, "snapgpu_align_sam_single_bam", n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
+                                     ops_stride, record_capacity, n_records, rec_begin, flag, SamOut{SAM_OUT_BAM, byte_capacity, bytes, block_begin, bam_bytes, {}});
+}
 extern "C" int snapgpu_align_sam_single_bgzf(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
                                              const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
                                              const char *names, const uint64_t *name_off, uint32_t ops_stride,
@@ -3382,10 +3373,30 @@ extern "C" int snapgpu_align_sam_single_bgzf(snapgpu_ctx *ctx, uint32_t n, const
                                              uint32_t block_input, uint64_t bgzf_capacity, uint8_t *bgzf, uint64_t *member_begin, uint64_t member_capacity,
                                              uint64_t *n_members, uint64_t *bgzf_bytes, uint64_t *bam_bytes)
 {
-    if (!ctx) return fail(ctx, SNAPGPU_E_INVALID, "snapgpu_align_sam_single_bgzf: null argument");
     const BgzfOut z{block_input, bgzf_capacity, bgzf, member_begin, member_capacity, n_members, bgzf_bytes};
-    return align_sam_single_text_call(ctx, "snapgpu_align_sam_single_bgzf", true, n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
-                                      ops_stride, record_capacity, n_records, rec_begin, flag, 0, nullptr, nullptr, bam_bytes, &z);
+    return align_sam_single_out_call(ctx, "snapgpu_align_sam_single_bgzf", n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
+                                     ops_stride, record_capacity, n_records, rec_begin, flag, SamOut{SAM_OUT_BGZF, 0, nullptr, nullptr, bam_bytes, z});
+}
+// (paired: SAMFormat::writePairs, SAM.cpp:1575-1895, after what snapgpu_align_sam_paired replaces)
+extern "C" int snapgpu_align_sam_paired_text(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                             const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                             const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                             snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                             uint64_t text_capacity, char *text, uint64_t *line_begin, uint64_t *text_bytes)
+{
+    const SamOut out{SAM_OUT_TEXT, text_capacity, text, line_begin, text_bytes, {}};
+    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_text", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt, flag, nullptr,
+                                 nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, names, name_off, &out);
+}
+extern "C" int snapgpu_align_sam_paired_bam(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                            const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                            const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                            snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                            uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes)
+{
+    const SamOut out{SAM_OUT_BAM, byte_capacity, bytes, block_begin, bam_bytes, {}};
+    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bam", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt, flag, nullptr,
+                                 nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, names, name_off, &out);
 }
 extern "C" int snapgpu_align_sam_paired_bgzf(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
                                              const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
@@ -3394,85 +3405,10 @@ extern "C" int snapgpu_align_sam_paired_bgzf(snapgpu_ctx *ctx, uint32_t n_pairs,
                                              uint32_t block_input, uint64_t bgzf_capacity, uint8_t *bgzf, uint64_t *member_begin, uint64_t member_capacity,
                                              uint64_t *n_members, uint64_t *bgzf_bytes, uint64_t *bam_bytes)
 {
-    const std::string w("snapgpu_align_sam_paired_bgzf");
-    if (!ctx || !bam_bytes || (n_pairs && (!bases || !quals || !offsets || !front_clip || !data_len || !skip || !names || !name_off || !flag || !first_written)))
-        return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
     const BgzfOut z{block_input, bgzf_capacity, bgzf, member_begin, member_capacity, n_members, bgzf_bytes};
-    if (const int rc = bgzf_out_check(ctx, w, z)) return rc;
-    uint64_t no_block_begin = 0;
-    PairedTextOut t{names, name_off, 0, nullptr, &no_block_begin, bam_bytes, true}; t.z = &z;
-    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bgzf", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt,
-                                 flag, nullptr, nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, &t);
-}
-
-// ---- bytes -> BGZF blocks (bgzf.h): what bgzf_append of the tool (host/snapgpu_sam.cpp) does with zlib, and on the reference's side the BGZF writer
-// of SNAPLib/Bam.cpp behind DataWriter's gzip filter.  Everything in HBM; the stream is synchronised when bgzf_core returns.
-static uint64_t bgzf_members(uint64_t n_bytes, uint32_t block_input) { return n_bytes ? (n_bytes + block_input - 1) / block_input : 1; }
-static int bgzf_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_bytes, uint32_t block_input)
-{
-    if (block_input == 0 || block_input > BGZF_MAX_BLOCK_INPUT) return fail(ctx, SNAPGPU_E_INVALID, w + ": block_input must be between 1 and 0xff00");
-    if (bgzf_members(n_bytes, block_input) > 0xFFFFFFFFull - SAMREC_CHUNK) return fail(ctx, SNAPGPU_E_UNSUPPORTED, w + ": more than 2^32 - 1 blocks in one call");
-    return SNAPGPU_OK;
-}
-static int bgzf_core(snapgpu_ctx *ctx, Stage &st, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t cap, void *d_out, void *d_member_begin,
-                     SamTextSummary *sum)
-{
-    BgzfArgs a; memset(&a, 0, sizeof(a));
-    a.n_bytes = n_bytes; a.block_input = block_input; a.n_members = (uint32_t)bgzf_members(n_bytes, block_input);
-    a.in = (const uint8_t *)d_in; a.cap = cap; a.out = (uint8_t *)d_out; a.member_begin = (uint64_t *)d_member_begin;
-    // a wavefront of the deflate launch holds BGZF_LDS_WORDS dwords of LDS: eight to a CU
-    uint32_t deflate_blocks = (uint32_t)ctx->num_cus * 4, scan_blocks = (uint32_t)ctx->num_cus * 8, place_blocks = scan_blocks;
-    if (deflate_blocks > a.n_members) deflate_blocks = a.n_members;
-    { const uint32_t need = (a.n_members + SAMREC_CHUNK - 1) / SAMREC_CHUNK; if (scan_blocks > (need + 3) / 4) scan_blocks = (need + 3) / 4; }
-    { const uint32_t need = (a.n_members + 3) / 4; if (place_blocks > need) place_blocks = need; }
-    a.tok_stride = (uint64_t)block_input + 1; a.slot_stride = ((uint64_t)block_input + 31 + 3) & ~(uint64_t)3;
-    a.tok = st.scratch((size_t)deflate_blocks * a.tok_stride * 4); a.slots = st.scratch((size_t)a.n_members * a.slot_stride);
-    a.size = st.scratch((size_t)a.n_members * 4 + 4); a.partial = st.scratch((size_t)((a.n_members + SAMREC_CHUNK - 1) / SAMREC_CHUNK) * 8);
-    a.summary = st.scratch(sizeof(SamTextSummary));
-    if (st.rc) return st.rc;
-    HIPCHK(ctx, hipMemsetAsync(a.summary, 0, sizeof(SamTextSummary), st.s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemsetAsync(a.slots, 0, (size_t)a.n_members * a.slot_stride, st.s), SNAPGPU_E_LAUNCH);      // (the bits of a member are ORed into its slot)
-    HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
-    snapgpu_launch_bgzf(&a, deflate_blocks, scan_blocks, place_blocks, st.s);
-    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(sum, a.summary, sizeof(SamTextSummary), hipMemcpyDeviceToHost, st.s), SNAPGPU_E_LAUNCH);
-    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
-    return finish_timing(ctx);
-}
-extern "C" int snapgpu_bgzf_compress_device(snapgpu_ctx *ctx, uint64_t n_bytes, const void *d_in, uint32_t block_input, uint64_t out_capacity, void *d_out,
-                                            void *d_member_begin, uint64_t *n_members, uint64_t *out_bytes, void *stream)
-{
-    const std::string w("snapgpu_bgzf_compress_device");
-    if (!ctx || !n_members || !out_bytes || !d_member_begin || (out_capacity && !d_out) || (n_bytes && !d_in)) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    int rc = bgzf_check(ctx, w, n_bytes, block_input);
-    if (rc) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
-    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = bgzf_core(ctx, st, n_bytes, d_in, block_input, out_capacity, d_out, d_member_begin, &sum))) return rc;
-    *n_members = bgzf_members(n_bytes, block_input); *out_bytes = sum.total;
-    return sum.total > out_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
-}
-extern "C" int snapgpu_bgzf_compress(snapgpu_ctx *ctx, uint64_t n_bytes, const uint8_t *in, uint32_t block_input, uint64_t out_capacity, uint8_t *out,
-                                     uint64_t *member_begin, uint64_t *n_members, uint64_t *out_bytes)
-{
-    const std::string w("snapgpu_bgzf_compress");
-    if (!ctx || !n_members || !out_bytes || !member_begin || (out_capacity && !out) || (n_bytes && !in)) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
-    int rc = bgzf_check(ctx, w, n_bytes, block_input);
-    if (rc) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
-    Stage st(ctx, ctx->stream);
-    const uint64_t nm = bgzf_members(n_bytes, block_input);
-    const void *d_in = st.in(in, (size_t)n_bytes, 16);
-    void *d_out = st.out(out, (size_t)out_capacity), *d_member_begin = st.out(member_begin, ((size_t)nm + 1) * 8);
-    if (st.rc) return st.rc;
-    SamTextSummary sum; memset(&sum, 0, sizeof(sum));
-    if ((rc = bgzf_core(ctx, st, n_bytes, d_in, block_input, out_capacity, d_out, d_member_begin, &sum))) return rc;
-    st.limit(d_out, (size_t)sum.written);                                // only the members that were written come down
-    if ((rc = st.download())) return rc;
-    *n_members = nm; *out_bytes = sum.total;
-    return sum.total > out_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
+    const SamOut out{SAM_OUT_BGZF, 0, nullptr, nullptr, bam_bytes, z};
+    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bgzf", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt, flag, nullptr,
+                                 nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, names, name_off, &out);
 }
 
 // Diagnostics (not part of the drop-in surface): how many SamfPre records the row-loop pre-pass (k_samf_dp8 / k_samf_dp8_paired) of the context's
