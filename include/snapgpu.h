@@ -834,6 +834,44 @@ int  snapgpu_align_sam_paired_bgzf(snapgpu_ctx *ctx, uint32_t n_pairs, const cha
                                    uint64_t *n_members, uint64_t *bgzf_bytes, uint64_t *bam_bytes);
 
 /*
+ * BAM records -> coordinate order on the device (what the reference's -so does per sort block, SortedDataWriter.cpp).  Record i is the bytes
+ * [block_begin[i], block_begin[i + 1]) at any byte address, and its key comes from its own words, read bytewise:
+ *   key = (uint64)(uint32)refID << 32 | (uint32)(pos + 1)        refID: the int32 at record offset 4, pos: the int32 at record offset 8
+ * so refID -1 sorts behind every contig, and an unmapped mate that carries its mate's coordinates sorts with its mate: the SAM specification's
+ * coordinate order.  The output is the STABLE sort by key (ties keep the input order), hence a function of the input alone:
+ *   d_sorted / sorted: block_begin[n_records] bytes at any byte address, not overlapping the input: the records in sorted order;
+ *   d_sorted_begin / sorted_begin: uint64 [n_records + 1], the record at place r is sorted[sorted_begin[r], sorted_begin[r + 1]);
+ *   d_perm / perm: uint32 [n_records] or NULL: the input index of the record at place r;  d_key / key: uint64 [n_records] or NULL: its key.
+ * The host form takes block_begin[0] as where the first record starts in `bytes`, and sorted_begin starts at 0.  n_records 0 is valid:
+ * nothing is written but sorted_begin[0] = 0.  SNAPGPU_E_INVALID, with every output untouched: NULL where a pointer is needed, a decreasing
+ * block_begin, a record shorter than 12 bytes (or of 4 GB or more), n_records above 2^32 - 1.  The device form is synchronous on `stream`
+ * (NULL: the context's); the host form goes through the staging layer of the other host-pointer entry points.
+ */
+int  snapgpu_bam_sort_device(snapgpu_ctx *ctx, uint64_t n_records, const void *d_bytes, const void *d_block_begin, void *d_sorted, void *d_sorted_begin,
+                             void *d_key, void *d_perm, void *stream);
+int  snapgpu_bam_sort(snapgpu_ctx *ctx, uint64_t n_records, const uint8_t *bytes, const uint64_t *block_begin, uint8_t *sorted, uint64_t *sorted_begin,
+                      uint64_t *key, uint32_t *perm);
+
+/*
+ * snapgpu_align_sam_single_bam / snapgpu_align_sam_paired_bam with the sort behind them: the unsorted record bytes and the sort's scratch stay in
+ * HBM, in buffers whose size is the library's business, and `bytes` / `block_begin` come back in key order -- exactly snapgpu_bam_sort over what
+ * the _bam form returns, with its key and perm (each NULL or [record_capacity] / [2 * n_pairs]).  rec_begin, flag, first_written and the results
+ * stay in record order, as in the _bam form.  For pairs every record is sorted on its own, so mates separate.  Every argument, check, warning and
+ * error is the _bam form's, except that under SNAPGPU_W_RECORDS_TRUNCATED or SNAPGPU_W_TEXT_TRUNCATED the counts (*n_records, *bam_bytes) are
+ * complete as there and bytes, block_begin, key and perm hold nothing the caller may use: it enlarges and calls again.
+ */
+int  snapgpu_align_sam_single_bam_sorted(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                         const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                         const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                         uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                         uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes, uint64_t *key, uint32_t *perm);
+int  snapgpu_align_sam_paired_bam_sorted(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                         const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                         const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                         snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                         uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes, uint64_t *key, uint32_t *perm);
+
+/*
  * Batched AffineGapVectorized<dir>::computeScore (banded[i] == 0) / computeScoreBanded
  * (banded[i] != 0).  Same string conventions as snapgpu_landau_vishkin; w[i] is the band
  * / edit limit, score_init[i] the initial score, is_rc[i] selects the end bonus.

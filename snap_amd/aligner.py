@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "snapgpu_set_contig_bam_ids", "snapgpu_bam_records_single", "snapgpu_bam_records_single_device", "snapgpu_align_sam_single_bam",
     "snapgpu_bam_records_paired", "snapgpu_bam_records_paired_device", "snapgpu_align_sam_paired_bam",
     "snapgpu_bgzf_compress", "snapgpu_bgzf_compress_device", "snapgpu_align_sam_single_bgzf", "snapgpu_align_sam_paired_bgzf",
+    "snapgpu_bam_sort", "snapgpu_bam_sort_device", "snapgpu_align_sam_single_bam_sorted", "snapgpu_align_sam_paired_bam_sorted",
     "snapgpu_default_index_build_params", "snapgpu_index_build", "snapgpu_index_build_from_fasta", "snapgpu_index_build_shaped",
     "snapgpu_index_build_from_fasta_shaped", "snapgpu_built_index_view",
     "snapgpu_built_index_save", "snapgpu_built_index_stats", "snapgpu_built_index_destroy",
@@ -482,7 +483,7 @@ class BaseAligner:
 
     def alignSamText(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
                      adjust_primary: bool = False, capacity: int | None = None, text_capacity: int | None = None, grow: bool = True,
-                     _fn: str = "snapgpu_align_sam_single_text"):
+                     _fn: str = "snapgpu_align_sam_single_text", _sorted: bool = False):
         """Single-end reads to the text of all their SAM records in one call (snapgpu_align_sam_single_text): alignSamRecords' inputs plus the
         reads' names; capacity / text_capacity: records / bytes to make room for (defaults: estimates); grow: call again with what the
         library asks for when one was too small.  Returns dict(text, line_begin, text_bytes, truncated, n_records, records_truncated,
@@ -498,12 +499,15 @@ class BaseAligner:
         rec_begin = np.zeros(n + 1, np.uint64)
         f = getattr(self.lib, _fn)
         f.argtypes = ([C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 3 +
-                      [C.c_uint64] + [C.c_void_p] * 3)
+                      [C.c_uint64] + [C.c_void_p] * (5 if _sorted else 3))
         while True:
             flag = np.zeros(cap, np.int32); line_begin = np.zeros(cap + 1, np.uint64); text = np.zeros(tcap, np.uint8)
+            if _sorted:
+                key = np.zeros(cap, np.uint64); perm = np.zeros(cap, np.uint32)
             n_rec = C.c_uint64(0); tb = C.c_uint64(0)
             rc = f(self.handle, n, ptr(bases), ptr(quals), ptr(offsets), ptr(front_clip), ptr(data_len), ptr(skip), 1 if use_m else 0, 1 if adjust_primary else 0,
-                   ptr(names), ptr(name_off), ops_stride, cap, C.addressof(n_rec), ptr(rec_begin), ptr(flag), tcap, ptr(text), ptr(line_begin), C.addressof(tb))
+                   ptr(names), ptr(name_off), ops_stride, cap, C.addressof(n_rec), ptr(rec_begin), ptr(flag), tcap, ptr(text), ptr(line_begin), C.addressof(tb),
+                   *((ptr(key), ptr(perm)) if _sorted else ()))
             if rc == W_RECORDS_TRUNCATED and grow:
                 cap = int(n_rec.value)
                 continue
@@ -514,8 +518,11 @@ class BaseAligner:
                 self._check(rc, _fn)
             break
         m = min(int(n_rec.value), cap)
-        return dict(text=text, line_begin=line_begin[:m + 1], text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED, n_records=int(n_rec.value),
-                    records_truncated=rc == W_RECORDS_TRUNCATED, rec_begin=rec_begin, flag=flag[:m])
+        d = dict(text=text, line_begin=line_begin[:m + 1], text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED, n_records=int(n_rec.value),
+                 records_truncated=rc == W_RECORDS_TRUNCATED, rec_begin=rec_begin, flag=flag[:m])
+        if _sorted:
+            d.update(key=key[:m], perm=perm[:m])
+        return d
 
     # ---- records -> the bytes of their BAM records (BAMFormat::writeRead) ----
     def setContigBamIds(self, ref_id=None, n_contigs: int | None = None):
@@ -556,6 +563,48 @@ class BaseAligner:
         return self._as_bam(self.alignSamText(bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m=use_m, ops_stride=ops_stride,
                                               adjust_primary=adjust_primary, capacity=capacity, text_capacity=byte_capacity, grow=grow,
                                               _fn="snapgpu_align_sam_single_bam"))
+
+    # ---- BAM records -> coordinate order (the reference's -so, per batch) ----
+    def bamSort(self, data, block_begin, want_key: bool = True, want_perm: bool = True, out=None):
+        """The BAM records data[block_begin[i] : block_begin[i + 1]] in coordinate order (snapgpu_bam_sort): the stable sort by
+        (uint32 refID) << 32 | uint32(pos + 1), the two words read from the records themselves.  out: a uint8 array of at least the records'
+        bytes to write into.  Returns dict(sorted uint8, sorted_begin uint64[n + 1], key uint64[n] or None, perm uint32[n] or None);
+        perm[r] is the input index of the record at place r."""
+        data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.asarray(data)
+        if data.dtype != np.uint8 or (data.size and not data.flags.c_contiguous):
+            data = np.ascontiguousarray(data, dtype=np.uint8)
+        data = data.reshape(-1)
+        block_begin = np.ascontiguousarray(block_begin, dtype=np.uint64)
+        n = block_begin.size - 1
+        nb = int(block_begin[n] - block_begin[0]) if n > 0 and block_begin[n] >= block_begin[0] else 0
+        if out is None:
+            out = np.zeros(nb, np.uint8)
+        sorted_begin = np.zeros(n + 1, np.uint64)
+        key = np.zeros(n, np.uint64) if want_key else None
+        perm = np.zeros(n, np.uint32) if want_perm else None
+        f = self.lib.snapgpu_bam_sort
+        f.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6
+        self._check(f(self.handle, n, ptr(data) if data.size else None, ptr(block_begin), ptr(out) if out.size else None, ptr(sorted_begin),
+                      ptr(key) if want_key else None, ptr(perm) if want_perm else None), "snapgpu_bam_sort")
+        return dict(sorted=out, sorted_begin=sorted_begin, key=key, perm=perm)
+
+    def bamSort_device(self, n_records: int, d_bytes: int, d_block_begin: int, d_sorted: int, d_sorted_begin: int, d_key: int = 0, d_perm: int = 0,
+                       stream: int = 0):
+        """Device-pointer form of bamSort (snapgpu_bam_sort_device): the records, block_begin (uint64[n + 1]) and every output in HBM, the bytes
+        at any byte address; d_key / d_perm 0: not wanted.  Synchronous on `stream` (0: the context's)."""
+        vp = lambda x: C.c_void_p(x) if x else None
+        f = self.lib.snapgpu_bam_sort_device
+        f.argtypes = [C.c_void_p, C.c_uint64] + [C.c_void_p] * 7
+        self._check(f(self.handle, n_records, vp(d_bytes), vp(d_block_begin), vp(d_sorted), vp(d_sorted_begin), vp(d_key), vp(d_perm), vp(stream)),
+                    "snapgpu_bam_sort_device")
+
+    def alignSamBamSorted(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
+                          adjust_primary: bool = False, capacity: int | None = None, byte_capacity: int | None = None, grow: bool = True):
+        """alignSamBam with the sort behind it on the device (snapgpu_align_sam_single_bam_sorted): bytes / block_begin come back in coordinate
+        order, rec_begin and flag stay in record order.  Returns alignSamBam's dict plus key uint64[records] and perm uint32[records]."""
+        return self._as_bam(self.alignSamText(bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m=use_m, ops_stride=ops_stride,
+                                              adjust_primary=adjust_primary, capacity=capacity, text_capacity=byte_capacity, grow=grow,
+                                              _fn="snapgpu_align_sam_single_bam_sorted", _sorted=True))
 
     # ---- bytes -> BGZF blocks (the BGZF writer behind BAMFormat, DataWriter's gzip filter) ----
     @staticmethod
@@ -915,7 +964,8 @@ class ChimericPairedEndAligner(BaseAligner):
         return int(tb.value), rc == W_TEXT_TRUNCATED
 
     def alignSamTextPaired(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
-                           text_capacity: int | None = None, grow: bool = True, want_results: bool = False, _fn: str = "snapgpu_align_sam_paired_text"):
+                           text_capacity: int | None = None, grow: bool = True, want_results: bool = False, _fn: str = "snapgpu_align_sam_paired_text",
+                           _sorted: bool = False):
         """Paired-end reads to the text of their SAM records in one call (snapgpu_align_sam_paired_text): alignSamPaired's inputs plus the
         mates' names; text_capacity: bytes to make room for (default: an estimate); grow: call again with what the library asks for when
         that was too few.  Returns dict(text, line_begin uint64[2 n_pairs + 1], text_bytes, truncated, flag [2 n_pairs], first_written
@@ -933,21 +983,26 @@ class ChimericPairedEndAligner(BaseAligner):
         results = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
         first_alt = np.zeros(npairs, dtype=PAIRED_RESULT_DTYPE) if want_results else None
         f = getattr(self.lib, _fn)
-        f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 3
+        f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * (5 if _sorted else 3)
         while True:
             flag = np.zeros(n, np.int32); first = np.zeros(npairs, np.int32); line_begin = np.zeros(n + 1, np.uint64); text = np.zeros(tcap, np.uint8)
+            if _sorted:
+                key = np.zeros(n, np.uint64); perm = np.zeros(n, np.uint32)
             tb = C.c_uint64(0)
             rc = f(self.handle, npairs, ptr(bases), ptr(quals), ptr(offsets), ptr(front_clip), ptr(data_len), ptr(skip), 1 if use_m else 0, ptr(names), ptr(name_off),
                    ops_stride, ptr(results) if want_results else None, ptr(first_alt) if want_results else None, ptr(flag), ptr(first), tcap, ptr(text),
-                   ptr(line_begin), C.addressof(tb))
+                   ptr(line_begin), C.addressof(tb), *((ptr(key), ptr(perm)) if _sorted else ()))
             if rc == W_TEXT_TRUNCATED and grow:
                 tcap = int(tb.value)
                 continue
             if rc != W_TEXT_TRUNCATED:
                 self._check(rc, _fn)
             break
-        return dict(text=text, line_begin=line_begin, text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED, flag=flag, first_written=first,
-                    results=results, first_alt=first_alt)
+        d = dict(text=text, line_begin=line_begin, text_bytes=int(tb.value), truncated=rc == W_TEXT_TRUNCATED, flag=flag, first_written=first,
+                 results=results, first_alt=first_alt)
+        if _sorted:
+            d.update(key=key, perm=perm)
+        return d
 
     # ---- pair units -> the bytes of their BAM records (BAMFormat::writePairs) ----
     def bamRecordsPaired(self, bases, quals, offsets, names, name_off, flag, contig, pos, mapq, ops, n_ops, nm, rnext, pnext, tlen, first_written,
@@ -971,6 +1026,15 @@ class ChimericPairedEndAligner(BaseAligner):
         dict(bytes, block_begin uint64[2 n_pairs + 1], bam_bytes, truncated, flag, first_written, results, first_alt)."""
         return self._as_bam(self.alignSamTextPaired(bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m=use_m, ops_stride=ops_stride,
                                                     text_capacity=byte_capacity, grow=grow, want_results=want_results, _fn="snapgpu_align_sam_paired_bam"))
+
+    def alignSamBamSortedPaired(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
+                                byte_capacity: int | None = None, grow: bool = True, want_results: bool = False):
+        """alignSamBamPaired with the sort behind it on the device (snapgpu_align_sam_paired_bam_sorted): bytes / block_begin in coordinate
+        order (every record on its own, so mates separate), flag / first_written / results in record order.  Returns alignSamBamPaired's dict
+        plus key uint64[2 n_pairs] and perm uint32[2 n_pairs]."""
+        return self._as_bam(self.alignSamTextPaired(bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m=use_m, ops_stride=ops_stride,
+                                                    text_capacity=byte_capacity, grow=grow, want_results=want_results,
+                                                    _fn="snapgpu_align_sam_paired_bam_sorted", _sorted=True))
 
     def alignSamBgzfPaired(self, bases, quals, offsets, front_clip, data_len, skip, names, name_off, use_m: bool = False, ops_stride: int = 64,
                            block_input: int = 0xff00, bgzf_capacity: int | None = None, member_capacity: int | None = None, grow: bool = True,

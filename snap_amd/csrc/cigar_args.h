@@ -153,6 +153,29 @@ struct BgzfArgs {
     SamTextSummary *summary;                                                     // total: bytes all members need; written: end of the last member below cap
 };
 extern "C" void snapgpu_launch_bgzf(const BgzfArgs *a, uint32_t deflate_blocks, uint32_t scan_blocks, uint32_t place_blocks, hipStream_t s);
+// snapgpu_bam_sort*: the BAM records of a batch into coordinate order (bam_sort.h).  Record i is bytes[block_begin[i] .. block_begin[i + 1]).
+#define BAMSORT_DECREASING 1u       // block_begin[i + 1] < block_begin[i], or a record that ends behind block_begin[n]
+#define BAMSORT_SHORT 2u            // a record shorter than 12 bytes: it has no refID and pos words
+#define BAMSORT_LONG 4u             // a record of 4 GB or more
+struct BamSortSummary {
+    uint32_t ones_lo, ones_hi, zeros_lo, zeros_hi;                               // the bits that are 1 in some key, and those that are 0 in some key
+    uint32_t flags, first_bad[3];                                                // BAMSORT_*; per flag (DECREASING, SHORT, LONG): ~ the first record that raised it
+};
+struct BamSortArgs {
+    uint32_t n, n_chunks;                                                        // n records, in tiles of SAMREC_CHUNK
+    const uint8_t *bytes; const uint64_t *block_begin;                           // [block_begin[n]], [n + 1]
+    uint64_t *key; uint32_t *index;                                              // [n] each, the key pass: key[i], index[i] = i
+    BamSortSummary *summary;
+    const uint32_t *perm;                                                        // [n] sorted: the record at place r
+    uint32_t *len; uint64_t *partial;                                            // [n + 1] the sorted records' lengths, [n_chunks] their tile sums
+    uint8_t *sorted; uint64_t *sorted_begin;                                     // [block_begin[n]], [n + 1]
+    SamTextSummary *scan_summary;                                                // (what sam_text.h's scan kernels fill)
+};
+extern "C" void snapgpu_launch_bam_sort_keys(const BamSortArgs *a, uint32_t blocks, hipStream_t s);
+// one pass over the 6 bits at `shift`: hist [64 * n_tiles], partial [64 * n_tiles / 1024 + 1], total [1]
+extern "C" void snapgpu_launch_bam_sort_pass(const uint64_t *keys_in, const uint32_t *vals_in, uint32_t n, uint32_t shift, uint32_t *hist, uint32_t *partial,
+                                             uint32_t *total, uint64_t *keys_out, uint32_t *vals_out, uint32_t blocks, hipStream_t s);
+extern "C" void snapgpu_launch_bam_sort_gather(const BamSortArgs *a, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_count(const SamRecArgs *a, uint32_t blocks, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_gather(const SamRecArgs *a, uint32_t m, hipStream_t s);
 extern "C" void snapgpu_launch_samrec_list(const SamRecArgs *a, uint32_t blocks, hipStream_t s);

@@ -13,6 +13,7 @@
 #include "sam_records.h"
 #include "sam_text.h"
 #include "sam_bam.h"
+#include "bam_sort.h"
 #include "bgzf.h"
 
 __global__ __launch_bounds__(256) void k_cigar_lv(CigarArgs a)
@@ -560,6 +561,35 @@ extern "C" void snapgpu_launch_sam_bam(const SamBamArgs *a, int paired, uint32_t
     hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, base);
     if (paired) hipLaunchKernelGGL(k_sambam_pair_write, dim3(write_blocks), dim3(256), 0, s, *a);
     else hipLaunchKernelGGL(k_sambam_write, dim3(write_blocks), dim3(256), 0, s, *a);
+}
+
+// ---- BAM records -> coordinate order (bam_sort.h): the keys; one radix pass (histogram, its scan, the stable scatter); the sorted offsets by
+// sam_text.h's scan (everything fits: cap is the whole 64-bit range) and the gather ---
+extern "C" void snapgpu_launch_bam_sort_keys(const BamSortArgs *a, uint32_t blocks, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_bamsort_keys, dim3(blocks), dim3(256), 0, s, *a);
+}
+extern "C" void snapgpu_launch_bam_sort_pass(const uint64_t *keys_in, const uint32_t *vals_in, uint32_t n, uint32_t shift, uint32_t *hist, uint32_t *partial,
+                                             uint32_t *total, uint64_t *keys_out, uint32_t *vals_out, uint32_t blocks, hipStream_t s)
+{
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)n + IB_TILE - 1) / IB_TILE);
+    const uint64_t n_hist = (uint64_t)64 * n_tiles;
+    const uint32_t n_chunks = (uint32_t)((n_hist + IB_TILE - 1) / IB_TILE);
+    hipLaunchKernelGGL(k_bamsort_hist, dim3(blocks), dim3(256), 0, s, keys_in, (uint64_t)n, shift, hist, n_tiles);
+    hipLaunchKernelGGL(k_bamsort_scan_sums, dim3(blocks), dim3(256), 0, s, (const uint32_t *)hist, n_hist, partial, n_chunks);
+    hipLaunchKernelGGL(k_bamsort_scan_partials, dim3(1), dim3(64), 0, s, partial, n_chunks, total);
+    hipLaunchKernelGGL(k_bamsort_scan_apply, dim3(blocks), dim3(256), 0, s, (const uint32_t *)hist, n_hist, (const uint32_t *)partial, n_chunks, hist);
+    hipLaunchKernelGGL(k_bamsort_scatter, dim3(blocks), dim3(256), 0, s, keys_in, vals_in, (uint64_t)n, shift, (const uint32_t *)hist, n_tiles, keys_out, vals_out);
+}
+extern "C" void snapgpu_launch_bam_sort_gather(const BamSortArgs *a, uint32_t scan_blocks, uint32_t write_blocks, hipStream_t s)
+{
+    SamTextArgs scan{};
+    scan.n = a->n; scan.n_chunks = a->n_chunks; scan.len = a->len; scan.partial = a->partial;
+    scan.line_begin = a->sorted_begin; scan.cap = ~0ull; scan.summary = a->scan_summary;
+    hipLaunchKernelGGL(k_bamsort_len, dim3(scan_blocks), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_samtext_partials, dim3(1), dim3(64), 0, s, scan);
+    hipLaunchKernelGGL(k_samtext_begins, dim3(scan_blocks), dim3(256), 0, s, scan);
+    hipLaunchKernelGGL(k_bamsort_gather, dim3(write_blocks), dim3(256), 0, s, *a);
 }
 
 // ---- bytes -> BGZF blocks (bgzf.h): every member into its slot, sam_text.h's scan over the sizes, the members that fit the capacity into place ---

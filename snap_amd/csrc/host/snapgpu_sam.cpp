@@ -31,6 +31,7 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <queue>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -47,7 +48,7 @@
 
 // The output is written to "<out>.partial" and renamed when it is complete, so that a run that stops half way (an input error, one of the
 // unsupported paired -om corners below) never leaves a truncated SAM -- or a BAM without its end-of-file block -- under the name asked for.
-static std::string g_partial_path;
+static std::string g_partial_path, g_sort_tmp_path;      // what die() removes: the unfinished output, and -so's spill file once it exists
 // where the host threads' time goes (SNAPGPU_SAM_VERBOSE=1 prints it): nanoseconds summed over the threads of a kind
 static std::atomic<unsigned long long> g_ns_prep(0), g_ns_align(0), g_ns_mid(0), g_ns_samcall(0), g_ns_format(0), g_ns_write(0), g_ns_parse(0);
 static std::atomic<unsigned long long> g_ns_wait_in(0), g_ns_wait_out(0), g_ns_wait_writer(0);      // feeders waiting for parsed batches / for room behind them; the writer waiting for the next batch in order
@@ -63,6 +64,7 @@ struct StageLap {                            // consecutive stages of one thread
 static void die(const char *msg, const char *arg = "") {
     fprintf(stderr, "snapgpu-sam: %s%s\n", msg, arg);
     if (!g_partial_path.empty()) remove(g_partial_path.c_str());
+    if (!g_sort_tmp_path.empty()) remove(g_sort_tmp_path.c_str());
     exit(1);
 }
 
@@ -272,6 +274,7 @@ struct Options {
     int passes = 1;                                                        // -passes N (measurement): stream the input N times over the resident index
     uint32_t ops_stride = 64;
     bool bam = false;                                                      // -o x.bam: BAM records in BGZF blocks (SNAPLib/Bam.cpp)
+    bool sorted = false; double sort_gb = 16.0;                            // -so: a coordinate-sorted BAM file (sorted runs, merged at the end); -sm: GB of runs held in memory before they spill
     bool verbose = false, host_loop = false;                               // SNAPGPU_SAM_VERBOSE; SNAPGPU_SAM_HOST_LOOP (tests: every record of a multi-result paired batch through the host loop)
     // The path a batch takes, chosen once (choose_paths) from the mode, the output kind, the options and five switches in the environment.
     // Every path writes the same file (BGZF: the same members with other compressed payloads); the opt-in ones are off until they have been
@@ -290,6 +293,8 @@ struct Options {
     //   paired, no -om              `paired_one_call` (snapgpu_align_sam_paired) unless SNAPGPU_SAM_PAIRED_FUSED=0, a measurement knob (unset: on);
     //                               off, or with a first-ALT pair: snapgpu_align_paired + snapgpu_sam_fields_paired
     //   paired, -om                 snapgpu_align_paired_secondary, then the records of each pair in rounds (PairedBatch::rounds)
+    //   -so (BAM only): DeviceBam without a switch where the table has a device path, through the `_bam_sorted` calls, so that a batch comes down as
+    //   a sorted run with its keys; every other batch is formatted on the host and sorted by snapgpu_bam_sort (sort_run); no batch is compressed on its own.
     //   `need_bam_ids`: BAM output with either BAM switch (paired -om too): the contexts get the contigs' BAM reference numbers.
     enum Output { HostFormat, DeviceText, DeviceBam, DeviceBgzf };
     struct Paths { Output output = HostFormat; bool single_one_call = false, single_records_call = false, paired_one_call = false, need_bam_ids = false, gather_for_aligner = false; } paths;
@@ -327,6 +332,8 @@ struct Work {                                // a batch on its way through the p
     uint32_t max_len = 0;                    // the longest read of the batch (unclipped): picks the context's read-length class
     std::string text;                        // the formatted records (BAM: BGZF blocks)
     bool text_done = false;                  // the feeder left the SAM lines in `text` (SNAPGPU_SAM_DEVICE_TEXT): nothing for the formatter to do
+    std::vector<uint64_t> keys;              // -so: the keys of the records of `text`, which are in key order once sort_done
+    bool sort_done = false;
     bool bgzf_done = false;                  // ... and `text` holds the batch's BGZF blocks already (SNAPGPU_SAM_DEVICE_BGZF): nothing to compress either
     bool bam = false;
     unsigned long long mapped = 0;
@@ -336,7 +343,7 @@ struct Work {                                // a batch on its way through the p
         rec_read.clear(); rec_secondary.clear(); rec.clear(); srec.clear(); rnext.clear(); first_written.clear(); pnext.clear(); tlen.clear();
         emit.clear(); pu_pair.clear(); pu_secondary.clear(); su_read.clear();
         prepared = false; front_clip.clear(); data_len.clear(); to_align.clear(); ab.clear(); aq.clear(); ao.clear(); skip.clear();
-        max_len = 0; text.clear(); text_done = false; bgzf_done = false; bam = false; mapped = 0;
+        max_len = 0; text.clear(); text_done = false; bgzf_done = false; bam = false; mapped = 0; keys.clear(); sort_done = false;
     }
 };
 
@@ -380,7 +387,7 @@ static char complement(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == '
 static inline void put_uint(std::string &o, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) o.push_back(t[--n]); }
 static inline void put_int(std::string &o, long long v) { if (v < 0) { o.push_back('-'); put_uint(o, (unsigned long long)(-(v + 1)) + 1ull); } else put_uint(o, (unsigned long long)v); }
 
-static void fail_rc(snapgpu_ctx *ctx, const char *what, int rc) { fprintf(stderr, "snapgpu-sam: %s failed (%d): %s\n", what, rc, snapgpu_last_error(ctx)); exit(1); }
+static void fail_rc(snapgpu_ctx *ctx, const char *what, int rc) { fprintf(stderr, "snapgpu-sam: %s failed (%d): %s\n", what, rc, snapgpu_last_error(ctx)); if (!g_sort_tmp_path.empty()) remove(g_sort_tmp_path.c_str()); exit(1); }
 
 // Read::clip and the useless-read test for read i of the batch (Read.h:586-608: back first, then front; SingleAligner.cpp:211-232)
 static inline bool clip_read(const Options &o, const Batch &b, size_t i, int32_t &front_clip, int32_t &data_len)
@@ -588,8 +595,8 @@ static bool env_switch(const char *name, bool unset) { const char *e = getenv(na
 static void choose_paths(Options &o)
 {
     Options::Paths &p = o.paths;
-    const bool text = env_switch("SNAPGPU_SAM_DEVICE_TEXT", false), bgzf = env_switch("SNAPGPU_SAM_DEVICE_BGZF", false), bam = env_switch("SNAPGPU_SAM_DEVICE_BAM", false) || bgzf;
-    if (!(o.paired && o.om >= 0)) p.output = o.bam ? (bgzf ? Options::DeviceBgzf : bam ? Options::DeviceBam : Options::HostFormat) : (text ? Options::DeviceText : Options::HostFormat);
+    const bool text = env_switch("SNAPGPU_SAM_DEVICE_TEXT", false), bgzf = env_switch("SNAPGPU_SAM_DEVICE_BGZF", false), bam = env_switch("SNAPGPU_SAM_DEVICE_BAM", false) || bgzf || o.sorted;
+    if (!(o.paired && o.om >= 0)) p.output = o.bam ? (bgzf && !o.sorted ? Options::DeviceBgzf : bam ? Options::DeviceBam : Options::HostFormat) : (text ? Options::DeviceText : Options::HostFormat);
     p.need_bam_ids = o.bam && bam;
     p.single_records_call = !o.paired && env_switch("SNAPGPU_SAM_SINGLE_FUSED", false) && (o.om >= 0 || o.ae || o.p.emit_alt_alignments != 0);
     p.paired_one_call = o.paired && o.om < 0 && env_switch("SNAPGPU_SAM_PAIRED_FUSED", true);
@@ -692,7 +699,7 @@ static bool device_output(const Options &o, snapgpu_ctx *ctx, Work &w, const cha
         if (rc != SNAPGPU_OK) fail_rc(ctx, (std::string(stem) + (bgzf ? "_bgzf" : o.bam ? "_bam" : "_text")).c_str(), rc);
         break;
     }
-    if (discard()) { w.text.clear(); return false; }
+    if (discard()) { w.text.clear(); w.sort_done = false; return false; }
     const size_t nr = (size_t)c.n_rec;
     if (o.bam) { g_bam_batches++; g_bam_records += nr; }
     if (!fixed_records) records_needed(nr, n);
@@ -720,6 +727,12 @@ static void gpu_single_text(const Options &o, FeederCtx &fc, Work &w)
                                             w.skip.data(), use_m, adjust_primary, b.names.data(), name_off.data(), c.ops_stride,
                                             c.rec_cap, &c.n_rec, rec_begin.data(), w.rec.flag.data(), 0xff00, c.bgzf_cap, (uint8_t *)&w.text[0], c.begin,
                                             c.max_members, &c.n_members, &c.bgzf_bytes, &c.text_bytes)
+            : o.sorted
+            ? (w.keys.resize((size_t)c.rec_cap), w.sort_done = true,
+               snapgpu_align_sam_single_bam_sorted(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
+                                                   w.skip.data(), use_m, adjust_primary, b.names.data(), name_off.data(), c.ops_stride,
+                                                   c.rec_cap, &c.n_rec, rec_begin.data(), w.rec.flag.data(), c.text_cap, (uint8_t *)&w.text[0], c.begin, &c.text_bytes,
+                                                   w.keys.data(), NULL))
             : o.paths.output == Options::DeviceBam
             ? snapgpu_align_sam_single_bam(ctx, (uint32_t)n, b.bases.data(), b.quals.data(), b.offsets.data(), w.front_clip.data(), w.data_len.data(),
                                            w.skip.data(), use_m, adjust_primary, b.names.data(), name_off.data(), c.ops_stride,
@@ -1056,6 +1069,11 @@ struct PairedBatch {
                     ? snapgpu_align_sam_paired_bgzf(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
                                                     skip.data(), use_m, b.names.data(), name_off.data(), c.ops_stride, res, alt, w.rec.flag.data(), w.first_written.data(),
                                                     0xff00, c.bgzf_cap, (uint8_t *)&w.text[0], c.begin, c.max_members, &c.n_members, &c.bgzf_bytes, &c.text_bytes)
+                    : o.sorted
+                    ? (w.keys.resize(nrec), w.sort_done = true,
+                       snapgpu_align_sam_paired_bam_sorted(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
+                                                           skip.data(), use_m, b.names.data(), name_off.data(), c.ops_stride, res, alt, w.rec.flag.data(), w.first_written.data(),
+                                                           c.text_cap, (uint8_t *)&w.text[0], c.begin, &c.text_bytes, w.keys.data(), NULL))
                     : o.paths.output == Options::DeviceBam
                     ? snapgpu_align_sam_paired_bam(ctx, (uint32_t)np, b.bases.data(), b.quals.data(), b.offsets.data(), front_clip.data(), data_len.data(),
                                                    skip.data(), use_m, b.names.data(), name_off.data(), c.ops_stride, res, alt, w.rec.flag.data(), w.first_written.data(),
@@ -1493,12 +1511,98 @@ static void format_paired(const std::vector<Contig> &contigs, Work &w)
 }
 
 // ---------------------------------------------------------------------------------------- main
+// ---------------------------------------------------------------------------------------- -so: sorted runs and their merge
+// Every batch becomes one run: its BAM records in key order (snap_amd/csrc/bam_sort.h: key = (uint32) refID << 32 | (uint32)(pos + 1), ties in
+// input order) and their keys.  Runs are kept in batch order; a run that would take the bytes held in memory past -sm goes uncompressed to
+// <out>.sort.tmp (its keys, 8 bytes a record, stay) and is read back in pieces.  The merge takes the smallest (key, run number), so a tie goes to
+// the lower batch: the file is the stable sort of the input-order record stream whatever -gpus, -q, -t or -b are.
+static inline uint32_t get_le32(const char *p) { return (uint32_t)(unsigned char)p[0] | ((uint32_t)(unsigned char)p[1] << 8) | ((uint32_t)(unsigned char)p[2] << 16) | ((uint32_t)(unsigned char)p[3] << 24); }
+// a batch that did not come down sorted: its records through snapgpu_bam_sort on the context the formatter threads share
+static void sort_run(snapgpu_ctx *ctx, std::mutex &m, Work &w)
+{
+    std::vector<uint64_t> bb(1, 0);
+    for (size_t at = 0; at < w.text.size();) {
+        if (w.text.size() - at < 4) die("internal error: a BAM record is cut short");
+        at += 4 + (size_t)get_le32(w.text.data() + at);
+        if (at > w.text.size()) die("internal error: a BAM record is cut short");
+        bb.push_back(at);
+    }
+    const size_t n = bb.size() - 1;
+    std::string sorted(w.text.size(), '\0');
+    std::vector<uint64_t> sb(n + 1);
+    w.keys.assign(n, 0);
+    if (n) {
+        std::lock_guard<std::mutex> l(m);
+        const int rc = snapgpu_bam_sort(ctx, n, (const uint8_t *)w.text.data(), bb.data(), (uint8_t *)&sorted[0], sb.data(), w.keys.data(), NULL);
+        if (rc != SNAPGPU_OK) fail_rc(ctx, "snapgpu_bam_sort", rc);
+    }
+    w.text.swap(sorted); w.sort_done = true;
+}
+struct SortRun {
+    std::string bytes; std::vector<uint64_t> keys; uint64_t n_bytes = 0, file_at = 0; bool spilled = false;
+    // the merge's cursor
+    size_t next = 0; uint64_t at = 0; std::vector<char> piece; uint64_t piece_at = 0;
+};
+struct SortRuns {
+    std::vector<SortRun> runs; uint64_t held = 0, limit = 0, tmp_bytes = 0, n_spilled = 0, n_records = 0;
+    std::string tmp_path; FILE *tmp = NULL;
+    void add(Work &w) {
+        runs.emplace_back();
+        SortRun &r = runs.back();
+        size_t n = 0;
+        for (size_t at = 0; at < w.text.size(); n++) at += 4 + (size_t)get_le32(w.text.data() + at);
+        if (w.keys.size() < n) die("internal error: a sorted run has fewer keys than records");
+        r.keys.assign(w.keys.begin(), w.keys.begin() + (ptrdiff_t)n); r.n_bytes = w.text.size(); n_records += n;
+        if (held + r.n_bytes > limit) {
+            if (!tmp) { if (!(tmp = fopen(tmp_path.c_str(), "w+b"))) die("cannot create ", tmp_path.c_str()); g_sort_tmp_path = tmp_path; }
+            if (fseeko(tmp, (off_t)tmp_bytes, SEEK_SET) != 0 || fwrite(w.text.data(), 1, w.text.size(), tmp) != w.text.size()) die("write error on ", tmp_path.c_str());
+            r.spilled = true; r.file_at = tmp_bytes; tmp_bytes += r.n_bytes; n_spilled++;
+        } else { r.bytes.swap(w.text); held += r.n_bytes; }                      // (the batch goes back to the pool next: its buffer stays with the run)
+    }
+    // the next record of run r: where it is and how long
+    const char *record(SortRun &r, size_t &len) {
+        if (!r.spilled) { len = 4 + (size_t)get_le32(r.bytes.data() + r.at); return r.bytes.data() + r.at; }
+        auto have = [&](uint64_t need) { return r.at >= r.piece_at && r.at + need <= r.piece_at + r.piece.size(); };
+        auto fill = [&](uint64_t need) {
+            const uint64_t PIECE = 1u << 20, left = r.n_bytes - r.at, want = need > PIECE ? need : PIECE;
+            r.piece.resize((size_t)(want < left ? want : left)); r.piece_at = r.at;
+            if (fseeko(tmp, (off_t)(r.file_at + r.at), SEEK_SET) != 0 || fread(r.piece.data(), 1, r.piece.size(), tmp) != r.piece.size()) die("read error on ", tmp_path.c_str());
+        };
+        if (!have(4)) fill(4);
+        len = 4 + (size_t)get_le32(r.piece.data() + (r.at - r.piece_at));
+        if (!have(len)) fill(len);
+        return r.piece.data() + (r.at - r.piece_at);
+    }
+    // the k-way merge; emit(data, n) takes the merged stream in pieces that are multiples of 0xff00 bytes but for the last
+    template <class Emit> void merge(Emit emit) {
+        if (tmp) fflush(tmp);
+        typedef std::pair<uint64_t, size_t> Head;                        // (key, run): the smaller run number wins a tie
+        std::priority_queue<Head, std::vector<Head>, std::greater<Head>> heap;
+        for (size_t i = 0; i < runs.size(); i++) if (!runs[i].keys.empty()) heap.push(Head(runs[i].keys[0], i));
+        const size_t FLUSH = 64 * (size_t)0xff00;
+        std::string buf; buf.reserve(FLUSH + (1u << 16));
+        while (!heap.empty()) {
+            const size_t i = heap.top().second; heap.pop();
+            SortRun &r = runs[i];
+            size_t len = 0;
+            const char *p = record(r, len);
+            buf.append(p, len);
+            r.at += len; r.next++;
+            if (r.next < r.keys.size()) heap.push(Head(r.keys[r.next], i));
+            else { std::string().swap(r.bytes); std::vector<char>().swap(r.piece); }
+            if (buf.size() >= FLUSH) { const size_t k = buf.size() / 0xff00 * 0xff00; emit(buf.data(), k); buf.erase(0, k); }
+        }
+        if (!buf.empty()) emit(buf.data(), buf.size());
+    }
+    void finish() { if (tmp) { fclose(tmp); tmp = NULL; (void)unlink(tmp_path.c_str()); g_sort_tmp_path.clear(); } }
+};
+
 int main(int argc, char **argv)
 {
     Options o;
     o.paired = argc >= 2 && strcmp(argv[1], "paired") == 0;
     if (argc < (o.paired ? 5 : 4) || (!o.paired && strcmp(argv[1], "single") != 0))
-        die("usage: snapgpu-sam single <index-dir> <reads.fq> -o <out.sam|out.bam> | paired <index-dir> <r1.fq> <r2.fq> -o <out.sam|out.bam>  [-d N] [-G-] [-=] [-M] [-om N] [-omax N] [-mpc N] [-ae] [-ea] [-mrl N] [-b N] [-gpus N] [-q N] [-t N]");
+        die("usage: snapgpu-sam single <index-dir> <reads.fq> -o <out.sam|out.bam> | paired <index-dir> <r1.fq> <r2.fq> -o <out.sam|out.bam>  [-d N] [-G-] [-=] [-M] [-om N] [-omax N] [-mpc N] [-ae] [-ea] [-mrl N] [-b N] [-gpus N] [-q N] [-t N] [-so [-sm GB]]");
     const std::string index_dir = argv[2], fastq = argv[3], fastq2 = o.paired ? argv[4] : "";
     std::string out_path;
     snapgpu_default_params(&o.p);
@@ -1529,6 +1633,8 @@ int main(int argc, char **argv)
         else if (a == "-q" && i + 1 < argc) o.ctx_per_gpu = atoi(argv[++i]);
         else if (a == "-t" && i + 1 < argc) o.n_format = atoi(argv[++i]);  // host threads that format records (the reference's -t counts aligner threads)
         else if (a == "-tp" && i + 1 < argc) o.n_parse = atoi(argv[++i]);  // host threads that parse a plain FASTQ file
+        else if (a == "-so") o.sorted = true;                                                // AlignerOptions.cpp: sort the output by coordinate
+        else if (a == "-sm" && i + 1 < argc) o.sort_gb = atof(argv[++i]);                  // GB of sorted runs held in memory (the reference's -sm sizes its sort buffers)
         else if (a == "-seqread") o.seqread = true;
         else if (a == "-passes" && i + 1 < argc) o.passes = atoi(argv[++i]);   // (measurement: the whole FASTQ -> SAM stream N times over the resident index; the output is the last pass's)
         else die("option not supported: ", a.c_str());
@@ -1537,6 +1643,8 @@ int main(int argc, char **argv)
     if (o.ae && o.paired) die("-ae is implemented for `single` only (the paired-end aligners' use of AlignmentAdjuster is not: DESIGN.md section 16)");
     if (o.ae && o.clip_front) die("-ae with front clipping (-C+x) is not supported: the adjuster is restated for reads the reader has not clipped at the front");
     o.bam = out_path.size() > 4 && out_path.compare(out_path.size() - 4, 4, ".bam") == 0;     // by extension, like the reference (AlignerOptions.cpp)
+    if (o.sorted && !o.bam) die("-so writes a coordinate-sorted BAM file: -o must end in .bam (sorted SAM text is not implemented)");
+    if (o.sorted && !(o.sort_gb >= 0 && o.sort_gb <= 1048576.0)) die("-sm must be between 0 and 1048576 (GB)");
     choose_paths(o);
     const bool batch_auto = o.batch_reads == 0;
     if (batch_auto) o.batch_reads = 262144;                                // (the mapped reader, which knows the file's size, picks below)
@@ -1578,6 +1686,10 @@ int main(int argc, char **argv)
         rc = snapgpu_broadcast_index(primary.data(), o.n_gpus);
         if (rc != SNAPGPU_OK) fail_rc(primary[0], "snapgpu_broadcast_index", rc);
     }
+    // -so: the formatter threads' snapgpu_bam_sort calls and the merge's snapgpu_bgzf_compress run on GPU 0's first context, which its first feeder
+    // uses too: calls on a context are serial, so that feeder holds sort_m while it works (a context of their own does not fit beside the
+    // feeders' secondary-result pools of a paired -om run)
+    snapgpu_ctx *sort_ctx = o.sorted ? primary[0] : NULL; std::mutex sort_m;
     std::vector<FeederCtx> fctx;                                            // one per feeder thread
     for (int g = 0; g < o.n_gpus; g++) {
         for (int k = 0; k < o.ctx_per_gpu; k++) {
@@ -1591,6 +1703,8 @@ int main(int argc, char **argv)
             fctx.push_back(f);
         }
     }
+    const bool merge_on_device = o.sorted && env_switch("SNAPGPU_SAM_DEVICE_BGZF", false);
+    unsigned long long sort_runs = 0, sort_records = 0, sort_spilled = 0; double s_merge = 0.0;
     // host threads: formatting a record is ~1 us of text work, so one GPU's ~5 M records/s want a few dozen formatters (the cap of 16 of
     // rounds 2-3 was the pipeline's bottleneck on a 256-thread host); parsers likewise
     { const unsigned hc = std::thread::hardware_concurrency() ? std::thread::hardware_concurrency() : 8;
@@ -1618,7 +1732,7 @@ int main(int argc, char **argv)
     // (FASTA.cpp:359-384), the header keeps the FASTA's order (getContigByOriginalContigNumber, SAM.cpp:1291)
     // The BAM header is the same text inside the binary header, followed by the contig table in the same (original) order (Bam.cpp:970-1031).
     {
-        std::string text = "@HD\tVN:1.6\tGO:query\n@RG\tID:FASTQ\tPL:Illumina\tPU:pu\tLB:lb\tSM:sm\n@PG\tID:SNAP\tPN:SNAP\tCL:" + cl + "\tVN:2.0.5\n";
+        std::string text = std::string("@HD\tVN:1.6\t") + (o.sorted ? "SO:coordinate" : "GO:query") + "\n@RG\tID:FASTQ\tPL:Illumina\tPU:pu\tLB:lb\tSM:sm\n@PG\tID:SNAP\tPN:SNAP\tCL:" + cl + "\tVN:2.0.5\n";
         std::string refs;
         std::vector<size_t> by_orig(contigs.size());
         bool perm = true;
@@ -1729,13 +1843,16 @@ int main(int argc, char **argv)
         feeders.emplace_back([&, t] {
             if (o.paired) {
                 Work *w;
-                while (q_parsed.pop(w)) { gpu_paired(o, fctx[t], *w); q_aligned.push(w); }
+                while (q_parsed.pop(w)) {
+                    { std::unique_lock<std::mutex> hold(sort_m, std::defer_lock); if (o.sorted && t == 0) hold.lock(); gpu_paired(o, fctx[t], *w); }
+                    q_aligned.push(w);
+                }
             } else {
                 GroupBuf gb; std::vector<Work *> ws;
                 for (;;) {
                     ws.clear();
                     { StageTimer st(g_ns_wait_in); if (q_parsed.pop_upto(ws, group, std::chrono::milliseconds(20)) == 0) break; }
-                    gpu_single_group(o, fctx[t], ws, gb);
+                    { std::unique_lock<std::mutex> hold(sort_m, std::defer_lock); if (o.sorted && t == 0) hold.lock(); gpu_single_group(o, fctx[t], ws, gb); }
                     { StageTimer st(g_ns_wait_out); for (Work *w : ws) q_aligned.push(w); }
                 }
             }
@@ -1746,10 +1863,12 @@ int main(int argc, char **argv)
             Work *w;
             while (q_aligned.pop(w)) {
                 if (!w->text_done) { StageTimer st(g_ns_format); if (o.paired) format_paired(contigs, *w); else format_single(contigs, *w); }
-                if (o.bam && !w->bgzf_done) { std::string z; z.reserve(w->text.size() / 3 + 64); bgzf_append(z, w->text.data(), w->text.size()); w->text.swap(z); }
+                if (o.sorted) { if (!w->sort_done) sort_run(sort_ctx, sort_m, *w); }
+                else if (o.bam && !w->bgzf_done) { std::string z; z.reserve(w->text.size() / 3 + 64); bgzf_append(z, w->text.data(), w->text.size()); w->text.swap(z); }
                 std::lock_guard<std::mutex> l(done_m); done[w->b.seq] = w; done_cv.notify_all();
             }
         });
+    SortRuns sr; sr.limit = (uint64_t)(o.sort_gb * 1073741824.0); sr.tmp_path = out_path + ".sort.tmp";
     const auto t_pipe = std::chrono::steady_clock::now();
     double t_first_s = -1.0;
     for (uint64_t next = 0;; next++) {                                      // the writer: batches in input order
@@ -1761,7 +1880,8 @@ int main(int argc, char **argv)
             if (!done.count(next)) break;
             w = done[next]; done.erase(next);
         }
-        { StageTimer st(g_ns_write); if (fwrite(w->text.data(), 1, w->text.size(), out) != w->text.size()) die("write error on ", out_path.c_str()); }
+        if (o.sorted) { StageTimer st(g_ns_write); sr.add(*w); }
+        else { StageTimer st(g_ns_write); if (fwrite(w->text.data(), 1, w->text.size(), out) != w->text.size()) die("write error on ", out_path.c_str()); }
         if (t_first_s < 0) t_first_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ready).count();
         total += w->b.n(); mapped += w->mapped;
         pool.put(w);
@@ -1773,6 +1893,24 @@ int main(int argc, char **argv)
     for (auto &t : feeders) t.join();
     for (auto &t : formatters) t.join();
     const auto t_joined = std::chrono::steady_clock::now();
+    if (o.sorted) {                                                          // the merged stream through BGZF: zlib, or the device's coder under SNAPGPU_SAM_DEVICE_BGZF=1
+        std::string z; std::vector<uint64_t> member_begin;
+        sr.merge([&](const char *data, size_t n) {
+            z.clear();
+            if (merge_on_device) {
+                const uint64_t nm = (n + 0xff00 - 1) / 0xff00;
+                z.resize((size_t)nm * (0xff00 + 31)); member_begin.resize((size_t)nm + 1);
+                uint64_t n_members = 0, out_bytes = 0;
+                const int zrc = snapgpu_bgzf_compress(sort_ctx, n, (const uint8_t *)data, 0xff00, z.size(), (uint8_t *)&z[0], member_begin.data(), &n_members, &out_bytes);
+                if (zrc != SNAPGPU_OK) fail_rc(sort_ctx, "snapgpu_bgzf_compress", zrc);
+                z.resize((size_t)out_bytes);
+            } else bgzf_append(z, data, n);
+            if (fwrite(z.data(), 1, z.size(), out) != z.size()) die("write error on ", out_path.c_str());
+        });
+        sr.finish();
+        sort_runs = sr.runs.size(); sort_records = sr.n_records; sort_spilled = sr.n_spilled;
+        s_merge = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_joined).count();
+    }
     if (o.bam) { std::string eof; bgzf_append(eof, "", 0); if (fwrite(eof.data(), 1, eof.size(), out) != eof.size()) die("write error on ", out_path.c_str()); }     // the empty end-of-file block
     if (fclose(out) != 0) die("write error on ", out_path.c_str());
     if (rename(partial_path.c_str(), out_path.c_str()) != 0) die("cannot rename the finished output to ", out_path.c_str());
@@ -1796,6 +1934,10 @@ int main(int argc, char **argv)
     fprintf(stderr, "snapgpu-sam: %llu reads, %llu mapped records, %d GPU(s) x %d feeder(s), %d formatter thread(s)\n", total, mapped, o.n_gpus, o.ctx_per_gpu, o.n_format);
     if (o.paths.output == Options::DeviceBam || o.paths.output == Options::DeviceBgzf)                     // (the last pass's, like the counts above)
         fprintf(stderr, "snapgpu-sam: BAM records from the device: %llu batches, %llu records\n", g_bam_batches.load(), g_bam_records.load());
+    if (o.sorted) {
+        fprintf(stderr, "snapgpu-sam: sorted on the device: %llu runs, %llu records, %llu spilled\n", sort_runs, sort_records, sort_spilled);
+        if (o.verbose) fprintf(stderr, "snapgpu-sam: merge phase (k-way merge, BGZF on the %s, write): %.3f s\n", merge_on_device ? "device" : "host", s_merge);
+    }
     if (o.paths.output == Options::DeviceBgzf)
         fprintf(stderr, "snapgpu-sam: BGZF blocks from the device: %llu batches, %llu blocks, %llu -> %llu bytes\n", g_bgzf_batches.load(), g_bgzf_members.load(),
                 g_bgzf_in.load(), g_bgzf_out.load());

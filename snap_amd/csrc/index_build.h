@@ -24,22 +24,9 @@
 #pragma once
 #include "dev_common.h"
 #include "probe.h"
+#include "radix_pass.h"              // IB_TILE, IB_BITS, IB_INVALID_KEY, the wave helpers, the pass and the scan (shared with bam_sort.h)
 
-#define IB_INVALID_KEY 0xFFFFFFFFFFFFFFFFull
-#define IB_TILE 1024u            // elements per wavefront tile: 16 rounds of 64
-#define IB_ROUNDS 16
-#define IB_BITS 6                // radix bits per pass: one bin per lane
 #define IB_EMPTY_SLOT 0x00000000FFFFFFFFull      // value = invalid (0xffffffff), key bytes cleared (HashTable.cpp:63-70)
-
-static __device__ __forceinline__ uint32_t ib_wave_id()  { return (uint32_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); }
-static __device__ __forceinline__ uint32_t ib_n_waves()  { return (uint32_t)((gridDim.x * blockDim.x) >> 6); }
-
-// inclusive prefix sum over the 64 lanes
-static __device__ __forceinline__ uint32_t ib_wave_incl_scan(uint32_t v) {
-    const int lane = lane_id();
-    for (int o = 1; o < WAVE; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)v, o); if (lane >= o) v += t; }
-    return v;
-}
 
 // ---------------------------------------------------------------- 1. seeds of all locations
 // keys[loc] = the seed at loc (first base most significant, A0 G1 C2 T3: Seed.h:48, Tables.cpp:52-58) or IB_INVALID_KEY when one of its
@@ -73,114 +60,28 @@ __global__ __launch_bounds__(256) void k_ib_keys(const uint8_t *genome, uint64_t
     }
 }
 
-// ---------------------------------------------------------------- 2. radix sort, one pass = histogram, scan, scatter
-// lanes with the same (valid) digit as this one
-static __device__ __forceinline__ uint64_t ib_peers(uint32_t d, bool valid) {
-    uint64_t p = BALLOT(valid);
-#pragma unroll
-    for (int b = 0; b < IB_BITS; b++) {
-        const bool bit = (d >> b) & 1u;
-        const uint64_t m = BALLOT(bit);
-        p &= bit ? m : ~m;
-    }
-    return valid ? p : 0ull;
-}
-
-// hist[bin * n_tiles + tile] = elements of the tile whose digit is bin (bin-major, so ONE exclusive scan over the whole array yields the
-// output offset of every (bin, tile)).  IB_INVALID_KEY elements are not counted: the first pass drops them.
+// ---------------------------------------------------------------- 2. radix sort, one pass = histogram, scan, scatter (radix_pass.h)
+// IB_INVALID_KEY elements are not counted and not scattered: the first pass drops them.  vals_in == NULL (first pass): the value of element i
+// is i, the genome location.
 __global__ __launch_bounds__(256) void k_ib_hist(const uint64_t *keys, uint64_t n, uint32_t shift, uint32_t *hist, uint32_t n_tiles)
 {
     static __shared__ uint32_t sh[4][64];
-    const int lane = lane_id();
-    uint32_t *h = sh[(threadIdx.x >> 6) & 3];
-    for (uint32_t tile = ib_wave_id(); tile < n_tiles; tile += ib_n_waves()) {
-        h[lane] = 0;
-        WAVE_SYNC();
-        for (int r = 0; r < IB_ROUNDS; r++) {
-            const uint64_t i = (uint64_t)tile * IB_TILE + (uint64_t)r * 64 + (uint64_t)lane;
-            const uint64_t key = i < n ? keys[i] : IB_INVALID_KEY;
-            const bool valid = key != IB_INVALID_KEY;
-            const uint32_t d = (uint32_t)(key >> shift) & 63u;
-            const uint64_t peers = ib_peers(d, valid);
-            if (valid && (peers & ((1ull << lane) - 1ull)) == 0) h[d] += (uint32_t)__popcll(peers);      // the lowest peer speaks for all
-            WAVE_SYNC();
-        }
-        hist[(size_t)lane * n_tiles + tile] = h[lane];
-        WAVE_SYNC();
-    }
+    ib_hist_body<true>(keys, n, shift, hist, n_tiles, sh[(threadIdx.x >> 6) & 3]);
 }
-
-// Stable scatter of one pass.  vals_in == NULL (first pass): the value of element i is i, the genome location.
 __global__ __launch_bounds__(256) void k_ib_scatter(const uint64_t *keys_in, const uint32_t *vals_in, uint64_t n, uint32_t shift,
                                                     const uint32_t *offs, uint32_t n_tiles, uint64_t *keys_out, uint32_t *vals_out)
 {
     static __shared__ uint32_t sh[4][64];
-    const int lane = lane_id();
-    uint32_t *run = sh[(threadIdx.x >> 6) & 3];
-    for (uint32_t tile = ib_wave_id(); tile < n_tiles; tile += ib_n_waves()) {
-        run[lane] = offs[(size_t)lane * n_tiles + tile];          // where the tile's elements of bin `lane` start in the output
-        WAVE_SYNC();
-        for (int r = 0; r < IB_ROUNDS; r++) {
-            const uint64_t i = (uint64_t)tile * IB_TILE + (uint64_t)r * 64 + (uint64_t)lane;
-            const uint64_t key = i < n ? keys_in[i] : IB_INVALID_KEY;
-            const bool valid = key != IB_INVALID_KEY;
-            const uint32_t val = valid ? (vals_in ? vals_in[i] : (uint32_t)i) : 0u;
-            const uint32_t d = (uint32_t)(key >> shift) & 63u;
-            const uint64_t peers = ib_peers(d, valid);
-            const uint64_t below = peers & ((1ull << lane) - 1ull);
-            const uint32_t base = valid ? run[d] : 0u;
-            WAVE_SYNC();
-            if (valid) {
-                const uint32_t pos = base + (uint32_t)__popcll(below);
-                keys_out[pos] = key; vals_out[pos] = val;
-                if (below == 0) run[d] = base + (uint32_t)__popcll(peers);
-            }
-            WAVE_SYNC();
-        }
-    }
+    ib_scatter_body<true>(keys_in, vals_in, n, shift, offs, n_tiles, keys_out, vals_out, sh[(threadIdx.x >> 6) & 3]);
 }
 
 // ---------------------------------------------------------------- exclusive scan of a u32 array (three kernels; chunk = 1024 per wave)
-__global__ __launch_bounds__(256) void k_ib_scan_sums(const uint32_t *in, uint64_t n, uint32_t *partial, uint32_t n_chunks)
-{
-    const int lane = lane_id();
-    for (uint32_t c = ib_wave_id(); c < n_chunks; c += ib_n_waves()) {
-        uint32_t s = 0;
-        for (int r = 0; r < IB_ROUNDS; r++) {
-            const uint64_t i = (uint64_t)c * IB_TILE + (uint64_t)r * 64 + (uint64_t)lane;
-            s += i < n ? in[i] : 0u;
-        }
-        s = ib_wave_incl_scan(s);
-        if (lane == 63) partial[c] = s;
-    }
-}
+__global__ __launch_bounds__(256) void k_ib_scan_sums(const uint32_t *in, uint64_t n, uint32_t *partial, uint32_t n_chunks) { ib_scan_sums_body(in, n, partial, n_chunks); }
 // one wavefront: partial[] -> its exclusive scan in place; total[0] = the sum
-__global__ __launch_bounds__(64) void k_ib_scan_partials(uint32_t *partial, uint32_t n_chunks, uint32_t *total)
-{
-    const int lane = lane_id();
-    uint32_t carry = 0;
-    for (uint32_t c0 = 0; c0 < n_chunks; c0 += 64) {
-        const uint32_t c = c0 + (uint32_t)lane;
-        const uint32_t v = c < n_chunks ? partial[c] : 0u;
-        const uint32_t inc = ib_wave_incl_scan(v);
-        if (c < n_chunks) partial[c] = carry + inc - v;
-        carry += (uint32_t)__shfl((int)inc, 63);
-    }
-    if (lane == 0) total[0] = carry;
-}
+__global__ __launch_bounds__(64) void k_ib_scan_partials(uint32_t *partial, uint32_t n_chunks, uint32_t *total) { ib_scan_partials_body(partial, n_chunks, total); }
 __global__ __launch_bounds__(256) void k_ib_scan_apply(const uint32_t *in, uint64_t n, const uint32_t *partial, uint32_t n_chunks, uint32_t *out)
 {
-    const int lane = lane_id();
-    for (uint32_t c = ib_wave_id(); c < n_chunks; c += ib_n_waves()) {
-        uint32_t carry = partial[c];
-        for (int r = 0; r < IB_ROUNDS; r++) {
-            const uint64_t i = (uint64_t)c * IB_TILE + (uint64_t)r * 64 + (uint64_t)lane;
-            const uint32_t v = i < n ? in[i] : 0u;
-            const uint32_t inc = ib_wave_incl_scan(v);
-            if (i < n) out[i] = carry + inc - v;
-            carry += (uint32_t)__shfl((int)inc, 63);
-        }
-    }
+    ib_scan_apply_body(in, n, partial, n_chunks, out);
 }
 
 // ---------------------------------------------------------------- 3. runs of equal seeds

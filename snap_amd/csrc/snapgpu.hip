@@ -36,6 +36,7 @@
 #include "cigar_ag.h"
 #include "cigar_args.h"
 #include "adjust.h"
+#include "radix_pass.h"          // IB_TILE, IB_BITS: the geometry of bam_sort_core's passes
 
 // =====================================================================================
 // kernels
@@ -2773,7 +2774,10 @@ struct SamTextIO {
 // library's own and their blocks go to z.  *total: the bytes of all the lines or records, written or not.
 enum SamOutKind { SAM_OUT_TEXT, SAM_OUT_BAM, SAM_OUT_BGZF };
 struct BgzfOut { uint32_t block_input; uint64_t cap; uint8_t *bgzf; uint64_t *member_begin; uint64_t member_capacity; uint64_t *n_members, *bgzf_bytes; };
-struct SamOut { SamOutKind kind; uint64_t cap; void *bytes, *begin; uint64_t *total; BgzfOut z; };
+// sort.on (SAM_OUT_BAM of the fused calls only): the records go into a buffer of the library's own like SAM_OUT_BGZF's, and `bytes` / `begin` take
+// them in coordinate order (bam_sort.h); key / perm: the sorted keys and the permutation, each NULL or [the records' count]
+struct BamSortOut { bool on; uint64_t *key; uint32_t *perm; };
+struct SamOut { SamOutKind kind; uint64_t cap; void *bytes, *begin; uint64_t *total; BgzfOut z; BamSortOut sort; };
 
 static int sam_text_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_records, uint32_t ops_stride, bool bam)
 {
@@ -2960,6 +2964,121 @@ extern "C" int snapgpu_bgzf_compress(snapgpu_ctx *ctx, uint64_t n_bytes, const u
     return sum.total > out_capacity ? SNAPGPU_W_TEXT_TRUNCATED : SNAPGPU_OK;
 }
 
+// ---- BAM records -> coordinate order (bam_sort.h): n > 0 records at d_bytes / d_block_begin, everything in HBM.  The key pass, ONE read-back (which
+// key bits vary over the batch, and whether the extents are sound: nothing is written to an output before that), an LSD pass for every 6-bit
+// digit that varies, the sorted offsets and the gather.  d_key / d_perm may be NULL.  The stream is synchronised when this returns.
+// the one text of each refusal of a record's extent (what: BAMSORT_*), for the key pass's findings and the host form's own loop
+static int bam_sort_refuse(snapgpu_ctx *ctx, const std::string &w, uint64_t record, uint32_t what)
+{
+    return fail(ctx, SNAPGPU_E_INVALID, w + ": record " + std::to_string(record) +
+                (what == BAMSORT_DECREASING ? ": block_begin must be non-decreasing" : what == BAMSORT_SHORT ? ": a BAM record is at least 12 bytes long (block_size, refID, pos)"
+                                                                                                               : ": a BAM record is shorter than 4 GB"));
+}
+static int bam_sort_core(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t n_records, const void *d_bytes, const void *d_block_begin,
+                         void *d_sorted, void *d_sorted_begin, void *d_key, void *d_perm)
+{
+    const uint32_t n = (uint32_t)n_records;
+    const uint32_t n_tiles = (uint32_t)((n_records + IB_TILE - 1) / IB_TILE);
+    BamSortArgs a; memset(&a, 0, sizeof(a));
+    a.n = n; a.n_chunks = (uint32_t)((n_records + SAMREC_CHUNK - 1) / SAMREC_CHUNK);
+    a.bytes = (const uint8_t *)d_bytes; a.block_begin = (const uint64_t *)d_block_begin;
+    a.sorted = (uint8_t *)d_sorted; a.sorted_begin = (uint64_t *)d_sorted_begin;
+    uint64_t *keys[2] = {st.scratch((size_t)n * 8), st.scratch((size_t)n * 8)};
+    uint32_t *vals[2] = {st.scratch((size_t)n * 4), st.scratch((size_t)n * 4)};
+    uint32_t *d_hist = st.scratch((size_t)64 * n_tiles * 4), *d_partial = st.scratch(((size_t)64 * n_tiles / IB_TILE + 2) * 4), *d_total = st.scratch(64);
+    a.len = st.scratch((size_t)n * 4 + 4); a.partial = st.scratch((size_t)a.n_chunks * 8);
+    a.summary = st.scratch(sizeof(BamSortSummary)); a.scan_summary = st.scratch(sizeof(SamTextSummary));
+    if (st.rc) return st.rc;
+    a.key = keys[0]; a.index = vals[0];
+    uint32_t grid = (uint32_t)ctx->num_cus * 8, key_blocks = grid, pass_blocks = grid, scan_blocks = grid, write_blocks = grid;
+    { const uint64_t need = (n_records + 255) / 256; if (key_blocks > need) key_blocks = (uint32_t)need; }      // (64 bits: n may be 2^32 - 1)
+    { const uint32_t need = (n_tiles + 3) / 4; if (pass_blocks > need) pass_blocks = need; }
+    { const uint32_t need = (a.n_chunks + 3) / 4; if (scan_blocks > need) scan_blocks = need; }
+    { const uint64_t need = (n_records + 3) / 4; if (write_blocks > need) write_blocks = (uint32_t)need; }
+    BamSortSummary sum; memset(&sum, 0, sizeof(sum));
+    HIPCHK(ctx, hipMemsetAsync(a.summary, 0, sizeof(BamSortSummary), st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, st.s), SNAPGPU_E_LAUNCH);
+    snapgpu_launch_bam_sort_keys(&a, key_blocks, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipMemcpyAsync(&sum, a.summary, sizeof(BamSortSummary), hipMemcpyDeviceToHost, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    if (sum.flags) {
+        HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
+        if (const int rc = finish_timing(ctx)) return rc;
+        // the first bad record, with ITS reason (first_bad[k] is ~index, 0 where flag k was not raised)
+        int k = 0;
+        for (int j = 1; j < 3; j++) if (sum.first_bad[j] > sum.first_bad[k]) k = j;
+        return bam_sort_refuse(ctx, w, ~sum.first_bad[k], 1u << k);
+    }
+    // a digit that is the same in every key leaves the order as it is: its pass is skipped
+    const uint64_t varying = (((uint64_t)sum.ones_hi << 32) | sum.ones_lo) & (((uint64_t)sum.zeros_hi << 32) | sum.zeros_lo);
+    int cur = 0;
+    for (uint32_t shift = 0; shift < 64; shift += IB_BITS) {
+        if (!((varying >> shift) & 63ull)) continue;
+        snapgpu_launch_bam_sort_pass(keys[cur], vals[cur], n, shift, d_hist, d_partial, d_total, keys[cur ^ 1], vals[cur ^ 1], pass_blocks, st.s);
+        cur ^= 1;
+    }
+    a.perm = vals[cur];
+    snapgpu_launch_bam_sort_gather(&a, scan_blocks, write_blocks, st.s);
+    HIPCHK(ctx, hipGetLastError(), SNAPGPU_E_LAUNCH);
+    if (d_key) HIPCHK(ctx, hipMemcpyAsync(d_key, keys[cur], (size_t)n * 8, hipMemcpyDeviceToDevice, st.s), SNAPGPU_E_LAUNCH);
+    if (d_perm) HIPCHK(ctx, hipMemcpyAsync(d_perm, vals[cur], (size_t)n * 4, hipMemcpyDeviceToDevice, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipEventRecord(ctx->ev1, st.s), SNAPGPU_E_LAUNCH);
+    HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+    return finish_timing(ctx);
+}
+static int bam_sort_check(snapgpu_ctx *ctx, const std::string &w, uint64_t n_records, const void *bytes, const void *block_begin, const void *sorted, const void *sorted_begin)
+{
+    if (!ctx || !sorted_begin || (n_records && (!bytes || !block_begin || !sorted))) return fail(ctx, SNAPGPU_E_INVALID, w + ": null argument");
+    if (n_records > 0xFFFFFFFFull) return fail(ctx, SNAPGPU_E_INVALID, w + ": more than 2^32 - 1 records in one call");
+    return SNAPGPU_OK;
+}
+extern "C" int snapgpu_bam_sort_device(snapgpu_ctx *ctx, uint64_t n_records, const void *d_bytes, const void *d_block_begin, void *d_sorted, void *d_sorted_begin,
+                                       void *d_key, void *d_perm, void *stream)
+{
+    const std::string w("snapgpu_bam_sort_device");
+    int rc = bam_sort_check(ctx, w, n_records, d_bytes, d_block_begin, d_sorted, d_sorted_begin);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, stream ? (hipStream_t)stream : ctx->stream);
+    if (n_records == 0) {
+        HIPCHK(ctx, hipMemsetAsync(d_sorted_begin, 0, 8, st.s), SNAPGPU_E_LAUNCH);
+        HIPCHK(ctx, hipStreamSynchronize(st.s), SNAPGPU_E_LAUNCH);
+        return SNAPGPU_OK;
+    }
+    return bam_sort_core(ctx, w, st, n_records, d_bytes, d_block_begin, d_sorted, d_sorted_begin, d_key, d_perm);
+}
+extern "C" int snapgpu_bam_sort(snapgpu_ctx *ctx, uint64_t n_records, const uint8_t *bytes, const uint64_t *block_begin, uint8_t *sorted, uint64_t *sorted_begin,
+                                uint64_t *key, uint32_t *perm)
+{
+    const std::string w("snapgpu_bam_sort");
+    int rc = bam_sort_check(ctx, w, n_records, bytes, block_begin, sorted, sorted_begin);
+    if (rc) return rc;
+    if (n_records == 0) { sorted_begin[0] = 0; return SNAPGPU_OK; }
+    // (the extents once more here: they size the upload)
+    for (uint64_t i = 0; i < n_records; i++) {
+        if (block_begin[i + 1] < block_begin[i]) return bam_sort_refuse(ctx, w, i, BAMSORT_DECREASING);
+        if (block_begin[i + 1] - block_begin[i] < 12) return bam_sort_refuse(ctx, w, i, BAMSORT_SHORT);
+        if (block_begin[i + 1] - block_begin[i] > 0xFFFFFFFFull) return bam_sort_refuse(ctx, w, i, BAMSORT_LONG);
+    }
+    const size_t first = (size_t)block_begin[0], nb = (size_t)(block_begin[n_records] - block_begin[0]);
+    HIPCHK(ctx, hipSetDevice(ctx->device), SNAPGPU_E_NODEVICE);
+    Stage st(ctx, ctx->stream);
+    // the bytes from the first record on, at the residue mod 16 that they have on the host, so that the device sees the caller's alignments
+    const size_t in_res = (size_t)((uintptr_t)(bytes + first) & 15u), out_res = (size_t)((uintptr_t)(sorted) & 15u);
+    std::vector<uint64_t> rel((size_t)n_records + 1);
+    for (uint64_t i = 0; i <= n_records; i++) rel[(size_t)i] = block_begin[i] - first;
+    uint8_t *d_in = st.scratch(nb + in_res + 16);
+    if (d_in && !st.rc) HIPCHK(ctx, hipMemcpyAsync(d_in + in_res, bytes + first, nb, hipMemcpyHostToDevice, st.s), SNAPGPU_E_LAUNCH);
+    const void *d_bb = st.in(rel.data(), rel.size() * 8);
+    uint8_t *d_sorted = st.scratch(nb + out_res + 16);
+    void *d_sorted_begin = st.out(sorted_begin, ((size_t)n_records + 1) * 8), *d_key = st.opt_out(key, (size_t)n_records * 8), *d_perm = st.opt_out(perm, (size_t)n_records * 4);
+    if (st.rc) return st.rc;
+    if ((rc = bam_sort_core(ctx, w, st, n_records, d_in + in_res, d_bb, d_sorted + out_res, d_sorted_begin, d_key, d_perm))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(sorted, d_sorted + out_res, nb, hipMemcpyDeviceToHost, st.s), SNAPGPU_E_LAUNCH);
+    return st.download();
+}
+
 // ---- the sink of the fused calls (snapgpu_align_sam_single_text / _bam / _bgzf and their paired forms): the records of the batch are in HBM,
 // and their bytes go where a SamOut says
 static int bgzf_out_check(snapgpu_ctx *ctx, const std::string &w, const BgzfOut &z)
@@ -2992,7 +3111,9 @@ static int bgzf_tail(snapgpu_ctx *ctx, const std::string &w, Stage &st, uint64_t
 static int sam_out_in_hbm(snapgpu_ctx *ctx, const std::string &w, Stage &st, const SamTextIO &io, const uint64_t *name_off, uint32_t RL, const SamOut &out,
                           void *d_bytes, void *d_begin, uint64_t *total, bool *truncated)
 {
-    const bool keep = out.kind == SAM_OUT_BGZF;
+    const bool sort = out.kind == SAM_OUT_BAM && out.sort.on;
+    const bool keep = out.kind == SAM_OUT_BGZF || sort;
+    void *const d_sorted = d_bytes, *const d_sorted_begin = d_begin;      // (sort: the staged outputs take the sorted records)
     uint64_t cap = out.cap;
     if (keep && io.n) {
         uint64_t longest = 0;
@@ -3014,6 +3135,17 @@ static int sam_out_in_hbm(snapgpu_ctx *ctx, const std::string &w, Stage &st, con
         cap = sum.total;
     }
     *total = sum.total;
+    if (sort) {
+        // the records in coordinate order where the _bam call has them in record order; a capacity they do not fit leaves no sorted byte
+        *truncated = sum.total > out.cap;
+        const bool run = io.n && !*truncated;
+        void *d_key = run ? (void *)st.opt_out(out.sort.key, (size_t)io.lines() * 8) : nullptr, *d_perm = run ? (void *)st.opt_out(out.sort.perm, (size_t)io.lines() * 4) : nullptr;
+        if (st.rc) return st.rc;
+        if (run) { if (const int rc = bam_sort_core(ctx, w, st, io.lines(), d_bytes, d_begin, d_sorted, d_sorted_begin, d_key, d_perm)) return rc; }
+        else if (!io.n) HIPCHK(ctx, hipMemsetAsync(d_sorted_begin, 0, 8, st.s), SNAPGPU_E_LAUNCH);
+        st.limit(d_sorted_begin, run || !io.n ? (size_t)(io.lines() + 1) * 8 : 0); st.limit(d_sorted, run ? (size_t)sum.total : 0);
+        return SNAPGPU_OK;
+    }
     if (keep) return bgzf_tail(ctx, w, st, sum.total, d_bytes, out.z, truncated);
     if (!io.n) HIPCHK(ctx, hipMemsetAsync(d_begin, 0, 8, st.s), SNAPGPU_E_LAUNCH);
     st.limit(d_begin, (size_t)(io.lines() + 1) * 8); st.limit(d_bytes, (size_t)sum.written);      // only the lines that were written come down
@@ -3366,6 +3498,16 @@ extern "C" int snapgpu_align_sam_single_bam(snapgpu_ctx *ctx, uint32_t n, const 
     return align_sam_single_out_call(ctx, "snapgpu_align_sam_single_bam", n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
                                      ops_stride, record_capacity, n_records, rec_begin, flag, SamOut{SAM_OUT_BAM, byte_capacity, bytes, block_begin, bam_bytes, {}});
 }
+extern "C" int snapgpu_align_sam_single_bam_sorted(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
+                                                   const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
+                                                   const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                                   uint64_t record_capacity, uint64_t *n_records, uint64_t *rec_begin, int32_t *flag,
+                                                   uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes, uint64_t *key, uint32_t *perm)
+{
+    return align_sam_single_out_call(ctx, "snapgpu_align_sam_single_bam_sorted", n, bases, quals, offsets, front_clip, data_len, skip, use_m, adjust_primary, names, name_off,
+                                     ops_stride, record_capacity, n_records, rec_begin, flag,
+                                     SamOut{SAM_OUT_BAM, byte_capacity, bytes, block_begin, bam_bytes, {}, BamSortOut{true, key, perm}});
+}
 extern "C" int snapgpu_align_sam_single_bgzf(snapgpu_ctx *ctx, uint32_t n, const char *bases, const char *quals, const uint64_t *offsets,
                                              const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m, int adjust_primary,
                                              const char *names, const uint64_t *name_off, uint32_t ops_stride,
@@ -3396,6 +3538,16 @@ extern "C" int snapgpu_align_sam_paired_bam(snapgpu_ctx *ctx, uint32_t n_pairs, 
 {
     const SamOut out{SAM_OUT_BAM, byte_capacity, bytes, block_begin, bam_bytes, {}};
     return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bam", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt, flag, nullptr,
+                                 nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, names, name_off, &out);
+}
+extern "C" int snapgpu_align_sam_paired_bam_sorted(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
+                                                   const int32_t *front_clip, const int32_t *data_len, const uint8_t *skip, int use_m,
+                                                   const char *names, const uint64_t *name_off, uint32_t ops_stride,
+                                                   snapgpu_paired_result *results, snapgpu_paired_result *first_alt, int32_t *flag, int32_t *first_written,
+                                                   uint64_t byte_capacity, uint8_t *bytes, uint64_t *block_begin, uint64_t *bam_bytes, uint64_t *key, uint32_t *perm)
+{
+    const SamOut out{SAM_OUT_BAM, byte_capacity, bytes, block_begin, bam_bytes, {}, BamSortOut{true, key, perm}};
+    return align_sam_paired_call(ctx, "snapgpu_align_sam_paired_bam_sorted", n_pairs, bases, quals, offsets, front_clip, data_len, skip, use_m, results, first_alt, flag, nullptr,
                                  nullptr, nullptr, nullptr, ops_stride, nullptr, nullptr, nullptr, nullptr, nullptr, first_written, nullptr, names, name_off, &out);
 }
 extern "C" int snapgpu_align_sam_paired_bgzf(snapgpu_ctx *ctx, uint32_t n_pairs, const char *bases, const char *quals, const uint64_t *offsets,
